@@ -16,6 +16,15 @@ A "step" is one pass of the hot path (half-kick+drift+wrap+bin, scan, sort, pair
 bookkeeping) over all atoms.  Atoms are resident in HBM when the timed region starts.
 
 Output: ONE JSON line on rank 0.
+
+A plain run does what the headline needs: set-up, warm-up, the K timed steps, a second pass with HIP events around every kernel only when
+the window must be charged for missing cell-list rebuilds (see "timed_window" below), the outputs (--dump-outputs) and the line.  Everything
+else it measures or checks (per-kernel times, roofline, streaming kernels, steady state, call overhead, pair energies on every step, the
+thermalised box, the CPU baseline with same-run parity) runs with --full only.
+
+--dump-outputs DIR writes, after the timed steps, what their last step left for a caller: x, y, z, vx, vy, vz, fx, fy, fz (float64, in
+original atom order) of every atom, or of a fixed seeded sample of DUMP_SAMPLE atoms on larger boxes (atom_index.npy says which), and the
+step's statistics (engTot.npy, ... one float64 scalar each): DIR/<name>.npy, well under 64 MB in all.
 """
 import argparse
 import json
@@ -61,8 +70,17 @@ def parse():
     ap.add_argument("--no-steady", action="store_true", help="skip the steady_state / call_overhead blocks")
     ap.add_argument("--steady-steps", type=int, default=300)
     ap.add_argument("--dry-run", action="store_true", help="launcher check: every rank reports its environment through the control plane and exits without touching a GPU")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel times / roofline, steady state, call overhead, "
+                                                         "energies on every step, the thermalised box, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
+
+DUMP_SAMPLE = 1 << 18       # atoms written by --dump-outputs on larger boxes (9 float64 arrays + the index: 21 MB)
+DUMP_SEED = 20240502
+DUMP_ATOM_KEYS = ("x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz")
+DUMP_STATS = ("step", "time", "engTot", "engKin", "engVdW", "engCoul", "engElecField", "engTemp", "engPot", "temperature", "pressure",
+              "engBond", "engAngle", "engCoulRec", "engCoulConst", "pairs_dropped", "nose_chit", "nose_conint")
 
 EXIT_RCCL_FAILED = 3        # one GPU per rank and RCCL did not come up
 EXIT_REHEARSAL = 4          # fewer GPUs than ranks: the line printed is a rehearsal (host-staged halo), never a result
@@ -199,6 +217,32 @@ def cpu_baseline(case, steps):
             "sample": "%d steps of the same %d-atom workload, linked-cell serial path, 1 thread; %.2f s wall; %.3f Matom-steps/s"
                       % (steps, n, wall, n * steps / wall / 1e6),
             "host_cpu": _cpu_model(), "host_cores": os.cpu_count(), "_energies": energies}
+
+
+def dump_outputs(directory, eng, st, n_atoms, cp):
+    """--dump-outputs: the per-atom state the last timed step left (every atom, or the same seeded sample of DUMP_SAMPLE atoms on every run)
+    and its statistics, float64.  A slab rank holds its own atoms only: the ranks pool their part of the sample, rank 0 writes."""
+    import numpy as np
+    if n_atoms <= DUMP_SAMPLE:
+        idx = np.arange(n_atoms)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_atoms, DUMP_SAMPLE, replace=False))
+    s = eng.state(DUMP_ATOM_KEYS)
+    vals = np.stack([s[k][idx] for k in DUMP_ATOM_KEYS])
+    if cp.world > 1:
+        own = np.flatnonzero(~np.isnan(vals[0]))
+        parts = cp.all_gather({"i": own.astype(np.int64), "v": np.ascontiguousarray(vals[:, own])})
+        vals = np.full_like(vals, np.nan)
+        for p in parts:
+            vals[:, p["i"]] = p["v"]
+    if cp.rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "atom_index.npy"), idx.astype(np.float64))
+    for k, v in zip(DUMP_ATOM_KEYS, vals):
+        np.save(os.path.join(directory, k + ".npy"), v.astype(np.float64))
+    for k in DUMP_STATS:
+        np.save(os.path.join(directory, k + ".npy"), np.array(float(st[k]), dtype=np.float64))
 
 
 def _cpu_model():
@@ -342,10 +386,17 @@ def main():
         wall = cp.all_max(wall)
     st = eng.stats()
     rebuilds_in_window = st["rebuilds"] - st0["rebuilds"]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, eng, st, n_atoms, cp)
     # ---- second pass over the same number of steps with HIP events around every kernel (on the engine's own stream):
-    #      source of the per-kernel durations / the roofline figure; its wall time is reported separately
+    #      source of the per-kernel durations / the roofline figure; its wall time is reported separately.  A plain run makes it only when
+    #      the timed window holds fewer rebuilds than its fair share (the missing ones are charged at the cost this pass measures)
+    K = max(int(st["sort_interval"]), 1)
+    charge = int(K > 1 and rebuilds_in_window < a.steps / K)
+    if world > 1:
+        charge = cp.all_max(charge)
     ktimes, wall_events = {}, None
-    if not a.no_profile:
+    if not a.no_profile and (a.full or charge):
         eng.set_profile(1)
         eng.reset_kernel_times()
         barrier()
@@ -355,7 +406,7 @@ def main():
         wall_events = (time.perf_counter() - t0) / max(a.steps, 2 * int(st["sort_interval"]) + 2) * a.steps
         ktimes = eng.kernel_times()
         eng.set_profile(0)
-    profile = 0 if a.no_profile else 1
+    profile = 1 if wall_events is not None else 0
     if world > 1 and profile:
         # slowest rank per kernel
         names = sorted(ktimes)
@@ -365,7 +416,6 @@ def main():
 
     if rank == 0:
         dt_ps = case["dt"]
-        K = max(int(st["sort_interval"]), 1)
         out = {
             "metric": "ns_per_day", "value": None, "unit": "ns/day", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": None, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -451,7 +501,7 @@ def main():
                     t_k = kern[k]["avg_us"] * 1e-6
                     stream[k] = {"bytes_per_atom": bb, "avg_us": kern[k]["avg_us"], "gbps": bb * n_local / t_k / 1e9, "hbm_frac": bb * n_local / t_k / HBM_PEAK}
             out["streaming"] = stream
-        if world == 1 and a.emulate_ranks <= 1 and not a.no_steady:
+        if a.full and world == 1 and a.emulate_ranks <= 1 and not a.no_steady:
             # (a) steady state: the timed window above is whatever --steps / --warmup the caller chose (the driver: 20 after 5 - inside the clock ramp of a
             # fresh process); this is the same engine a few hundred steps later, one long call.  (b) call overhead: the reference's loop is per step
             # (main.cu:281-410), so a caller that couples something to every step calls aztot_step(1) - each call ends with the deferred half-kick,
@@ -487,7 +537,7 @@ def main():
                                         "step_stat_over_long_call": (w2 / (ncall * stat)) / (w / ns)}
             except Exception as ex:   # noqa: BLE001
                 out["steady_state"] = "failed: %r" % (ex,)
-        if world == 1 and not a.no_cpu_baseline and a.emulate_ranks <= 1:
+        if a.full and world == 1 and not a.no_cpu_baseline and a.emulate_ranks <= 1:
             # the same timed region with pair energies booked on every step (options.energies_every_step): what a caller who asks for statistics after every
             # single step would see
             try:

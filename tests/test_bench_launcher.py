@@ -75,8 +75,8 @@ def test_more_ranks_than_gpus_is_a_rehearsal_and_says_so_in_the_exit_code():
 
 @pytest.mark.gpu
 def test_one_gpu_line_is_what_it_was():
-    """--gpus 1 runs in the process itself (no launcher): metric, unit and the blocks the driver reads are there"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+    """--gpus 1 runs in the process itself (no launcher): metric, unit and the blocks the driver reads are there (the per-kernel blocks with --full)"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600,
                        env=clean_env())
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
@@ -99,7 +99,7 @@ def test_one_gpu_line_is_what_it_was():
 @pytest.mark.gpu
 def test_cpu_baseline_leg_and_same_run_parity():
     """the serial CPU path timed beside the GPU in the same run (the reference's own code when its binary travelled, else our port), with the energies of both"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C2", "--steps", "20", "--warmup", "5", "--no-steady", "--cpu-steps", "3"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C2", "--steps", "20", "--warmup", "5", "--no-steady", "--cpu-steps", "3", "--full"], capture_output=True, text=True,
                        timeout=600, env=clean_env())
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
@@ -109,6 +109,32 @@ def test_cpu_baseline_leg_and_same_run_parity():
     assert c["cores"] == 1 and c["kind"] in ("reference", "port") and c["value"] > 0
     if c["kind"] == "reference":
         assert c["same_run_parity"]["engTot_rel_diff"] < 1e-11, c["same_run_parity"]
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full the line holds the headline only; --dump-outputs writes the last timed step's per-atom state and statistics as float64 .npy"""
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C2", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d)], capture_output=True,
+                       text=True, timeout=600, env=clean_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["metric"] == "ns_per_day" and out["unit"] == "ns/day" and out["higher_is_better"] is True and out["dtype"] == "f64" and out["steps"] == 20
+    assert out["value"] > 0 and abs(out["value"] - 20 * 0.001 * 86400.0 / (out["ms_per_step"] * 20)) < 1e-9 * out["value"]
+    for k in ("steady_state", "call_overhead", "thermalised", "cpu_baseline"):
+        assert k not in out, k
+    n = out["config"]["n_atoms"]
+    import numpy as np
+    total = 0
+    for k in ("atom_index", "x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz"):
+        a = np.load(d / (k + ".npy"))
+        total += a.nbytes
+        assert a.dtype == np.float64 and a.shape == (n,) and np.isfinite(a).all(), k
+    assert np.array_equal(np.load(d / "atom_index.npy"), np.arange(n))
+    assert float(np.load(d / "engTot.npy")) == out["energy"]["engTot"] and float(np.load(d / "engVdW.npy")) == out["energy"]["engVdW"]
+    assert total < 64 << 20
 
 
 def test_the_launcher_ends_ranks_that_hang():

@@ -13,7 +13,7 @@ import pytest
 
 from aztotmd_amd import api, inputs
 from oracle import oracle
-from util import FRC, VEL, add_random_dynamics, family_with_coulomb, mixed_case, per_atom_err, random_case, rel_err
+from util import FRC, VEL, add_random_dynamics, family_with_coulomb, mixed_case, per_atom_err, random_case, reference_dumps, rel_err
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -793,33 +793,15 @@ def test_dense_cells_and_odd_shapes(case_name):
         assert st["pairs_dropped"] == sto["nDropped"]
 
 
-@pytest.mark.skipif(not oracle.ref_available(), reason="oracle/_ref/ref_driver did not travel to this machine")
 @pytest.mark.parametrize("name", ["lj_nose", "buck", "bmhs", "fennel_field", "direct", "ewald", "bonded"])
 def test_hip_path_against_the_reference_binary(name):
     """No oracle in between: the HIP hot path against the reference's OWN compiled serial code (oracle/_ref/ref_driver: box.cpp,
     vdw.cpp, elec.cpp, cell_list.cpp, integrators.cpp, temperature.cpp, bonds.cpp, angles.cpp built where they lie) on the same
-    inputs - forces at step 0 to 1e-11, trajectory after 30 steps to 1e-9 (the north star's tolerance), energies to 1e-10."""
-    if name == "lj_nose":
-        case = inputs.lj_case((5, 5, 5), a=5.26, seed=21, rc=6.5, cell_list=6.5, T=140.0, vel_T=100.0)
-        case.update(tstat_type=1, tau=0.08, nEq=12, freqEq=4)
-    elif name == "buck":
-        case = mixed_case("buck", seed=5)
-    elif name == "bmhs":
-        case = mixed_case("bmhs", seed=6)
-    elif name == "fennel_field":
-        case = mixed_case("lnjs+fenn+field", seed=7)
-        case.update(Uy=0.0, Uz=0.0)       # the serial clear_force knows only dU/dx (integrators.cpp:17-39); y, z are the GPU path's
-    elif name == "direct":
-        case = mixed_case("lnjs+dir", seed=8)
-    elif name == "ewald":
-        case = ewald_case(ewald_k=(5, 6, 7))
-    else:
-        case = inputs.molecular_case((9, 9, 9), seed=31, charges=(-0.2, 0.1), elec="fenn")
-    case = dict(case)
-    case.update(nsteps=30, dump=[0, 30])
-    ref = oracle.run_ref(case)
+    inputs - forces at step 0 to 1e-11, trajectory after 30 steps to 1e-9 (the north star's tolerance), energies to 1e-10.  The binary's
+    dumps are stored in tests/golden/ref_dumps/ (tests/util.py reference_case has the inputs); where it is present it is run again."""
+    case, dumps = reference_dumps("gpu", name)
     e = engine(case)
-    d0, d30 = ref["dumps"][0], ref["dumps"][30]
+    d0, d30 = dumps[0], dumps[30]
     s = e.state()
     for k in FKEYS:
         assert rel_err(s[k], d0[k]) < 1e-11, (name, k)

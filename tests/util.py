@@ -172,10 +172,10 @@ def add_random_dynamics(case, seed):
 
 
 def materialise_case_study(k, directory, nstep=None):
-    """Write the reference's shipped example input k (1 or 2) - stored as data in tests/golden/case_study_k.npz by
+    """Write the reference's shipped example input k (1, 2, or "src": the set beside its sources) - stored as data in tests/golden/case_study_k.npz by
     tests/golden/make_case_studies.py - back into `directory` as atoms.xyz / field.txt / control.txt / cuda.txt."""
     import os
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "case_study_%d.npz" % k))
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "case_study_%s.npz" % k))
     os.makedirs(directory, exist_ok=True)
     names, idx, pos = [str(s) for s in z["names"]], z["name_idx"], z["pos"]
     eol = "\r\n" if bool(z["crlf"]) else "\n"           # the shipped files have DOS line ends: kept, the parser must cope
@@ -190,6 +190,90 @@ def materialise_case_study(k, directory, nstep=None):
         with open(os.path.join(directory, fn), "wb") as f:
             f.write(data)
     return directory
+
+
+REF_CPU = ("buck", "bmhs", "p746", "lnjs+dir", "lnjs+fenn+field", "bonded", "ewald")
+REF_GPU = ("lj_nose", "buck", "bmhs", "fennel_field", "direct", "ewald", "bonded")
+
+
+def reference_case(side, name):
+    """Inputs of the tests that hold a path against the reference binary's own dumps: side "cpu" (test_oracle_golden.py, the oracle;
+    name in REF_CPU) or "gpu" (test_gpu_parity.py, the HIP path; name in REF_GPU).  tests/golden/make_ref_dumps.py runs the binary on
+    exactly these cases."""
+    if side == "cpu" and name == "bonded":
+        case = inputs.molecular_case((6, 6, 7), seed=5, charges=(-0.3, 0.15), elec="dir", r_real=7.0)
+        case.update(nsteps=30, dump=[0, 30])
+    elif side == "cpu" and name == "ewald":
+        case = inputs.lj_case((6, 5, 4), a=5.4, seed=2, rc=5.2, cell_list=5.2, charges=(0.5, -0.5), elec="fenn", r_real=5.2, alpha=0.5, vel_T=200.0)
+        case.update(elec_type=2, ewald_k=(7, 5, 6), nsteps=10, dump=[0, 10])
+    elif side == "cpu":
+        # mixed two-species liquid, 20 steps
+        case = inputs.lj_case((5, 5, 5), a=5.6, seed=99, rc=7.0, vel_T=90.0)
+        sp = [(39.9, 0.0), (20.2, 0.0)]
+        case["types"] = (np.arange(500) % 2).astype(np.int32)
+        if name == "buck":
+            vdw = [(0, 0, 2, 7.0, [1822.0, 0.3, 63.0]), (0, 1, 2, 6.5, [1400.0, 0.29, 40.0]), (1, 1, 2, 6.0, [900.0, 0.28, 20.0])]
+        elif name == "bmhs":
+            vdw = [(a, b, 4, 7.0, [0.25, 3.1, 2.4 + 0.1 * a, 60.0, 80.0]) for a, b in ((0, 0), (0, 1), (1, 1))]
+        elif name == "p746":
+            vdw = [(a, b, 3, 7.0, [3000.0, 1.0, 20.0 + 5 * b]) for a, b in ((0, 0), (0, 1), (1, 1))]
+        else:
+            vdw = [(a, b, 1, 7.0, [0.01006, 3.3952]) for a, b in ((0, 0), (0, 1), (1, 1))]
+            sp = [(39.9, 0.3), (20.2, -0.3)]
+            if "dir" in name:
+                case.update(elec_type=1, rReal=7.0)
+            else:
+                case.update(elec_type=3, rReal=7.0, alpha=0.35, Ux=0.02)
+        case.update(species=sp, vdw=vdw, nsteps=20, dump=[0, 20])
+    else:
+        if name == "lj_nose":
+            case = inputs.lj_case((5, 5, 5), a=5.26, seed=21, rc=6.5, cell_list=6.5, T=140.0, vel_T=100.0)
+            case.update(tstat_type=1, tau=0.08, nEq=12, freqEq=4)
+        elif name == "buck":
+            case = mixed_case("buck", seed=5)
+        elif name == "bmhs":
+            case = mixed_case("bmhs", seed=6)
+        elif name == "fennel_field":
+            case = mixed_case("lnjs+fenn+field", seed=7)
+            case.update(Uy=0.0, Uz=0.0)       # the serial clear_force knows only dU/dx (integrators.cpp:17-39); y, z are the GPU path's
+        elif name == "direct":
+            case = mixed_case("lnjs+dir", seed=8)
+        elif name == "ewald":
+            case = inputs.lj_case((5, 5, 5), a=5.26, seed=11, rc=6.5, cell_list=6.5, charges=(0.4, -0.4), elec="fenn", r_real=6.5, alpha=0.45, vel_T=80.0)
+            case.update(elec_type=2, ewald_k=(5, 6, 7))
+        else:
+            case = inputs.molecular_case((9, 9, 9), seed=31, charges=(-0.2, 0.1), elec="fenn")
+        case = dict(case)
+        case.update(nsteps=30, dump=[0, 30])
+    return case
+
+
+def reference_fixture_path(side, name):
+    import os
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_dumps", "%s_%s.npz" % (side, name.replace("+", "_")))
+
+
+def reference_dumps(side, name):
+    """(case, {step: {field: value}}): the reference binary's dumps of reference_case(side, name) as tests/golden/make_ref_dumps.py stored
+    them, so that the comparison needs nothing outside the repository.  Where the binary itself is present (oracle/_ref/ref_driver) it is
+    run on the spot as well and must reproduce the fixture bit for bit."""
+    from oracle import casefile, oracle
+    case = reference_case(side, name)
+    z = np.load(reference_fixture_path(side, name))
+    for k in ("x", "y", "z", "vx", "vy", "vz"):
+        assert np.array_equal(case[k], z["in_" + k]), "the case generator drifted away from the committed fixture"
+    dumps = {}
+    for st in z["steps"].tolist():
+        d = dict(zip(casefile.ENERGY_FIELDS, z["e_%d" % st].tolist()))
+        for k in ("x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz"):
+            d[k] = z["%s_%d" % (k, st)]
+        dumps[st] = d
+    if oracle.ref_available():
+        live = oracle.run_ref(case)["dumps"]
+        for st, d in dumps.items():
+            for k, v in d.items():
+                assert np.array_equal(live[st][k], v, equal_nan=True), ("the reference binary no longer reproduces the fixture", side, name, st, k)
+    return case, dumps
 
 
 def case_from_parsed(o, seed=12345):
