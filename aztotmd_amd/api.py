@@ -90,10 +90,13 @@ class _State(C.Structure):
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64))
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, C.c_int)
 
-EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "aztot_model_create", "aztot_model_set_bonded", "aztot_model_query", "aztot_model_species_name", "aztot_free_md", "aztot_default_options",
+EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "aztot_model_create", "aztot_model_set_bonded", "aztot_model_query", "aztot_model_species_name", "aztot_model_nucleus_name", "aztot_free_md", "aztot_default_options",
            "aztot_init_device", "aztot_free_device", "aztot_step", "aztot_sync", "aztot_forces", "aztot_get_stats", "aztot_species_crossings", "aztot_md_to_host",
            "aztot_set_state", "aztot_get_clock", "aztot_set_clock", "aztot_cell_table", "aztot_kernel_times", "aztot_reset_kernel_times", "aztot_set_profile", "aztot_comm_id_bytes", "aztot_comm_make_id", "aztot_comm_selftest", "aztot_comm_ranks",
-           "aztot_init_device_slab", "aztot_last_error", "aztot_version")
+           "aztot_init_device_slab", "aztot_rdf_setup", "aztot_rdf_sample", "aztot_rdf_reset", "aztot_rdf_shape", "aztot_rdf_counts", "aztot_rdf_values",
+           "aztot_last_error", "aztot_version")
+
+RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
 
 
 def library_path():
@@ -164,6 +167,14 @@ def lib():
         L.aztot_comm_make_id.argtypes = [C.c_void_p]
         L.aztot_comm_selftest.argtypes = [C.c_int]
         L.aztot_comm_ranks.argtypes = [C.c_void_p]
+        L.aztot_model_species_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+        L.aztot_model_nucleus_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+        L.aztot_rdf_setup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
+        L.aztot_rdf_sample.argtypes = [C.c_void_p]
+        L.aztot_rdf_reset.argtypes = [C.c_void_p]
+        L.aztot_rdf_shape.argtypes = [C.c_void_p, C.c_int, _ip, _ip]
+        L.aztot_rdf_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int]
+        L.aztot_rdf_values.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -265,6 +276,17 @@ class Model:
             out[0] = float(seed)
         _check(lib().aztot_model_query(self.h, key.encode(), out.ctypes.data_as(_dp), n))
         return out[:n]
+
+    def species_name(self, i):
+        buf = C.create_string_buffer(64)
+        _check(lib().aztot_model_species_name(self.h, int(i), buf, 64))
+        return buf.value.decode()
+
+    def nucleus_name(self, i):
+        """name of nucleus i (aztot_model_nucleus_name); query("nuclei") gives the nucleus of each species"""
+        buf = C.create_string_buffer(64)
+        _check(lib().aztot_model_nucleus_name(self.h, int(i), buf, 64))
+        return buf.value.decode()
 
     def close(self):
         if self.h:
@@ -442,6 +464,43 @@ class Engine:
 
     def set_profile(self, on):
         _check(lib().aztot_set_profile(self.h, int(bool(on))))
+
+    # ---- radial distribution functions (aztot_rdf_*) ----
+    def rdf_setup(self, rmax, dr, nuclei=False):
+        """(re)allocate and zero the RDF histograms; returns the number of bins, (int)(min(rmax, L_x) / dr)"""
+        return _check(lib().aztot_rdf_setup(self.h, float(rmax), float(dr), int(bool(nuclei))))
+
+    def rdf_sample(self):
+        _check(lib().aztot_rdf_sample(self.h))
+
+    def rdf_reset(self):
+        _check(lib().aztot_rdf_reset(self.h))
+
+    def _rdf_shape(self, kind):
+        nb, npair = C.c_int32(), C.c_int32()
+        _check(lib().aztot_rdf_shape(self.h, RDF_KINDS[kind], C.byref(nb), C.byref(npair)))
+        return nb.value, npair.value
+
+    def rdf_counts(self, kind="species"):
+        """(samples, counts[n_bins, n_pairs]) - uint64 totals, pairs in the column order of rdf.dat"""
+        nb, npair = self._rdf_shape(kind)
+        out = np.zeros(max(nb * npair, 1), dtype=np.uint64)
+        samples = C.c_int64()
+        _check(lib().aztot_rdf_counts(self.h, RDF_KINDS[kind], C.byref(samples), out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size))
+        return samples.value, out[:nb * npair].reshape(nb, npair)
+
+    def rdf(self, kind="species"):
+        """(r[n_bins], g[n_bins, n_pairs], pair_names): bin centres, normalised g(r) (copy_rdf / out_rdf) and the 'A-B' column names"""
+        nb, npair = self._rdf_shape(kind)
+        r = np.zeros(max(nb, 1))
+        g = np.zeros(max(nb * npair, 1))
+        _check(lib().aztot_rdf_values(self.h, RDF_KINDS[kind], r.ctypes.data_as(_dp), g.ctypes.data_as(_dp), g.size))
+        if kind == "species":
+            names = [self.model.species_name(i) for i in range(int(self.model.query("n_species")[0]))]
+        else:
+            names = [self.model.nucleus_name(i) for i in range(int(self.model.query("n_nuclei")[0]))]
+        pairs = ["%s-%s" % (names[a], names[b]) for a in range(len(names)) for b in range(a, len(names))]
+        return r[:nb], g[:nb * npair].reshape(nb, npair), pairs
 
     def close(self):
         if getattr(self, "h", None):

@@ -36,6 +36,7 @@ template <typename F>
 int guarded(F&& f)
 {
     try { f(); g_err.clear(); return AZTOT_OK; }
+    catch (const ArgError& e) { return fail(AZTOT_ERR_ARG, e.what()); }
     catch (const std::exception& e) { return fail(classify(e.what()), e.what()); }
     catch (...) { return fail(AZTOT_ERR_ARG, "unknown exception"); }
 }
@@ -99,6 +100,15 @@ int aztot_model_species_name(const aztot_model* m, int i, char* buf, int cap)
     return AZTOT_OK;
 }
 
+int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
+{
+    if (!m || !buf || cap <= 0) return fail(AZTOT_ERR_ARG, "bad argument");
+    const Nuclei n = nuclei_of(m->m);
+    if (i < 0 || i >= (int)n.names.size()) return fail(AZTOT_ERR_ARG, "bad argument");
+    std::snprintf(buf, (size_t)cap, "%s", n.names[i].c_str());
+    return AZTOT_OK;
+}
+
 // Keys (all values returned as doubles):
 //  n_atoms n_species box dt nstep nequil eqfreq temperature tstat_type elec_type r_real alpha scale scale2 daipi2
 //  rmax r2max degfree tkin cell_list use_cell_list stat init_vel elecfield nthread kB m_scale fcoul
@@ -107,6 +117,8 @@ int aztot_model_species_name(const aztot_model* m, int i, char* buf, int cap)
 //  ewald (kx, ky, kz, mr4a2, rkcut2, engElec1, number of k-vectors)  kvecs (l, m, n, rkx, rky, rkz, akk per k-vector)
 //  n_bonded (bond types, angle types, bonds, angles)  bond_types (type, spec1, spec2, p0..p4)  angle_types (type, central, k, cos0)
 //  bonds (at1, at2, type id per bond, after the turn of read_bondlist)  angles (central, lig1, lig2, type id)
+//  rdf (present, rmax, dr, every, out_every, nucl: the 'rdf' line of control.txt; present = 0 without one)
+//  nuclei (nucleus index of each species)  n_nuclei
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -167,6 +179,9 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             for (size_t i = 0; i < m.bondA.size(); i++) { v.push_back(m.bondA[i]); v.push_back(m.bondB[i]); v.push_back(m.bondT[i]); }
         else if (k == "angles")
             for (size_t i = 0; i < m.angC.size(); i++) { v.push_back(m.angC[i]); v.push_back(m.angL1[i]); v.push_back(m.angL2[i]); v.push_back(m.angT[i]); }
+        else if (k == "rdf") v = {(double)m.rdf_present, m.rdf_rmax, m.rdf_dr, (double)m.rdf_every, (double)m.rdf_out_every, (double)m.rdf_nucl};
+        else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
+        else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
         else if (k == "x") per_atom(m.x);
         else if (k == "y") per_atom(m.y);
@@ -378,6 +393,71 @@ int aztot_comm_ranks(aztot_md* md)
 int aztot_comm_selftest(int device)
 {
     return guarded([&] { RcclExchanger::selftest(device); });
+}
+
+int aztot_rdf_setup(aztot_md* md, double rmax, double dr, int nuclei)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int n = 0;
+    const int rc = guarded([&] { n = md->eng->rdf_setup(rmax, dr, nuclei != 0); });
+    return rc < 0 ? rc : n;
+}
+
+int aztot_rdf_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->rdf_sample(); });
+}
+
+int aztot_rdf_reset(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->rdf_reset(); });
+}
+
+int aztot_rdf_shape(aztot_md* md, int kind, int* n_bins, int* n_pairs)
+{
+    if (!md || !md->eng || !n_bins || !n_pairs) return fail(AZTOT_ERR_ARG, "null argument");
+    long long samples = 0;
+    return guarded([&] { md->eng->rdf_counts(kind, *n_bins, *n_pairs, samples, nullptr); });
+}
+
+int aztot_rdf_counts(aztot_md* md, int kind, int64_t* samples, uint64_t* counts, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, np = 0;
+        long long s = 0;
+        md->eng->rdf_counts(kind, nb, np, s, nullptr);
+        need = nb * np;
+        if (samples) *samples = s;
+        if (counts && cap >= need)
+        {
+            std::vector<unsigned long long> c;
+            md->eng->rdf_counts(kind, nb, np, s, &c);
+            for (int k = 0; k < need; k++) counts[k] = c[k];
+        }
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_rdf_values(aztot_md* md, int kind, double* r, double* g, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, np = 0;
+        long long s = 0;
+        md->eng->rdf_counts(kind, nb, np, s, nullptr);
+        need = nb * np;
+        if (cap < need) return;
+        std::vector<double> rv, gv;
+        md->eng->rdf_values(kind, rv, gv);
+        if (r) std::memcpy(r, rv.data(), sizeof(double) * rv.size());
+        if (g) std::memcpy(g, gv.data(), sizeof(double) * gv.size());
+    });
+    return rc < 0 ? rc : need;
 }
 
 }  // extern "C"

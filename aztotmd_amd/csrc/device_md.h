@@ -168,4 +168,18 @@ struct DevStats
     unsigned long long specCross[kSpecCap * 6];   // per species: crossings of the walls Xn, Xp, Yn, Yp, Zn, Zp (specAcBoxNeg/Pos, cuStruct.h)
 };
 
+// private cell grid and histogram shape of the RDF sampler (rdf.hip.h)
+struct RdfGrid
+{
+    int nc[3];                  // cells per axis (edge L / nc >= rmax)
+    int nCell;
+    int halfShell;              // 1: every axis has >= 3 cells, the 13 forward neighbours + the own cell visit every pair once; 0: each distinct cell once, j > i
+    double L[3], invL[3], half[3], icsz[3];
+    double r2max, idr;          // rmax^2 and 1 / dr (fp64, the bin rule of the C ABI)
+    int nBins;
+    int nSpec, nPairS;          // species and their pairs (upper-triangular, row-major: cuStat.cu:479-486)
+    int nNucl, nPairN;          // nuclei and their pairs (0: no nuclei histogram)
+    int nucl[kSpecCap];         // nucleus of each species
+};
+
 }  // namespace aztot

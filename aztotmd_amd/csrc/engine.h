@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,12 @@ namespace aztot {
 
 struct Counts;
 struct PairLists;
+
+// a caller error that the C ABI reports as AZTOT_ERR_ARG (capi.cpp: guarded)
+struct ArgError : std::runtime_error
+{
+    using std::runtime_error::runtime_error;
+};
 
 struct KernelTimer
 {
@@ -133,6 +140,14 @@ public:
     int n_atoms_global() const { return model_.nAt; }
     int comm_ranks() const { return xch_ ? xch_->comm_ranks() : 0; }
     void sync_all();                        // everything queued or deferred by earlier calls has happened when this returns (aztot_sync)
+
+    // radial distribution functions (rdf.hip.h; aztot_rdf_* in include/aztot.h): a private cell grid over the current positions, integer totals
+    int rdf_setup(double rmax, double dr, bool nuclei);     // (re)allocates and zeroes; returns the number of bins
+    void rdf_sample();                                       // one sample of the configuration as aztot_md_to_host would return it
+    void rdf_reset();
+    // kind 0 species, 1 nuclei: bins, pairs, samples and (if counts) the totals [bin][pair]
+    void rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts);
+    void rdf_values(int kind, std::vector<double>& r, std::vector<double>& g);     // bin centres and normalised g(r), same layout
 
 private:
     void step_body(int nsteps);
@@ -277,6 +292,24 @@ private:
     std::vector<PendingEvent> pending_;
     std::vector<hipEvent_t> eventPool_;
     void drain_events();
+
+    struct RdfState
+    {
+        double rmax = 0, dr = 0;
+        int nBins = 0;                  // 0: not set up
+        bool nuclei = false;
+        long long samples = 0;
+        int copies = 0;                 // LDS sub-histograms per workgroup of k_rdf_pairs (0: straight into the totals)
+        int blocks = 0;
+        std::vector<void*> allocs;
+        int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
+        double *x = nullptr, *y = nullptr, *z = nullptr;
+        unsigned long long *histS = nullptr, *histN = nullptr;
+        Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
+        DevStats* scanStats = nullptr;
+        RdfGrid grid{};
+    } rdf_;
+    void rdf_free();
 
     // hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was captured in
     // (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue swaps

@@ -16,6 +16,7 @@
 #include "kernels.hip.h"
 #include "pair_tile.hip.h"
 #include "pair_list.hip.h"
+#include "rdf.hip.h"
 #include "slab.hip.h"
 
 namespace aztot {
@@ -379,6 +380,7 @@ void Engine::release()
     for (void* p : allocs_) (void)hipFree(p);
     allocs_.clear();
     free_lists();
+    rdf_free();
     if (evIntegrated_) (void)hipEventDestroy(evIntegrated_);
     if (evHalo_) (void)hipEventDestroy(evHalo_);
     evIntegrated_ = evHalo_ = nullptr;
@@ -2047,6 +2049,169 @@ void Engine::set_state(const aztot_state& in)
     {   // from now on the sort carries the per-atom thermostat state along; a captured graph has the old carry mode baked in
         thermoTouched_ = true;
         destroy_graphs();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Radial distribution functions (rdf.hip.h).  Launched on the engine's stream between two aztot_step calls, never inside a captured step; they read
+// the current per-atom arrays and write only their own buffers.
+// ---------------------------------------------------------------------------------------------------
+void Engine::rdf_free()
+{
+    if (!rdf_.allocs.empty() && stream_) (void)hipStreamSynchronize(stream_);
+    for (void* p : rdf_.allocs) (void)hipFree(p);
+    rdf_ = RdfState();
+}
+
+int Engine::rdf_setup(double rmax, double dr, bool nuclei)
+{
+    if (nranks_ > 1) throw std::runtime_error("out of scope: radial distribution functions of a slab-decomposed (multi-GPU) run are not supported");
+    if (!(rmax > 0.0) || !(dr > 0.0)) throw ArgError("rdf: rmax and dr must be positive");
+    // bins as init_rdf (rdf.cpp:40-48, what sizes the GPU path's buffer): min(rmax, L_x) / dr
+    const double nb = std::min(rmax, model_.L[0]) * (1.0 / dr);
+    if (!(nb >= 1.0)) throw ArgError("rdf: no bin (dr > min(rmax, box x edge))");
+    const Nuclei nu = nuclei_of(model_);
+    const int nSpec = model_.nSpec(), nNucl = (int)nu.names.size();
+    const long long nPairS = (long long)nSpec * (nSpec + 1) / 2, nPairN = nuclei ? (long long)nNucl * (nNucl + 1) / 2 : 0;
+    if (nb * (double)(nPairS + nPairN) > (double)(1 << 28)) throw ArgError("rdf: too many bins (min(rmax, box x edge) / dr x pairs > 2^28)");
+    settle();
+    sync();
+    rdf_free();
+    RdfState& R = rdf_;
+    R.rmax = rmax; R.dr = dr; R.nuclei = nuclei; R.nBins = (int)nb;
+    RdfGrid& G = R.grid;
+    const int N = model_.nAt;
+    // cells with an edge >= rmax (a hair more: the cell of a coordinate is floor(x * nc / L) in fp64), at most about N of them (a dilute gas in a
+    // large box would otherwise get mostly empty cells)
+    long long nc[3];
+    for (int k = 0; k < 3; k++) nc[k] = std::max(1LL, (long long)std::floor(model_.L[k] / (rmax * (1.0 + 1e-9))));
+    const long long cellCap = std::max(27, N);
+    while (nc[0] * nc[1] * nc[2] > cellCap)
+    {
+        const int k = (nc[0] >= nc[1] && nc[0] >= nc[2]) ? 0 : (nc[1] >= nc[2] ? 1 : 2);
+        nc[k] = std::max(1LL, nc[k] * 3 / 4);
+    }
+    for (int k = 0; k < 3; k++)
+    {
+        G.nc[k] = (int)nc[k];
+        G.L[k] = model_.L[k]; G.invL[k] = P_.invL[k]; G.half[k] = P_.half[k];
+        G.icsz[k] = (double)nc[k] / model_.L[k];
+    }
+    G.nCell = G.nc[0] * G.nc[1] * G.nc[2];
+    G.halfShell = (G.nc[0] >= 3 && G.nc[1] >= 3 && G.nc[2] >= 3) ? 1 : 0;
+    G.r2max = rmax * rmax; G.idr = 1.0 / dr; G.nBins = R.nBins;
+    G.nSpec = nSpec; G.nPairS = (int)nPairS;
+    G.nNucl = nNucl; G.nPairN = (int)nPairN;
+    for (int t = 0; t < kSpecCap; t++) G.nucl[t] = t < nSpec ? nu.of[t] : 0;
+    const size_t nEnt = (size_t)R.nBins * (size_t)(nPairS + nPairN);
+    R.copies = (4 * nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget) ? 4 : (nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget ? 1 : 0);
+    R.blocks = std::max(1, std::min(kRdfMaxBlocks, div_up(N, kBlock)));
+    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 8))); R.allocs.push_back(p); return p; };
+    const size_t n = (size_t)std::max(N, 1);
+    R.cellOf = (int32_t*)alloc(n * 4); R.rankOf = (int32_t*)alloc(n * 4); R.kind = (int32_t*)alloc(n * 4);
+    R.x = (double*)alloc(n * 8); R.y = (double*)alloc(n * 8); R.z = (double*)alloc(n * 8);
+    R.cellCount = (int32_t*)alloc((size_t)G.nCell * 4);
+    R.cellStart = (int32_t*)alloc((size_t)(G.nCell + 1) * 4);
+    R.chunkTot = (int32_t*)alloc((size_t)div_up(G.nCell, kScanChunk) * 4);
+    R.histS = (unsigned long long*)alloc((size_t)R.nBins * nPairS * 8);
+    R.histN = (unsigned long long*)alloc((size_t)R.nBins * std::max(nPairN, 1LL) * 8);
+    R.scanCounts = (Counts*)alloc(sizeof(Counts));
+    R.scanStats = (DevStats*)alloc(sizeof(DevStats));
+    HIP_CHECK(hipMemsetAsync(R.cellCount, 0, (size_t)G.nCell * 4, stream_));
+    HIP_CHECK(hipMemsetAsync(R.scanCounts, 0, sizeof(Counts), stream_));
+    HIP_CHECK(hipMemsetAsync(R.scanStats, 0, sizeof(DevStats), stream_));
+    rdf_reset();
+    return R.nBins;
+}
+
+void Engine::rdf_reset()
+{
+    if (!rdf_.nBins) throw ArgError("rdf: aztot_rdf_setup has not been called");
+    HIP_CHECK(hipMemsetAsync(rdf_.histS, 0, (size_t)rdf_.nBins * rdf_.grid.nPairS * 8, stream_));
+    if (rdf_.grid.nPairN) HIP_CHECK(hipMemsetAsync(rdf_.histN, 0, (size_t)rdf_.nBins * rdf_.grid.nPairN * 8, stream_));
+    rdf_.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Engine::rdf_sample()
+{
+    if (!rdf_.nBins) throw ArgError("rdf: aztot_rdf_setup has not been called");
+    if (!failed_.empty()) throw std::runtime_error("this handle failed in an earlier call: " + failed_);
+    settle();                       // the deferred end of the last aztot_step call: the positions are those aztot_md_to_host would return
+    RdfState& R = rdf_;
+    const RdfGrid& G = R.grid;
+    const int N = model_.nAt;
+    if (N < 2) { R.samples++; return; }
+    AtomArrays A = cur();
+    const int nb = div_up(N, kBlock);
+    timed("k_rdf_bin", [&] { hipLaunchKernelGGL(k_rdf_bin, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, R.cellOf, R.rankOf, R.cellCount); });
+    // exclusive scan of the cell counts (which it leaves cleared for the next sample)
+    if (G.nCell <= kScanSingleMax)
+        timed("k_rdf_scan", [&] { hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, G.nCell, R.cellCount, R.cellStart, R.scanCounts, R.scanStats, 0); });
+    else
+        timed("k_rdf_scan", [&] {
+            const int nChunk = div_up(G.nCell, kScanChunk);
+            hipLaunchKernelGGL(k_scan_totals, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, R.cellCount, R.chunkTot);
+            hipLaunchKernelGGL(k_scan_apply, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, R.cellCount, R.chunkTot, R.cellStart, R.scanCounts, R.scanStats, 0);
+        });
+    timed("k_rdf_place", [&] {
+        hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, R.cellOf, R.rankOf, R.cellStart, R.x, R.y, R.z, R.kind);
+    });
+    const size_t lds = (size_t)R.copies * (size_t)R.nBins * (size_t)(G.nPairS + G.nPairN) * sizeof(uint32_t);
+    timed("k_rdf_pairs", [&] {
+        hipLaunchKernelGGL(k_rdf_pairs, dim3(R.blocks), dim3(kBlock), lds, stream_, G, N, R.cellStart, R.x, R.y, R.z, R.kind, R.copies, R.histS, R.histN);
+    });
+    check_launch("rdf kernels");
+    R.samples++;
+    // Leave the engine as every reader does (aztot_get_stats: settled AND drained).  Returning with the sample still running let the next aztot_step
+    // open on a busy stream, and that changed engKin in its last bit in about one run of three (sort_every = 1; seen in test_gpu_rdf.py).
+    sync();
+}
+
+void Engine::rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts)
+{
+    if (!rdf_.nBins) throw ArgError("rdf: aztot_rdf_setup has not been called");
+    if (kind != 0 && kind != 1) throw ArgError("rdf: kind must be AZTOT_RDF_SPECIES or AZTOT_RDF_NUCLEI");
+    if (kind == 1 && !rdf_.nuclei) throw ArgError("rdf: nuclei histograms were not requested at aztot_rdf_setup");
+    nBins = rdf_.nBins;
+    nPairs = kind ? rdf_.grid.nPairN : rdf_.grid.nPairS;
+    samples = rdf_.samples;
+    if (!counts) return;
+    counts->resize((size_t)nBins * nPairs);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(counts->data(), kind ? rdf_.histN : rdf_.histS, counts->size() * 8, hipMemcpyDeviceToHost));
+}
+
+// g(r) as copy_rdf / copy_nrdf / out_rdf (cuStat.cu:514-560,719-760; rdf.cpp:128-175):
+//   g = count * V / (nA nB) * 2 / (sphera dr^3 samples) / (3 i (i + 1) + 1) * C3,   C3 = 1 for A-A, 0.5 for A-B;  0 where nA nB = 0 or no sample
+void Engine::rdf_values(int kind, std::vector<double>& r, std::vector<double>& g)
+{
+    int nBins = 0, nPairs = 0;
+    long long samples = 0;
+    std::vector<unsigned long long> c;
+    rdf_counts(kind, nBins, nPairs, samples, &c);
+    std::vector<double> num;
+    if (kind == 0) for (const auto& s : model_.species) num.push_back((double)s.number);
+    else for (int v : nuclei_of(model_).number) num.push_back((double)v);
+    const int n = (int)num.size();
+    const double sphera = 4.0 * units::pi / 3.0;                        // const.h:15
+    const double dr = rdf_.dr, V = model_.L[0] * model_.L[1] * model_.L[2];
+    const double C1 = samples > 0 ? 2.0 / (sphera * dr * dr * dr * (double)samples) : 0.0;
+    r.resize(nBins);
+    g.assign((size_t)nBins * nPairs, 0.0);
+    for (int i = 0; i < nBins; i++)
+    {
+        r[i] = (i + 0.5) * dr;
+        const double C2 = 1.0 / (3.0 * i * (i + 1.0) + 1.0);
+        int p = 0;
+        for (int a = 0; a < n; a++)
+            for (int b = a; b < n; b++, p++)
+            {
+                const double nAnB = num[a] * num[b];
+                if (nAnB == 0.0) continue;
+                const double C3 = a == b ? 1.0 : 0.5;
+                g[(size_t)i * nPairs + p] = (double)c[(size_t)i * nPairs + p] * V / nAnB * C1 * C2 * C3;
+            }
     }
 }
 

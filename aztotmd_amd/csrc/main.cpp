@@ -5,6 +5,12 @@
 //   revcon.xyz      final configuration in atoms.xyz format     (out_atoms, out_md.cpp:65-87; main.cu:436)
 //   velocities.dat  per-species |v|, vx, vy, vz table            (out_velocities, out_md.cpp:126-190; main.cu:445)
 //   tchars.dat      thermal energies and radii (radiative thermostat only)  (out_thermalchar, main.cu:51-118)
+//   rdf.dat         radial distribution functions, when control.txt has 'rdf rmax dr every out_every [nucl]' (rdf_iter / copy_rdf, cuStat.cu:514-600)
+//   rdf_n.dat       the same per nucleus pair, with 'nucl' (nrdf_iter / copy_nrdf, cuStat.cu:703-790)
+//   rdf<k>.dat      running RDFs at the samples with (c - 1) % out_every == 0, k = c - 1 (and rdf_n<k>.dat)
+// RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
+// (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
+// stat row (c % stat == 0, and the last step) or an RDF sample (which only reads the state: its place against the stat row of the same step does not matter).
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -20,6 +26,30 @@ static void die(const char* what)
 {
     std::fprintf(stderr, "FATAL ERROR: %s: %s\n", what, aztot_last_error());
     std::exit(1);
+}
+
+// copy_rdf / copy_nrdf layout: header "r\tA-A\tA-B...", rows "%f" r then "\t%f" per pair
+static void write_rdf(aztot_md* md, int kind, const std::vector<std::string>& names, const std::string& path)
+{
+    const int need = aztot_rdf_values(md, kind, nullptr, nullptr, 0);
+    if (need < 0) die("rdf values");
+    int nb = 0, np = 0;
+    if (aztot_rdf_shape(md, kind, &nb, &np) != AZTOT_OK) die("rdf shape");
+    std::vector<double> r(std::max(nb, 1)), g(std::max(need, 1));
+    if (aztot_rdf_values(md, kind, r.data(), g.data(), need) < 0) die("rdf values");
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) { std::perror(path.c_str()); std::exit(1); }
+    std::fprintf(f, "r");
+    for (size_t a = 0; a < names.size(); a++)
+        for (size_t b = a; b < names.size(); b++) std::fprintf(f, "\t%s-%s", names[a].c_str(), names[b].c_str());
+    std::fprintf(f, "\n");
+    for (int i = 0; i < nb; i++)
+    {
+        std::fprintf(f, "%f", r[i]);
+        for (int p = 0; p < np; p++) std::fprintf(f, "\t%f", g[(size_t)i * np + p]);
+        std::fprintf(f, "\n");
+    }
+    std::fclose(f);
 }
 
 static double q1(const aztot_model* m, const char* key)
@@ -82,12 +112,45 @@ int main(int argc, char** argv)
     for (int j = 0; j < nSpec; j++) std::fprintf(mf, "\t%s_px\tnx\tpy\tny\tpz\tnz", names[j].c_str());
     std::fprintf(mf, "\n");
     std::vector<int64_t> crossings(6 * (size_t)nSpec);
+    // radial distribution functions (read_rdf: rdf rmax dr every out_every [nucl])
+    double rdfp[6] = {0, 0, 0, 0, 0, 0};
+    aztot_model_query(model, "rdf", rdfp, 6);
+    const int rdfEvery = (int)rdfp[3], rdfOut = (int)rdfp[4];
+    const bool nucl = rdfp[5] != 0.0;
+    bool rdfOn = rdfp[0] != 0.0 && rdfEvery > 0;
+    std::vector<std::string> nnames;
+    if (rdfOn)
+    {
+        if (aztot_rdf_setup(md, rdfp[1], rdfp[2], nucl ? 1 : 0) < 0)
+        {
+            std::fprintf(stderr, "WARNING: rdf directive not usable (%s): no RDF output\n", aztot_last_error());
+            rdfOn = false;
+        }
+        const int nn = (int)q1(model, "n_nuclei");
+        for (int i = 0; i < nn; i++) { char b[16]; aztot_model_nucleus_name(model, i, b, 16); nnames.push_back(b); }
+    }
+    auto rdf_due = [&](int c) { return rdfOn && c >= 1 && (c - 1) % rdfEvery == 0; };
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
-        const int n = std::min(stat, nStep - done);
+        int n = std::min(stat - done % stat, nStep - done);
+        if (rdfOn)
+        {   // next sample: the smallest c > done with (c - 1) % every == 0
+            const int next = done < 1 ? 1 : done + 1 + (rdfEvery - (done % rdfEvery)) % rdfEvery;
+            n = std::min(n, next - done);
+        }
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
+        if (rdf_due(done))
+        {
+            if (aztot_rdf_sample(md) != AZTOT_OK) die("rdf sample");
+            if (rdfOut > 0 && (done - 1) % rdfOut == 0)
+            {
+                write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf" + std::to_string(done - 1) + ".dat");
+                if (nucl) write_rdf(md, AZTOT_RDF_NUCLEI, nnames, out + "/rdf_n" + std::to_string(done - 1) + ".dat");
+            }
+        }
+        if (done % stat != 0 && done != nStep) continue;
         if (aztot_get_stats(md, &st) != AZTOT_OK) die("stats");
         std::fprintf(sf, "%f\t%d\t%f\t%f\t%f\t%f\t%f", st.time, (int)st.step, st.engTot, st.engKin, st.engVdW, st.engCoul, st.engCoulRec);
         if (radi) std::fprintf(sf, "\t%f", st.engTemp);
@@ -104,6 +167,11 @@ int main(int argc, char** argv)
     }
     std::fclose(sf);
     std::fclose(mf);
+    if (rdfOn)
+    {
+        write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf.dat");
+        if (nucl) write_rdf(md, AZTOT_RDF_NUCLEI, nnames, out + "/rdf_n.dat");
+    }
 
     std::vector<double> x(N), y(N), z(N), vx(N), vy(N), vz(N), U(N), rad(N);
     std::vector<int32_t> types(N);

@@ -103,6 +103,10 @@ struct Model
     double desired_cell_size = 0;
     int stat = 1000;
     int max_neigh = 50;
+    // 'rdf rmax dr every out_every [nucl]' (read_rdf rdf.cpp:14-37); absent: rdf_present = 0 (the reference refuses such a file, we run without RDF)
+    int rdf_present = 0;
+    double rdf_rmax = 0, rdf_dr = 0;
+    int rdf_every = 0, rdf_out_every = 0, rdf_nucl = 0;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;
@@ -126,6 +130,15 @@ struct Model
     int nSpec() const { return (int)species.size(); }
     const PairPot& pot(int a, int b) const { return pairpots[(size_t)a * species.size() + b]; }
 };
+
+// nuclei table of read_spec (sys_init.cpp:86-103): a nucleus index per species, in order of first appearance of the nucleus name
+struct Nuclei
+{
+    std::vector<std::string> names;
+    std::vector<int> of;            // [nSpec]: nucleus index of each species
+    std::vector<int> number;        // [nNucl]: atoms per nucleus
+};
+Nuclei nuclei_of(const Model& m);
 
 // init_md: read field.txt, atoms.xyz, control.txt (+ cuda.txt) from `dir`; throws std::runtime_error
 // with the reference's ERROR[..] code in the message.

@@ -371,8 +371,37 @@ void read_sim(const std::string& dir, Model& m)
 
     if (seek_value(f, " cell_list %lf ", &m.desired_cell_size)) m.use_clist = 1;   // sys_init.cpp:862-865
     if (!seek_value(f, " stat %d ", &m.stat)) m.stat = 1000;
+    // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
+    m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
+    if (seek_value(f, " rdf %lf ", &m.rdf_rmax))
+    {
+        m.rdf_present = 1;
+        if (std::fscanf(f, " %lf %d %d", &m.rdf_dr, &m.rdf_every, &m.rdf_out_every) != 3) fail("ERROR[408] malformed 'rdf' directive in control.txt");
+        char w[64] = {0};
+        if (std::fscanf(f, " %63s", w) == 1 && std::strcmp(w, "nucl") == 0) m.rdf_nucl = 1;
+    }
     if (!seek_value(f, " max_neigh %d ", &m.max_neigh)) m.max_neigh = 50;
 }
+
+}  // namespace
+
+Nuclei nuclei_of(const Model& m)
+{
+    Nuclei n;
+    n.of.resize(m.nSpec());
+    for (int i = 0; i < m.nSpec(); i++)
+    {
+        const auto& nm = m.species[i].nucleus.empty() ? m.species[i].name : m.species[i].nucleus;
+        int j = 0;
+        while (j < (int)n.names.size() && n.names[j] != nm) j++;
+        if (j == (int)n.names.size()) { n.names.push_back(nm); n.number.push_back(0); }
+        n.of[i] = j;
+    }
+    for (int t : m.types) if (t >= 0 && t < m.nSpec()) n.number[n.of[t]]++;
+    return n;
+}
+
+namespace {
 
 // read_cuda: cuInit.cu:684-754 (optional file: defaults as the reference's)
 void read_cuda(const std::string& dir, Model& m)

@@ -196,6 +196,9 @@ int aztot_model_set_bonded(aztot_model *m, const aztot_bonded *b);
 int aztot_model_query(const aztot_model *m, const char *key, double *out, int cap);
 /* name of species i as written in field.txt (NUL-terminated, at most cap-1 characters) */
 int aztot_model_species_name(const aztot_model *m, int i, char *buf, int cap);
+/* name of nucleus i (the second word of a 'spec' line of field.txt; models made by aztot_model_create: the species name).  Nuclei are numbered in order of
+   first appearance among the species (read_spec, sys_init.cpp:86-103); aztot_model_query "nuclei" gives the nucleus of each species, "n_nuclei" their number */
+int aztot_model_nucleus_name(const aztot_model *m, int i, char *buf, int cap);
 void aztot_free_md(aztot_model *m);
 
 /* ---- device: replaces init_cudaMD / md_to_host / free_device_md (cuInit.h:4,6,7) --------------------- */
@@ -247,6 +250,34 @@ int aztot_set_clock(aztot_md *md, const aztot_clock *in);
    atom_id[s] = original index of the atom in slot s.  Either array may be NULL; caps are entry counts.  Returns the number of
    cells (or a negative error); never part of a step - a read-back for tests and restarts. */
 int aztot_cell_table(aztot_md *md, int32_t dims[3], int32_t *cell_start, int cap_cells, int32_t *atom_id, int cap_atoms);
+
+/* ---- radial distribution functions: brute_rdf / brute_nrdf + copy_rdf / copy_nrdf (cuStat.cu:436-760), get_rdf / out_rdf (rdf.cpp) -------
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.
+   Bins:    n_bins = (int)(min(rmax, L_x) * (1 / dr)) (init_rdf, rdf.cpp:40-48); rmax <= 0, dr <= 0 or n_bins == 0 -> AZTOT_ERR_ARG.
+   Pairs:   every unordered pair i < j whose minimum-image distance r (fp64, delta_periodic: one shift by L where |d| > L / 2) has r * r < rmax * rmax and
+            bin = (int)(r * (1 / dr)) < n_bins is counted once in `bin`, whatever rmax is against the box.  Species pair (a, b), mn = min, mx = max:
+            index mn * (nSpec - 1) + mn * (1 - mn) / 2 + mx (upper-triangular, row-major: the column order of rdf.dat); nuclei the same over nucleus indices.
+   Counts:  uint64 totals [bin][pair] and an int64 number of samples: exact, independent of the order the pairs arrive in.  Unlike the reference (which
+            clears its float histogram after 500 samples, cuStat.cu:576-583) nothing is ever cleared but by aztot_rdf_reset / aztot_rdf_setup.
+   g(r):    count * V / (nA * nB) * 2 / (sphera * dr^3 * samples) / (3 i (i + 1) + 1) * C3, C3 = 1 for A-A, 0.5 for A-B, sphera = 4 pi / 3 (const.h:15);
+            0 where nA * nB == 0 or before the first sample.  Bin centres r = (i + 0.5) dr.
+   Timing:  aztot_rdf_sample first completes the deferred end of the last aztot_step call (as every reader does), then only READS the state: a run that
+            samples gives bit-identical positions, velocities, forces and statistics to one that calls aztot_get_stats at the same points.
+   Sampling or reading before aztot_rdf_setup -> AZTOT_ERR_ARG; a handle that failed earlier refuses to sample but can still be read. */
+enum { AZTOT_RDF_SPECIES = 0, AZTOT_RDF_NUCLEI = 1 };
+/* (re)allocate and zero; nuclei = 1 also fills the nuclei histogram (whatever the model's 'nucl' flag says).  Returns n_bins. */
+int aztot_rdf_setup(aztot_md *md, double rmax, double dr, int nuclei);
+/* one sample of the current configuration (the positions aztot_md_to_host would return); returns when the sample is taken and the device idle,
+   as aztot_get_stats does */
+int aztot_rdf_sample(aztot_md *md);
+/* zero the totals and the sample count */
+int aztot_rdf_reset(aztot_md *md);
+/* histogram shape of `kind` (AZTOT_RDF_*): bins and pairs; AZTOT_ERR_ARG for AZTOT_RDF_NUCLEI when the setup did not ask for nuclei */
+int aztot_rdf_shape(aztot_md *md, int kind, int *n_bins, int *n_pairs);
+/* raw totals [bin][pair] into counts (if cap >= n_bins * n_pairs) and the number of samples; returns n_bins * n_pairs */
+int aztot_rdf_counts(aztot_md *md, int kind, int64_t *samples, uint64_t *counts, int cap);
+/* bin centres r[n_bins] and g[bin][pair] (if cap >= n_bins * n_pairs); returns n_bins * n_pairs */
+int aztot_rdf_values(aztot_md *md, int kind, double *r, double *g, int cap);
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
