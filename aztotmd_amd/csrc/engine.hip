@@ -868,6 +868,11 @@ void Engine::upload_initial()
         for (int k = 0; k < n; k++) tmp[k] = initial_radius(opt_.seed, (uint64_t)ids[k]);
         HIP_CHECK(hipMemcpy(A.rad, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     }
+    else if (P_.use_radii)
+    {   // a radius-dependent potential without the radiative thermostat: the radii it would have drawn (cuTemp.cu:41), never unset memory
+        for (int k = 0; k < n; k++) tmp[k] = initial_radius(opt_.seed, (uint64_t)ids[k]);
+        HIP_CHECK(hipMemcpy(A.rad, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    }
     Counts c{};
     c.ownedBegin = 0; c.ownedEnd = n; c.nTotal = n; c.srcBegin = 0; c.srcEnd = n;
     HIP_CHECK(hipMemcpy(dCounts_, &c, sizeof(Counts), hipMemcpyHostToDevice));

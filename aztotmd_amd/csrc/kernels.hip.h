@@ -168,7 +168,7 @@ __device__ __forceinline__ double fast_rsqrt(double x)
 
 // erfc(x) for 0 <= x <= 4 given ex = exp(-x*x), which the caller needs anyway (Fennell / Ewald force term):
 // erfc(x) = ex * p(t), t = 3u - 2, u = 1/(1 + x/2), p = our own degree-15 fit of erfcx (tools/fit_erfcx.py; max relative error
-// 7e-14 against scipy on [0, 4]; degree 16 until round 4: 8.5e-15 for one more FMA per visit and two more scalar registers in a loop
+// 7.2e-14 on [0, 4], 7.16e-14 at x = 3.89 evaluated exactly - tests/test_pair_functions_model.py; degree 16 until round 4: 8.5e-15 for one more FMA per visit and two more scalar registers in a loop
 // that had run out of them).  23 instructions instead of ocml's 140-instruction erfc plus a second exp; the host selects
 // this kernel only when alpha * rc <= 4.  tests/test_gpu_parity.py checks the result against the oracle's libm erfc.
 // Coefficients live in constant memory so that they reach the polynomial chains through scalar registers: as 64-bit literals

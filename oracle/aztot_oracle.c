@@ -381,6 +381,16 @@ int orc_prepare(orc_sys *s)
             s->rad[i] = 0.577 + rand01_ctr(s->seed, (uint64_t)i, &draw) * 0.0001;      /* cuTemp.cu:41 */
         }
     }
+    else
+    {   /* a radius-dependent potential without the radiative thermostat: the same initial radii (as the engine) */
+        int use_radii = 0;
+        for (int k = 0; k < s->nSpec * s->nSpec; k++) if (s->vdw[k].type != VDW_NONE && s->vdw[k].use_radii) use_radii = 1;
+        for (int i = 0; use_radii && i < s->N; i++)
+        {
+            uint64_t draw = 1000;
+            s->rad[i] = 0.577 + rand01_ctr(s->seed, (uint64_t)i, &draw) * 0.0001;
+        }
+    }
     return 1;
 }
 
