@@ -1,6 +1,7 @@
 """ctypes front-end of the C ABI in include/aztot.h (mirrors the reference's host seam:
 init_md -> init_cudaMD -> [step loop] -> md_to_host -> free_device_md; main.cu:239-463)."""
 import ctypes as C
+import enum
 import os
 import subprocess
 
@@ -97,6 +98,34 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
+
+
+class DebugBit(enum.IntFlag):
+    """Engine(debug=...): the measurement / test switches of `enum DebugBit` in csrc/device_md.h, which says what each one does
+    (tests/test_debug_bits.py holds the two lists to each other)."""
+    DBG_BUILD_PHASE_MASK = 3
+    DBG_ALWAYS_CLEANUP = 4
+    DBG_KICK_EVERY_STEP = 128
+    DBG_LARGE_KICK_PATH = 256
+    DBG_GENERIC_PAIR = 512
+    DBG_KEEP_VDW_CUT_TEST = 1024
+    DBG_STAGE_ONLY = 2048
+    DBG_SLAB_GRAPH = 4096
+    DBG_FIXED_INTERVAL = 8192
+    DBG_OVERLAP_HALO = 16384
+    DBG_NO_LISTS = 32768
+    DBG_SHORT_LISTS = 65536
+    DBG_NO_FUSE_NEXT = 131072
+    DBG_FUSE_NEXT = 262144
+    DBG_CHECK_EVERY_ATOM = 524288
+    DBG_LIST_STATS = 2097152
+    DBG_KICK_POST_SPLIT = 4194304
+    DBG_GRAPH_ALWAYS = 8388608
+    DBG_PLAIN_ONE_ATOM = 16777216
+    DBG_NO_BOUNDARY_RADI = 33554432
+    DBG_ONE_WAVE_PER_CELL = 67108864
+    DBG_ENERGIES_EVERY_STEP = 134217728
+    DBG_SETTLE_EVERY_CALL = 268435456
 
 
 def library_path():
@@ -306,7 +335,7 @@ class Engine:
     def __init__(self, model, device=0, initial_forces=1, center_box=0, seed=12345, pair_variant=0, cell_size=0.0, use_graph=1,
                  profile=0, slab=None, debug=0, sort_every=0, split=0, skin=0.0, energies_every_step=0):
         """slab: None or dict(rank=, nranks=, rccl_id=bytes) or dict(rank=, nranks=, sendrecv=callable, allreduce=callable).
-        debug: measurement / test switches (DebugBit in csrc/engine.h); they are not part of the ABI - the library reads them from the
+        debug: measurement / test switches (DebugBit above, from csrc/device_md.h); they are not part of the ABI - the library reads them from the
         environment variable AZTOT_DEBUG when the device handle is created, so it is set around that call here."""
         L = lib()
         o = _Options()

@@ -95,6 +95,39 @@ struct SplitArgs
     int capacity = 0;
 };
 
+// Measurement switches, read once from the environment variable AZTOT_DEBUG (a bit mask) when an engine is created.  Every bit but DBG_STAGE_ONLY keeps the
+// results unchanged (up to summation order): they select between code paths for A/B timing and let the tests reach paths a normal run rarely takes.
+enum DebugBit : unsigned
+{
+    DBG_BUILD_PHASE_MASK = 3,            // NOT result-preserving (phase timing of k_build_lists): 1 staging only, 2 + candidates and filter, 3 + compaction
+    DBG_ALWAYS_CLEANUP = 4,              // the clean-up launch behind every k_pair_list whatever the system size (small systems on one GPU run without it: Engine::choose_optimism)
+    DBG_KICK_EVERY_STEP = 128,           // k_integrate2 launched every step
+    DBG_LARGE_KICK_PATH = 256,           // the deferred half-kick of large systems whatever the size
+    DBG_GENERIC_PAIR = 512,              // the generic (switch-based) pair body instead of a specialised mode
+    DBG_KEEP_VDW_CUT_TEST = 1024,        // Lennard-Jones family: keep the per-pair cut-off test although it always passes (family 6, Engine::construct)
+    DBG_STAGE_ONLY = 2048,               // NOT result-preserving: the staging pair kernel stages its tile and stops (phase timing)
+    DBG_SLAB_GRAPH = 4096,               // hipGraph replay of a loopback slab rank
+    DBG_FIXED_INTERVAL = 8192,           // lazy re-sort at the fixed interval options.sort_every whatever the atoms' speed (exercises the wider-stencil fallback)
+    DBG_OVERLAP_HALO = 16384,            // slab ranks: coordinate exchange of plain steps on a second stream beside the interior cells' pair forces (measured slower)
+    DBG_NO_LISTS = 32768,                // no pair lists: the steps between two rebuilds stage every cell
+    DBG_SHORT_LISTS = 65536,             // pair lists capped at 14 iterations (part of a liquid's cells then goes through the clean-up launch)
+    DBG_NO_FUSE_NEXT = 131072,           // next-step fusion off ...
+    DBG_FUSE_NEXT = 262144,              // ... or on, whatever the system size
+    DBG_CHECK_EVERY_ATOM = 524288,       // plain steps check every atom against its reference position (no displacement bound)
+    DBG_LIST_STATS = 2097152,            // list statistics on stderr (with AZTOT_VERBOSE)
+    DBG_KICK_POST_SPLIT = 4194304,       // second half-kick and radiative thermostat as two launches
+    DBG_GRAPH_ALWAYS = 8388608,          // hipGraph replay also above 500 000 atoms
+    DBG_PLAIN_ONE_ATOM = 16777216,       // plain steps integrate one atom per thread
+    DBG_NO_BOUNDARY_RADI = 33554432,     // thermostat runs close a step and open the next in two launches
+    DBG_ONE_WAVE_PER_CELL = 67108864,    // one wave per cell in the staging kernel whatever the system
+    DBG_ENERGIES_EVERY_STEP = 134217728, // = options.energies_every_step
+    DBG_SETTLE_EVERY_CALL = 268435456    // every aztot_step call ends with the look / statistics / synchronisation (one GPU defers them to the next look or read)
+};
+
+// StepParams::potSet, the potential set the pair kernels are chosen for (Engine::construct decides, AZTOT_PAIR_DISPATCH): any mix of potentials, radii and species;
+// <= 4 species whose pair potentials all belong to the family StepParams::vdwFamily, no radii (parameters in an LDS table); one species, surk + thermostat radii
+enum PotSet { POTSET_GENERIC = 0, POTSET_ONE_FAMILY = 2, POTSET_ONE_SURK = 4 };
+
 // uniform parameters of the step (kernel argument, by value)
 struct StepParams
 {
@@ -117,19 +150,19 @@ struct StepParams
     double alpha, el_scale, el_scale2, daipi2, rReal, fcoul, sqrtpi;
     double E[3];                  // external field gradient
     // thermostat
-    int32_t tstat, nEq, freqEq, pad0;
+    int32_t tstat, nEq, freqEq, debugMask;     // debugMask: AZTOT_DEBUG (DebugBit)
     double tKin, revDegFree, rkB;
     double rQmass, qMassTau2;     // Nose-Hoover: 1/(2 tKin tau^2), 2 tKin (sys_init.cpp:1107-1112)
     double revLight, radFrac, radThr, numPi;
     uint64_t seed;
-    int32_t nAtGlobal, pad1;
+    int32_t nAtGlobal, potSet;    // potSet: PotSet
     // slab decomposition
     double xlo, xhi;              // owned x-range [xlo, xhi)
     int32_t rank, nranks;
     int32_t fuseKick;             // 1: the pair kernel also applies the second half-kick and books the kinetic energy (plain NVE steps)
-    int32_t vdwFamily;            // pad1 == 2: the one potential type all defined species pairs share (1 lnjs, 2 buck, 3 p746, 4 bmhs)
+    int32_t vdwFamily;            // POTSET_ONE_FAMILY: the one potential type all defined species pairs share (1 lnjs, 2 buck, 3 p746, 4 bmhs)
     int32_t cycleStep;            // lazy re-sort: which step since the last rebuild of the cells this launch belongs to (0: the rebuilding step itself)
-    int32_t pad2;                 // 1: plain steps may skip the per-atom displacement check while the displacement bound allows (Counts::cycMaxRun)
+    int32_t boundSkip;            // 1: plain steps may skip the per-atom displacement check while the displacement bound allows (Counts::cycMaxRun)
     double lazySlack2;            // lazy re-sort: square of the displacement an atom may have since the last sort ((hw * cell edge - rc) / 2 per axis, minimum);
                                   // 0: the cells are rebuilt every step
     double pruneR2;               // tile kernels: atoms farther than this (squared) from the centre cell's box are not staged: (rc + 2 slack)^2

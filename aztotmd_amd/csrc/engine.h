@@ -19,7 +19,7 @@
 namespace aztot {
 
 struct Counts;
-struct PairLists;
+struct PairLists; struct PairLaunch;
 
 // a caller error that the C ABI reports as AZTOT_ERR_ARG (capi.cpp: guarded)
 struct ArgError : std::runtime_error
@@ -37,35 +37,6 @@ struct KernelTimer
 }  // namespace aztot
 #include "exchange.h"
 namespace aztot {
-
-// Measurement switches, read once from the environment variable AZTOT_DEBUG (a bit mask) when an engine is created.  Every bit but DBG_STAGE_ONLY keeps the
-// results unchanged (up to summation order): they select between code paths for A/B timing and let the tests reach paths a normal run rarely takes.
-enum DebugBit : unsigned
-{
-    DBG_BUILD_PHASE_MASK = 3,            // NOT result-preserving (phase timing of k_build_lists): 1 staging only, 2 + candidates and filter, 3 + compaction
-    DBG_ALWAYS_CLEANUP = 4,              // the clean-up launch behind every k_pair_list whatever the system size (small systems on one GPU run without it: Engine::choose_optimism)
-    DBG_KICK_EVERY_STEP = 128,           // k_integrate2 launched every step
-    DBG_LARGE_KICK_PATH = 256,           // the deferred half-kick of large systems whatever the size
-    DBG_GENERIC_PAIR = 512,              // the generic (switch-based) pair body instead of a specialised mode
-    DBG_KEEP_VDW_CUT_TEST = 1024,        // Lennard-Jones family: keep the per-pair cut-off test although it always passes (family 6, Engine::construct)
-    DBG_STAGE_ONLY = 2048,               // NOT result-preserving: the staging pair kernel stages its tile and stops (phase timing)
-    DBG_SLAB_GRAPH = 4096,               // hipGraph replay of a loopback slab rank
-    DBG_FIXED_INTERVAL = 8192,           // lazy re-sort at the fixed interval options.sort_every whatever the atoms' speed (exercises the wider-stencil fallback)
-    DBG_OVERLAP_HALO = 16384,            // slab ranks: coordinate exchange of plain steps on a second stream beside the interior cells' pair forces (measured slower)
-    DBG_NO_LISTS = 32768,                // no pair lists: the steps between two rebuilds stage every cell
-    DBG_SHORT_LISTS = 65536,             // pair lists capped at 14 iterations (part of a liquid's cells then goes through the clean-up launch)
-    DBG_NO_FUSE_NEXT = 131072,           // next-step fusion off ...
-    DBG_FUSE_NEXT = 262144,              // ... or on, whatever the system size
-    DBG_CHECK_EVERY_ATOM = 524288,       // plain steps check every atom against its reference position (no displacement bound)
-    DBG_LIST_STATS = 2097152,            // list statistics on stderr (with AZTOT_VERBOSE)
-    DBG_KICK_POST_SPLIT = 4194304,       // second half-kick and radiative thermostat as two launches
-    DBG_GRAPH_ALWAYS = 8388608,          // hipGraph replay also above 500 000 atoms
-    DBG_PLAIN_ONE_ATOM = 16777216,       // plain steps integrate one atom per thread
-    DBG_NO_BOUNDARY_RADI = 33554432,     // thermostat runs close a step and open the next in two launches
-    DBG_ONE_WAVE_PER_CELL = 67108864,    // one wave per cell in the staging kernel whatever the system
-    DBG_ENERGIES_EVERY_STEP = 134217728, // = options.energies_every_step
-    DBG_SETTLE_EVERY_CALL = 268435456    // every aztot_step call ends with the look / statistics / synchronisation (one GPU defers them to the next look or read)
-};
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 // The host state machine in one table.  "Forget" = the three assignments `sinceSort_ = 1 << 30; listsValid_ = false;
@@ -167,7 +138,7 @@ private:
     void upload_bonded();
     void upload_ewald();
     void launch_ewald();
-    void sort_and_forces(int stepMode, bool withBonded = true);   // 0: bin + sort + forces (aztot_forces), 1: a step that re-sorts, 2: a plain step of the lazy re-sort
+    void sort_and_forces(int stepMode, bool withBonded = true);   // StepMode (kernels.hip.h): bin + sort + forces (aztot_forces), a step that re-sorts, a plain step of the lazy re-sort
     void launch_step_kernels();
     bool adapt_sort_interval();
     void look_sync();               // what a look reads (Counts, the list builder's report) copied into pinned memory behind the queued work, then ONE stream synchronisation
@@ -181,6 +152,9 @@ private:
     void check_overflow();
     void sync();
     template <typename F> void timed(const char* name, F&& launch);
+    template <typename T> T* dev_alloc(size_t n, bool zero, std::vector<void*>* owner);
+    template <typename T> T* dev_alloc(size_t n, bool zero = false) { return dev_alloc<T>(n, zero, &allocs_); }
+    PairLaunch pair_launch(const StepParams& Q);    // what the pair launches of the step in flight share (Q: P_ as the launch sees it)
     AtomArrays& cur() { return buf_[cur_]; }
     AtomArrays& oth() { return buf_[cur_ ^ 1]; }
 

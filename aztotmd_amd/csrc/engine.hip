@@ -31,11 +31,24 @@ void check_hip(hipError_t e, const char* what)
 namespace {
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 constexpr int kFuseKickMaxAtoms = 262144;
+// volume of the points within r of a box with edges a, b, c: the box, its face slabs, edge quarter-cylinders and corner octants
+inline double swept_volume(double a, double b, double c, double r) { return a * b * c + 2.0 * r * (a * b + b * c + c * a) + 3.14159265358979 * r * r * (a + b + c) + 4.18879020478639 * r * r * r; }
 constexpr int kLazyCapMax = 128;         // longest sort interval (steps)
 constexpr int kListCandMax = 1920;       // the LDS tile of k_pair_list holds candCap + 1 records of 32 B next to a 1 KiB table: below 64 KiB
 constexpr int kListIterMax = 248;
 constexpr long long kSnapshotKeepSteps = 32;     // a verified snapshot younger than this is kept at the end of a call (Engine::settle)
 }  // namespace
+
+// device memory for n elements (never less than 16 bytes), zero-filled on stream_ if asked.  `owner` is the list that frees it: the engine's (release), the
+// RDF sampler's (rdf_free), or none - the caller frees it itself (free_lists)
+template <typename T> T* Engine::dev_alloc(size_t n, bool zero, std::vector<void*>* owner)
+{
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, std::max<size_t>(sizeof(T) * n, 16)));
+    if (owner) owner->push_back(p);
+    if (zero) HIP_CHECK(hipMemsetAsync(p, 0, sizeof(T) * n, stream_));
+    return (T*)p;
+}
 
 template <typename F>
 void Engine::timed(const char* name, F&& launch)
@@ -206,7 +219,7 @@ void Engine::construct()
     P_.numPi = 3.14159;         // cuTemp.cu:228
     P_.seed = opt_.seed;
     P_.rank = rank_; P_.nranks = nranks_;
-    P_.pad0 = debug_;
+    P_.debugMask = debug_;
     P_.use_radii = 0;
     for (const auto& p : m.pairpots) if (p.type && p.use_radii) P_.use_radii = 1;
     P_.single_lj = (m.nSpec() == 1 && m.pairpots[0].type == AZTOT_VDW_LJ && m.elec_type == AZTOT_ELEC_NONE) ? 1 : 0;
@@ -227,19 +240,19 @@ void Engine::construct()
         {
             if (p.type == 0) continue;
             if (p.use_radii || p.type < AZTOT_VDW_LJ || p.type > AZTOT_VDW_BHM) uniform = false;
-            if (family == 0) family = p.type; else if (family != p.type) family = 5;   // 5: mixed families, type looked up per species pair
+            if (family == 0) family = p.type; else if (family != p.type) family = VDW_MIXED;   // mixed families, type looked up per species pair
         }
         if (family == 0) family = AZTOT_VDW_LJ;          // charges only: any family does, nothing is inside a VdW cut-off
         if ((m.elec_type == AZTOT_ELEC_FENNEL || m.elec_type == AZTOT_ELEC_EWALD) && m.alpha * m.rReal > 4.0) uniform = false;
-        if (debug_ & 512) uniform = false;      // debug bit 512: take the generic kernel
-        P_.pad1 = uniform ? 2 : 0;
+        if (debug_ & DBG_GENERIC_PAIR) uniform = false;
+        P_.potSet = uniform ? POTSET_ONE_FAMILY : POTSET_GENERIC;
         P_.vdwFamily = uniform ? family : 0;
         if (uniform && family == AZTOT_VDW_LJ)
         {   // family 6 = Lennard-Jones where EVERY species pair has a potential and none of their cut-offs lies inside the pair test's r2Max (the usual input:
             // one cut-off for everything, C3): the per-pair cut-off test - a table read, a compare and two selects per visit - always passes and is compiled out
             bool always = true;
             for (const auto& p : m.pairpots) if (p.type != AZTOT_VDW_LJ || p.r2cut < m.r2Max) always = false;
-            if (always && !(debug_ & 1024)) P_.vdwFamily = 6;          // (debug bit 1024: keep the test)
+            if (always && !(debug_ & DBG_KEEP_VDW_CUT_TEST)) P_.vdwFamily = VDW_LJ_NOCUT;
         }
         if (uniform && family == AZTOT_VDW_LJ)
         {   // the same shortcut for the Lennard-Jones family with charges: |f| <= |f_LJ| + |f_Coulomb|, each held below 0.5e5 beyond its radius.  LJ part
@@ -267,8 +280,8 @@ void Engine::construct()
             if (ok) P_.ljDropR2 = 2.0 * r2;
         }
         // kernel specialisation 4: ONE species with the radius-dependent surk potential and no electrostatics (case study 2)
-        if (m.nSpec() == 1 && m.pairpots[0].type == AZTOT_VDW_SURK && m.pairpots[0].use_radii && m.elec_type == AZTOT_ELEC_NONE && !(debug_ & 512))
-            P_.pad1 = 4;
+        if (m.nSpec() == 1 && m.pairpots[0].type == AZTOT_VDW_SURK && m.pairpots[0].use_radii && m.elec_type == AZTOT_ELEC_NONE && !(debug_ & DBG_GENERIC_PAIR))
+            P_.potSet = POTSET_ONE_SURK;
     }
     std::memset(&S_, 0, sizeof(S_));
     for (int i = 0; i < m.nSpec(); i++)
@@ -284,48 +297,40 @@ void Engine::construct()
     upload_ewald();
     {
         // who applies the second half-kick on plain NVE steps (nothing is added to the pair forces, nothing rescales velocities)
-        const bool plainNve = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !hasBonded_ && !hasEwald_ && !(debug_ & 128);
+        const bool plainNve = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP);
         const int variant = pair_variant();
         // small systems / slabs are bound by launch latency: the tile kernel's epilogue does it (one kernel less: C2 0.083 -> 0.063 ms).
         // On 1 M atoms that 13-lane read-modify-write of the velocities makes L2 write lines back several times (rocprofv3: 221 MB
         // instead of 63 + 76 MB per step) for no gain, so large systems fold it into the next step's streaming k_integrate1_bin.
-        fuseEpilogue_ = plainNve && variant >= 2 && capacity_ <= kFuseKickMaxAtoms && !(debug_ & 256);   // debug bit 256: large-system path
+        fuseEpilogue_ = plainNve && variant >= 2 && capacity_ <= kFuseKickMaxAtoms && !(debug_ & DBG_LARGE_KICK_PATH);
         // (bonded and reciprocal-space forces are added behind the pair kernel and are complete before the next step's integrate kernel just the same: runs with
         //  bonds / angles / the Ewald sum defer the kick too - they cannot take the pair kernel's epilogue, which would kick with the pair forces alone.
         //  M4: one 17 us launch per step less)
-        const bool kickCanWait = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !(debug_ & 128);
+        const bool kickCanWait = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !(debug_ & DBG_KICK_EVERY_STEP);
         lazyKick_ = kickCanWait && !fuseEpilogue_;
-        P_.pad2 = 0;
+        P_.boundSkip = 0;
         // next-step fusion (NextStep, pair_tile.hip.h): plain NVE (nothing happens between the forces and the next half-kick; on slab ranks the coordinate
         // exchange of the next step simply follows the pair kernel that produced the coordinates), a lazy run that walks
-        // pair lists; debug bit 131072 switches it off.  Up to ~500 000 atoms per GPU, where a step is bound by launch latency (measured: 40 000 atoms 0.0230 ->
+        // pair lists; DBG_NO_FUSE_NEXT switches it off.  Up to ~500 000 atoms per GPU, where a step is bound by launch latency (measured: 40 000 atoms 0.0230 ->
         // 0.0199 ms/step; emulated slab ranks of 143 000 / 250 000 / 333 000 atoms -9 % / -5 % / -4 %): on 1 M atoms the 13-lane stores of the epilogue cost
-        // the pair kernel exactly what the streaming k_integrate1_bin<2> costs on its own (111 + 31 -> 140 us); debug bit 262144 forces it on there
+        // the pair kernel exactly what the streaming k_integrate1_bin<2> costs on its own (111 + 31 -> 140 us); DBG_FUSE_NEXT forces it on there
         // ... and runs with the radiative thermostat (case study 1: 40 000 atoms, two launches per step - the pair kernel and the boundary kernel that closes
         // the step with the thermostat and opens the next): the thermostat acts on one atom at a time, so the lane that closes the atom's step applies it too
         // (k_pair_list<..., TSTAT>) and a step is ONE launch.  Not where the pair kernel reads radii (the thermostat rewrites them while other waves still
         // gather: case study 2's surk potential), not with bonded terms or the Ewald sum (their forces arrive after the pair kernel).
-        const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !hasEwald_ && !(debug_ & 128) && !P_.use_radii && P_.pad1 != 4 && (P_.single_lj || P_.pad1 == 2) &&
+        const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP) && !P_.use_radii && P_.potSet != POTSET_ONE_SURK && (P_.single_lj || P_.potSet == POTSET_ONE_FAMILY) &&
                               nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
-        fuseNextTstat_ = radiFuse && listsOn_ && variant == 2 && !(debug_ & 131072);
-        if (((plainNve && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & 262144))) || radiFuse) && listsOn_ && variant == 2 && !(debug_ & 131072))
+        fuseNextTstat_ = radiFuse && listsOn_ && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
+        if (((plainNve && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && listsOn_ && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
         {
             fuseNextOk_ = true;
-            const size_t nd = sizeof(double) * (size_t)capacity_;
             for (int b = 0; b < 2; b++)
-                for (int d = 0; d < 3; d++)
-                {
-                    void* p = nullptr;
-                    HIP_CHECK(hipMalloc(&p, std::max<size_t>(nd, 16)));
-                    allocs_.push_back(p);
-                    altXyz_[b][d] = (double*)p;
-                    HIP_CHECK(hipMemsetAsync(p, 0, nd, stream_));
-                }
+                for (int d = 0; d < 3; d++) altXyz_[b][d] = dev_alloc<double>((size_t)capacity_, true);
         }
     }
     // displacement bound instead of the per-atom check on plain steps: wherever k_integrate1_bin<2> opens every plain step (engines that fuse the next
-    // step into the pair kernel keep the per-atom check there); debug bit 524288 switches it off
-    P_.pad2 = (lazyOn_ && !fuseNextOk_ && !(debug_ & 524288)) ? 1 : 0;
+    // step into the pair kernel keep the per-atom check there); DBG_CHECK_EVERY_ATOM switches it off
+    P_.boundSkip = (lazyOn_ && !fuseNextOk_ && !(debug_ & DBG_CHECK_EVERY_ATOM)) ? 1 : 0;
     if (nranks_ > 1 && !xch_)
     {   // options.reserved[1]: loopback measurement mode (see LoopbackExchanger)
         ownedXch_.reset(new LoopbackExchanger((P_.ncxLocal - 2 * P_.hw[0]) * P_.csz[0], P_.L[0], lay_.mig_offset(), lay_.halo_offset(),
@@ -447,13 +452,12 @@ void Engine::allocate()
     {   // few cells (less than half a residency of waves) and a stencil with columns to share out: several waves per cell in the staging kernel
         const int cells = pair_tile_cells(P_);
         int n = 1;
-        if (pair_tile_supported(P_) && !(debug_ & 67108864))
+        if (pair_tile_supported(P_) && !(debug_ & DBG_ONE_WAVE_PER_CELL))
             while (n < 8 && cells * n * 2 <= 4096 && n * 2 <= P_.nOff[0] * P_.nOff[1]) n *= 2;
-        if (n == 1 && pair_tile_supported(P_) && !(debug_ & 67108864))
+        if (n == 1 && pair_tile_supported(P_) && !(debug_ & DBG_ONE_WAVE_PER_CELL))
         {   // more cells than that, but a stencil that needs several tiles per cell (dense systems, small cells: expected candidates = density x volume
             // within the cut-off of a cell): two waves per cell, each with half the columns and fewer tile flushes (measured: S40 -8 %, M4 -9 %; four: worse)
-            const double r = model_.rMax, a = P_.csz[0], b = P_.csz[1], c = P_.csz[2];
-            const double vol = a * b * c + 2.0 * r * (a * b + b * c + c * a) + 3.14159265358979 * r * r * (a + b + c) + 4.18879020478639 * r * r * r;
+            const double vol = swept_volume(P_.csz[0], P_.csz[1], P_.csz[2], model_.rMax);
             const double density = (double)model_.nAt / (model_.L[0] * model_.L[1] * model_.L[2]);
             if (density * vol > 1.15 * kTileCap && P_.nOff[0] * P_.nOff[1] >= 2) n = 2;
         }
@@ -463,25 +467,18 @@ void Engine::allocate()
     }
     pairBlocks_ = std::max(div_up(capacity_, kBlock), pair_tile_grid(P_) * std::max(split_.n, kListMaxWaves) + 24 + 3 * pair_cleanup_grid(pair_tile_cells(P_)));
     maxBlocks_ = std::max(div_up(capacity_, kBlock), pairBlocks_) + 1;
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); allocs_.push_back(p); return p; };
-    const size_t nd = sizeof(double) * (size_t)capacity_, ni = sizeof(int32_t) * (size_t)capacity_;
+    const size_t nAtoms = (size_t)capacity_, nCells = (size_t)(nCellAlloc_ + 1);
     for (int b = 0; b < 2; b++)
     {
         AtomArrays& A = buf_[b];
         double** d[] = {&A.x, &A.y, &A.z, &A.vx, &A.vy, &A.vz, &A.fx, &A.fy, &A.fz, &A.U, &A.rad};
-        for (auto pp : d) { *pp = (double*)alloc(nd); HIP_CHECK(hipMemsetAsync(*pp, 0, nd, stream_)); }
-        A.type = (int32_t*)alloc(ni); A.id = (int32_t*)alloc(ni);
-        HIP_CHECK(hipMemsetAsync(A.type, 0, ni, stream_)); HIP_CHECK(hipMemsetAsync(A.id, 0, ni, stream_));
+        for (auto pp : d) *pp = dev_alloc<double>(nAtoms, true);
+        A.type = dev_alloc<int32_t>(nAtoms, true); A.id = dev_alloc<int32_t>(nAtoms, true);
     }
-    dCellOf_ = (int32_t*)alloc(ni); dSlotOf_ = (int32_t*)alloc(ni);
-    dTmpId_ = (int32_t*)alloc(ni); dTmpSrc_ = (int32_t*)alloc(ni); dTmpCell_ = (int32_t*)alloc(ni); dCellOfSorted_ = (int32_t*)alloc(ni);
-    dCellCount_ = (int32_t*)alloc(sizeof(int32_t) * (size_t)(nCellAlloc_ + 1));
-    dCellStart_ = (int32_t*)alloc(sizeof(int32_t) * (size_t)(nCellAlloc_ + 1));
-    HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(nCellAlloc_ + 1), stream_));
-    HIP_CHECK(hipMemsetAsync(dCellStart_, 0, sizeof(int32_t) * (size_t)(nCellAlloc_ + 1), stream_));
-    dPartials_ = (double*)alloc(sizeof(double) * (size_t)PS_COUNT * maxBlocks_);
-    HIP_CHECK(hipMemsetAsync(dPartials_, 0, sizeof(double) * (size_t)PS_COUNT * maxBlocks_, stream_));
-    dStats_ = (DevStats*)alloc(sizeof(DevStats));
+    dCellOf_ = dev_alloc<int32_t>(nAtoms); dSlotOf_ = dev_alloc<int32_t>(nAtoms);
+    dTmpId_ = dev_alloc<int32_t>(nAtoms); dTmpSrc_ = dev_alloc<int32_t>(nAtoms); dTmpCell_ = dev_alloc<int32_t>(nAtoms); dCellOfSorted_ = dev_alloc<int32_t>(nAtoms);
+    dCellCount_ = dev_alloc<int32_t>(nCells, true); dCellStart_ = dev_alloc<int32_t>(nCells, true);
+    dPartials_ = dev_alloc<double>((size_t)PS_COUNT * maxBlocks_, true); dStats_ = dev_alloc<DevStats>(1);
     {
         DevStats zero;
         std::memset(&zero, 0, sizeof(zero));
@@ -491,21 +488,16 @@ void Engine::allocate()
     }
     if (split_.n > 1)
     {
-        const size_t nb = sizeof(double) * (size_t)split_.n * capacity_;
-        split_.fx = (double*)alloc(nb); split_.fy = (double*)alloc(nb); split_.fz = (double*)alloc(nb);
-        split_.arrived = (int32_t*)alloc(sizeof(int32_t) * (size_t)P_.nCellLocal);
-        HIP_CHECK(hipMemsetAsync(split_.arrived, 0, sizeof(int32_t) * (size_t)P_.nCellLocal, stream_));
+        const size_t nb = (size_t)split_.n * capacity_;
+        split_.fx = dev_alloc<double>(nb); split_.fy = dev_alloc<double>(nb); split_.fz = dev_alloc<double>(nb);
+        split_.arrived = dev_alloc<int32_t>((size_t)P_.nCellLocal, true);
     }
-    dCounts_ = (Counts*)alloc(sizeof(Counts));
-    dChunkTot_ = (int32_t*)alloc(sizeof(int32_t) * (size_t)(div_up(nCellAlloc_, kScanChunk) + 1));
-    dEkGlobal_ = (double*)alloc(sizeof(double) * 2);
-    dStage_ = (double*)alloc(sizeof(double) * PS_COUNT * kCollectParts);
-    HIP_CHECK(hipMemsetAsync(dStage_, 0, sizeof(double) * PS_COUNT * kCollectParts, stream_));
+    dCounts_ = dev_alloc<Counts>(1); dChunkTot_ = dev_alloc<int32_t>((size_t)(div_up(nCellAlloc_, kScanChunk) + 1));
+    dEkGlobal_ = dev_alloc<double>(2); dStage_ = dev_alloc<double>((size_t)PS_COUNT * kCollectParts, true);
     if (nranks_ > 1)
     {
-        for (int k = 0; k < 4; k++) { dMsg_[k] = (char*)alloc(lay_.bytes()); HIP_CHECK(hipMemsetAsync(dMsg_[k], 0, lay_.bytes(), stream_)); }
-        dHaloInfo_ = (int32_t*)alloc(sizeof(int32_t) * 16);
-        HIP_CHECK(hipMemsetAsync(dHaloInfo_, 0, sizeof(int32_t) * 16, stream_));
+        for (int k = 0; k < 4; k++) dMsg_[k] = dev_alloc<char>(lay_.bytes(), true);
+        dHaloInfo_ = dev_alloc<int32_t>(16, true);
     }
     const int ns = model_.nSpec();
     std::vector<DevPot> pots((size_t)ns * ns);
@@ -516,7 +508,7 @@ void Engine::allocate()
             DevPot& d = pots[(size_t)a * ns + b];
             d.type = p.type; d.use_radii = p.use_radii; d.p0 = p.p0; d.p1 = p.p1; d.p2 = p.p2; d.p3 = p.p3; d.p4 = p.p4; d.r2cut = p.r2cut;
             // Lennard-Jones uses p0..p2 only (vdw.cpp:283-288: 4 eps, sigma^2, 24 eps); the two free slots carry the force law in powers of 1/r^2 for the
-            // one-species kernel (pair_body, MODE 1): f = u^4 (A2 u^3 - A1) with u = 1/r^2, A1 = 24 eps sigma^6, A2 = 48 eps sigma^12
+            // one-species kernel (pair_body, PM_ONE_LJ): f = u^4 (A2 u^3 - A1) with u = 1/r^2, A1 = 24 eps sigma^6, A2 = 48 eps sigma^12
             if (p.type == AZTOT_VDW_LJ) { const double s6 = p.p1 * p.p1 * p.p1; d.p3 = p.p2 * s6; d.p4 = 2.0 * p.p2 * s6 * s6; }
         }
     {   // lazy re-sort: no external field (its energy is booked from wrapped coordinates), a stencil that can be widened by one cell on a violation
@@ -535,7 +527,7 @@ void Engine::allocate()
         lazyOn_ = sortEvery != 1 && (widenOk || nranks_ > 1) && m.rMax > 0 && slack > 1e-3 && m.E[0] == 0.0 && m.E[1] == 0.0 &&
                   m.E[2] == 0.0 && pair_tile_supported(P_);
         lazyCap_ = sortEvery > 1 ? std::min(sortEvery, kLazyCapMax) : kLazyCapMax;
-        if (lazyOn_ && (debug_ & 8192)) lazyK_ = lazyCap_;
+        if (lazyOn_ && (debug_ & DBG_FIXED_INTERVAL)) lazyK_ = lazyCap_;
         // The slack an atom may use is half the skin (both atoms of a pair move).  With a skin (options.skin >= 0) the cells were sized for it and the box
         // may give a little more for free - taken up to a quarter above the target, beyond that it would only lengthen the lists; without one
         // (options.skin < 0) it is capped at 1.2 % of the cut-off as in round 2.
@@ -546,8 +538,8 @@ void Engine::allocate()
         P_.pruneR2 = rp * rp * (1.0 + 1e-12);
         if (lazyOn_)
         {
-            ref_.x = (double*)alloc(nd); ref_.y = (double*)alloc(nd); ref_.z = (double*)alloc(nd);
-            if (capacity_ < (1 << 26) && !(debug_ & 32768))          // atom index + 6 bits of image code in 32 bits; debug 32768: no lists
+            ref_.x = dev_alloc<double>(nAtoms); ref_.y = dev_alloc<double>(nAtoms); ref_.z = dev_alloc<double>(nAtoms);
+            if (capacity_ < (1 << 26) && !(debug_ & DBG_NO_LISTS))          // atom index + 6 bits of image code in 32 bits
             {
                 if (P_.ncxLocal > 1023 || P_.nc[1] > 1023 || P_.nc[2] > 1023) throw std::runtime_error("more than 1023 cells along an axis");
                 int devLds = 0;
@@ -557,7 +549,7 @@ void Engine::allocate()
                 // with room for a liquid's fluctuations (+ 30 % / + 50 %); cells that need more keep no list, and the engine grows the lists when
                 // that happens to more than a few (adapt_sort_interval)
                 const double a = P_.csz[0], b = P_.csz[1], c = P_.csz[2], r = rp;
-                const double vol = a * b * c + 2.0 * r * (a * b + b * c + c * a) + 3.14159265358979 * r * r * (a + b + c) + 4.18879020478639 * r * r * r;
+                const double vol = swept_volume(a, b, c, r);
                 const double density = (double)m.nAt / (m.L[0] * m.L[1] * m.L[2]);
                 const double perCell = density * a * b * c, partners = density * 4.18879020478639 * r * r * r;
                 // (a cell's iterations are its atoms' partners divided by the slices each atom gets, NS = 64 / atoms: sized for a cell 60 % fuller than the mean)
@@ -593,7 +585,7 @@ void Engine::allocate()
             }
         }
     }
-    dPots_ = (DevPot*)alloc(sizeof(DevPot) * pots.size());
+    dPots_ = dev_alloc<DevPot>(pots.size());
     HIP_CHECK(hipMemcpyAsync(dPots_, pots.data(), sizeof(DevPot) * pots.size(), hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
@@ -615,13 +607,10 @@ void Engine::allocate_lists(int candCap, int iterCap)
     }
     while (iterCap > 2 * kListMinIter && build_lists_lds_bytes(probe) > listLdsMax_) { iterCap -= 8; probe.iterCap = probe.iterLds = iterCap; }
     const size_t nc = (size_t)P_.nCellLocal;
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); return p; };
-    dCandList_ = (uint32_t*)alloc(sizeof(uint32_t) * nc * candCap);
-    dListMeta_ = (int32_t*)alloc(sizeof(int32_t) * 4 * nc);
-    dPairList_ = (uint16_t*)alloc(sizeof(uint16_t) * nc * (size_t)listWaves_ * (size_t)iterCap * kWave);
-    dNoList_ = (int32_t*)alloc(sizeof(int32_t) * 16);
-    dRel_ = (float4*)alloc(sizeof(float4) * ((size_t)capacity_ + kWave));
-    HIP_CHECK(hipMemsetAsync(dRel_, 0, sizeof(float4) * ((size_t)capacity_ + kWave), stream_));
+    dCandList_ = dev_alloc<uint32_t>(nc * candCap, true, nullptr);             // (free_lists owns these five) every entry is an atom index at all times
+    dListMeta_ = dev_alloc<int32_t>(4 * nc, false, nullptr);
+    dPairList_ = dev_alloc<uint16_t>(nc * (size_t)listWaves_ * (size_t)iterCap * kWave, true, nullptr);   // every entry is a tile offset at all times (k_pair_list reads ahead)
+    dNoList_ = dev_alloc<int32_t>(16, true, nullptr); dRel_ = dev_alloc<float4>((size_t)capacity_ + kWave, true, nullptr);
     candCap_ = candCap; iterCap_ = iterCap;
     candLds_ = candCap; iterLds_ = iterCap;          // (tightened once the builder has reported what the cells really hold: adapt_sort_interval)
     {   // header: -1 = no list ; second word: the cell's coordinates in the local grid (the kernels decode them with shifts)
@@ -635,9 +624,6 @@ void Engine::allocate_lists(int candCap, int iterCap)
         HIP_CHECK(hipMemcpyAsync(dListMeta_, mx.data(), sizeof(int32_t) * 4 * nc, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    HIP_CHECK(hipMemsetAsync(dCandList_, 0, sizeof(uint32_t) * nc * candCap, stream_));      // every entry is an atom index at all times
-    HIP_CHECK(hipMemsetAsync(dPairList_, 0, sizeof(uint16_t) * nc * (size_t)listWaves_ * (size_t)iterCap * kWave, stream_));   // every entry is a tile offset at all times (k_pair_list reads ahead)
-    HIP_CHECK(hipMemsetAsync(dNoList_, 0, sizeof(int32_t) * 16, stream_));
     listsOn_ = true;
     listsValid_ = false;
     if (std::getenv("AZTOT_VERBOSE"))
@@ -694,7 +680,7 @@ void Engine::upload_bonded()
     if (!hasBonded_) return;
     const int N = m.nAt;
     auto up = [&](const void* src, size_t bytes) {
-        void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); allocs_.push_back(p);
+        void* p = dev_alloc<char>(bytes);
         if (bytes) HIP_CHECK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
         return p;
     };
@@ -754,8 +740,7 @@ void Engine::upload_ewald()
         else if (m.kvecs[k - 1].m != a.m) flags |= EWK_NEW_LM;
         kv[k] = EwaldK{a.l, a.m, a.n, flags, a.rkx, a.rky, a.rkz, a.akk};
     }
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); allocs_.push_back(p); return p; };
-    EwaldK* dkv = (EwaldK*)alloc(sizeof(EwaldK) * kv.size());
+    EwaldK* dkv = dev_alloc<EwaldK>(kv.size());
     HIP_CHECK(hipMemcpy(dkv, kv.data(), sizeof(EwaldK) * kv.size(), hipMemcpyHostToDevice));
     ew_.kv = dkv;
     // work items of k_ewald_sfac: (l, m, |n|) with the indices of its +n / -n members
@@ -768,7 +753,7 @@ void Engine::upload_ewald()
         if (it == slot.end()) { slot[key] = (int)work.size(); work.push_back(EwaldW{kv[k].l, kv[k].m, std::abs(kv[k].n), -1, -1}); it = slot.find(key); }
         if (kv[k].n >= 0) work[it->second].kPlus = (int)k; else work[it->second].kMinus = (int)k;
     }
-    EwaldW* dw = (EwaldW*)alloc(sizeof(EwaldW) * work.size());
+    EwaldW* dw = dev_alloc<EwaldW>(work.size());
     HIP_CHECK(hipMemcpy(dw, work.data(), sizeof(EwaldW) * work.size(), hipMemcpyHostToDevice));
     ew_.work = dw; ew_.nW = (int)work.size();
     // work items of k_ewald_force: runs of consecutive n with the same (l, m) (the table is in ewald_rec's nested-loop order)
@@ -778,14 +763,14 @@ void Engine::upload_ewald()
         if (!groups.empty() && groups.back().l == kv[k].l && groups.back().m == kv[k].m && groups.back().nHi + 1 == kv[k].n) groups.back().nHi = kv[k].n;
         else groups.push_back(EwaldG{kv[k].l, kv[k].m, kv[k].n, kv[k].n, (int)k});
     }
-    EwaldG* dg = (EwaldG*)alloc(sizeof(EwaldG) * groups.size());
+    EwaldG* dg = dev_alloc<EwaldG>(groups.size());
     HIP_CHECK(hipMemcpy(dg, groups.data(), sizeof(EwaldG) * groups.size(), hipMemcpyHostToDevice));
     ew_.groups = dg; ew_.nG = (int)groups.size();
-    ew_.T = (double*)alloc(sizeof(double) * 2 * kv.size());
+    ew_.T = dev_alloc<double>(2 * kv.size());
     ew_.nK = (int)kv.size(); ew_.kx = m.ewald_k[0]; ew_.ky = m.ewald_k[1]; ew_.kz = m.ewald_k[2];
     ew_.nBlocksA = std::max(1, std::min(1024, div_up(capacity_, kEwTile)));
-    ew_.partial = (double*)alloc(sizeof(double) * 2 * (size_t)ew_.nK * ew_.nBlocksA);
-    ew_.S = (double*)alloc(sizeof(double) * 2 * (size_t)ew_.nK);
+    ew_.partial = dev_alloc<double>(2 * (size_t)ew_.nK * ew_.nBlocksA);
+    ew_.S = dev_alloc<double>(2 * (size_t)ew_.nK);
     HIP_CHECK(hipMemset(ew_.S, 0, sizeof(double) * 2 * (size_t)ew_.nK));
     ew_.scale = m.el_scale; ew_.scale2 = m.el_scale2;
     {   // both kernels keep the three per-atom harmonic tables in dynamic LDS: 1 KiB per harmonic (+ 12 KiB of force slices).  Beyond
@@ -861,7 +846,7 @@ void Engine::upload_initial()
         photon_engs(N, ph.data(), m.Temp, opt_.seed);
         unit_vectors(ux.data(), uy.data(), uz.data());
         auto alloc_up = [&](double*& d, const std::vector<double>& h) {
-            void* p = nullptr; HIP_CHECK(hipMalloc(&p, sizeof(double) * h.size())); allocs_.push_back(p); d = (double*)p;
+            d = dev_alloc<double>(h.size());
             HIP_CHECK(hipMemcpy(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
         };
         alloc_up(dPhotons_, ph); alloc_up(dUvx_, ux); alloc_up(dUvy_, uy); alloc_up(dUvz_, uz);
@@ -894,6 +879,8 @@ int Engine::pair_variant() const
     return variant;
 }
 
+PairLaunch Engine::pair_launch(const StepParams& Q) { return PairLaunch{Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_}; }
+
 void Engine::launch_pair()
 {
     const int variant = pair_variant();
@@ -901,6 +888,7 @@ void Engine::launch_pair()
     {
         StepParams Q = P_;
         Q.fuseKick = fuseNow_ ? 1 : 0;
+        const PairLaunch C = pair_launch(Q);
         // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
         // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
         const bool wantEnergies = stepsLeftInRun_ == 0 || (debug_ & DBG_ENERGIES_EVERY_STEP);
@@ -918,12 +906,12 @@ void Engine::launch_pair()
                 r.blockBase = nb;
                 if (lists)
                 {
-                    nb += launch_pair_list(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, r, pl, NextStep(), wantEnergies);
-                    nb += launch_pair_cleanup(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, r, pl);
+                    nb += launch_pair_list(C, r, pl, NextStep(), wantEnergies);
+                    nb += launch_pair_cleanup(C, r, pl);
                 }
                 else
                 {
-                    launch_pair_tile(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, r, PairLists(), 0, NextStep(), split_);
+                    launch_pair_tile(C, r, PairLists(), 0, NextStep(), split_);
                     nb += pair_range_grid(r.n) * split_.n;
                 }
             };
@@ -944,7 +932,7 @@ void Engine::launch_pair()
                 // plain step until the next rebuild, it walks them; the clean-up launch stages the cells that keep no list
                 if (candMode_ == 1)
                 {   // (k_rank_gather has cleared the count of cells without a list)
-                    timed("build_lists", [&] { launch_build_lists(Q, dCellStart_, stream_, PairRange(), pl); });
+                    timed("build_lists", [&] { launch_build_lists(C, PairRange(), pl); });
                     listsValid_ = true;
                     unlistedState_ = 0;
                     if (nranks_ > 1 && !capturing_)
@@ -967,9 +955,9 @@ void Engine::launch_pair()
                 if (fuseNext_ && fuseNextTstat_) { nx.photons = dPhotons_; nx.uvx = dUvx_; nx.uvy = dUvy_; nx.uvz = dUvz_; pairClosedStep_ = true; }
                 else nx.pendingAfter = lazyKick_ ? 1 : -1;         // this step's second half-kick is owed to the next k_integrate1_bin (a call may open
                                                                     // with a plain step, where no scan re-arms the flag)
-                timed("pair_list", [&] { splitBlocks_ = launch_pair_list(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, PairRange(), pl, nx, wantEnergies); });
+                timed("pair_list", [&] { splitBlocks_ = launch_pair_list(C, PairRange(), pl, nx, wantEnergies); });
                 if (!skipCleanup)
-                    timed("pair_cleanup", [&] { splitBlocks_ += launch_pair_cleanup(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, PairRange(), pl, nx); });
+                    timed("pair_cleanup", [&] { splitBlocks_ += launch_pair_cleanup(C, PairRange(), pl, nx); });
                 if (fuseNext_)
                 {   // the next step's positions are in the other set of coordinate arrays now
                     AtomArrays& A = cur();
@@ -978,7 +966,7 @@ void Engine::launch_pair()
                 }
             }
             else
-                timed("pair_tile", [&] { launch_pair_tile(Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_, PairRange(), pl, 0, NextStep(), split_); });
+                timed("pair_tile", [&] { launch_pair_tile(C, PairRange(), pl, 0, NextStep(), split_); });
         }
     }
     else
@@ -1042,12 +1030,12 @@ void Engine::exchange_halo()
 void Engine::sort_and_forces(int stepMode, bool withBonded)
 {
     const int gridAtoms = div_up(capacity_, kBlock);
-    const bool integrate_first = stepMode != 0;
-    P_.cycleStep = (stepMode == 2) ? sinceSort_ + 1 : 0;           // which step since the last rebuild (the slack-violation flag is indexed by it)
-    if (stepMode == 2)
+    const bool integrate_first = stepMode != STEP_BIN_ONLY;
+    P_.cycleStep = (stepMode == STEP_PLAIN) ? sinceSort_ + 1 : 0;           // which step since the last rebuild (the slack-violation flag is indexed by it)
+    if (stepMode == STEP_PLAIN)
     {   // plain step of the lazy re-sort: integrate only; slots, cells and buffers stay as they are
         if (preIntegrated_) preIntegrated_ = false;                 // the previous step's pair kernel has opened this step already (NextStep)
-        else if (nranks_ == 1 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & 16777216))
+        else if (nranks_ == 1 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & DBG_PLAIN_ONE_ATOM))
             // one GPU (the owned range starts at 0: 16-byte loads are aligned), nothing scales the velocities at the start of the step: two atoms per thread
             timed("integrate1", [&] {
                 hipLaunchKernelGGL(k_integrate_plain2, dim3(div_up(div_up(capacity_, 2), kBlock)), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dPartials_,
@@ -1055,7 +1043,7 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
             });
         else
         timed("integrate1", [&] {
-            hipLaunchKernelGGL(k_integrate1_bin<2>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
+            hipLaunchKernelGGL(k_integrate1_bin<STEP_PLAIN>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
         });
         if (nranks_ > 1)
@@ -1068,9 +1056,9 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
             // own stream next to the interior cells' pair forces; the boundary cells wait for it (launch_pair).  Not while kernels are being timed
             // one by one, not with the per-atom kernel, and not when there is no interior to speak of.
             const int interiorLayers = P_.ncxLocal - 4 * P_.hw[0];
-            // OPT-IN (debug bit 16384): measured on one rank of 7 (loopback) the two cross-stream event waits and the two extra launches cost 30 us
+            // OPT-IN (DBG_OVERLAP_HALO): measured on one rank of 7 (loopback) the two cross-stream event waits and the two extra launches cost 30 us
             // where the exchange they hide takes 7 (0.0685 -> 0.0981 ms/step), so the default is the serial order
-            overlapHalo_ = !profile_ && xch_->device_side() && pair_variant() == 2 && interiorLayers >= 1 && (debug_ & 16384);
+            overlapHalo_ = !profile_ && xch_->device_side() && pair_variant() == 2 && interiorLayers >= 1 && (debug_ & DBG_OVERLAP_HALO);
             if (overlapHalo_)
             {
                 HIP_CHECK(hipEventRecord(evIntegrated_, stream_));
@@ -1088,17 +1076,17 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     }
     else
     {
-    candMode_ = (stepMode == 1 && lazyOn_ && lazyK_ > 1) ? 1 : 0;       // a step that opens an interval of plain steps records the lists
+    candMode_ = (stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? 1 : 0;       // a step that opens an interval of plain steps records the lists
     if (integrate_first)
         timed("integrate1_bin", [&] {
-            hipLaunchKernelGGL(k_integrate1_bin<1>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
+            hipLaunchKernelGGL(k_integrate1_bin<STEP_RESORT>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
         });
     else
     {
         HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(nCellAlloc_ + 1), stream_));
         timed("bin", [&] {
-            hipLaunchKernelGGL(k_integrate1_bin<0>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
+            hipLaunchKernelGGL(k_integrate1_bin<STEP_BIN_ONLY>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
         });
     }
@@ -1121,11 +1109,11 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     timed("rank_gather", [&] {
         hipLaunchKernelGGL(k_rank_gather, dim3(gridAtoms), dim3(kBlock), 0, stream_, dCounts_, dCellStart_, dTmpId_, dTmpSrc_, dTmpCell_, cur(), oth(),
                            dCellOfSorted_, (P_.tstat == AZTOT_TSTAT_RADI || P_.use_radii || thermoTouched_) ? 2 : 0, P_, dCounts_, bonded_.idxOfId, ref_,
-                           dHaloInfo_, (listsOn_ && stepMode == 1 && lazyOn_ && lazyK_ > 1) ? dNoList_ + 2 : nullptr, listsOn_ ? dRel_ : nullptr);
+                           dHaloInfo_, (listsOn_ && stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? dNoList_ + 2 : nullptr, listsOn_ ? dRel_ : nullptr);
     });
     cur_ ^= 1;
     sinceSort_ = 0;
-    if (!capturing_ && stepMode == 1) rebuilds_++;
+    if (!capturing_ && stepMode == STEP_RESORT) rebuilds_++;
     listsValid_ = false;            // (until this step's launch_pair records them)
     if (nranks_ > 1 && lazyOn_ && lazyK_ > 1)
     {   // where the boundary layers sit in the sorted arrays: [ownedBegin, end of layer 2hw-1) goes left, [start of layer ncx-2hw, ownedEnd) goes right;
@@ -1168,7 +1156,7 @@ void Engine::forces(bool withBonded)
     settle();
     snap_.valid = false;
     sinceSort_ = 1 << 30;           // a sort interval does not run on through a force call (it re-bins wrapped coordinates)
-    sort_and_forces(0, withBonded);
+    sort_and_forces(STEP_BIN_ONLY, withBonded);
     sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false;
     // energies of this configuration; kinetic energy and wall counters are left untouched
     unsigned mask = (1u << PS_EVDW) | (1u << PS_ECOUL) | (1u << PS_DROPPED);
@@ -1195,9 +1183,9 @@ void Engine::launch_step_kernels()
     // plain NVE steps leave integrate2 to somebody else (decided once, in the constructor): small systems / slabs -> the tile
     // kernel's epilogue (fuseEpilogue_); large ones -> the next step's k_integrate1_bin (lazyKick_, see finish_steps)
     fuseNow_ = fuseEpilogue_;
-    const int stepMode = (lazyOn_ && sinceSort_ < lazyK_ - 1) ? 2 : 1;
+    const int stepMode = (lazyOn_ && sinceSort_ < lazyK_ - 1) ? STEP_PLAIN : STEP_RESORT;
     // is there a next step before the host looks or the cycle ends, and is it a plain one?
-    const int sinceAfter = (stepMode == 2) ? sinceSort_ + 1 : 0;
+    const int sinceAfter = (stepMode == STEP_PLAIN) ? sinceSort_ + 1 : 0;
     const bool nextPlain = lazyOn_ && sinceAfter < lazyK_ - 1 && stepsLeftInRun_ > 0;
     {   // does this step's pair kernel also open the next step?  Only if this step walks the lists (k_pair_list and its clean-up launch carry the epilogue)
         const bool lists = listsOn_ && lazyOn_ && lazyK_ > 1 && pair_variant() == 2;
@@ -1212,12 +1200,12 @@ void Engine::launch_step_kernels()
     const bool fused = fuseNow_;                 // launch_pair drops the request if the tile kernel is not the one running
     fuseNow_ = false;
     ekinFromPair_ = fused;
-    // radiative thermostat without equilibration scaling: nothing global happens between the second half-kick and the thermostat - one launch (debug bit
-    // 4194304: two, as everywhere else)
+    // radiative thermostat without equilibration scaling: nothing global happens between the second half-kick and the thermostat - one launch
+    // (DBG_KICK_POST_SPLIT: two, as everywhere else)
     const bool closed = pairClosedStep_;           // (thermostat run, fused: the pair kernel has closed this step and opened the next)
-    const bool kickAndPost = !closed && !fused && !lazyKick_ && !equil && P_.tstat == AZTOT_TSTAT_RADI && !(debug_ & 4194304);
-    // ... and when a plain step follows, the same launch opens it (k_boundary_radi; debug bit 33554432: no)
-    if (kickAndPost && nextPlain && !(debug_ & 33554432))
+    const bool kickAndPost = !closed && !fused && !lazyKick_ && !equil && P_.tstat == AZTOT_TSTAT_RADI && !(debug_ & DBG_KICK_POST_SPLIT);
+    // ... and when a plain step follows, the same launch opens it (k_boundary_radi; DBG_NO_BOUNDARY_RADI: no)
+    if (kickAndPost && nextPlain && !(debug_ & DBG_NO_BOUNDARY_RADI))
     {
         StepParams Q = P_;
         Q.cycleStep = sinceSort_ + 1;              // of the step being opened
@@ -1306,15 +1294,13 @@ void Engine::choose_optimism()
 // restart needs (aztot_state + aztot_clock): everything else is rebuilt by the step that rebuilds the cells, and the replay opens with one.
 void Engine::take_snapshot()
 {
-    const size_t nd = sizeof(double) * (size_t)capacity_, ni = sizeof(int32_t) * (size_t)capacity_;
     if (!snap_.A.x)
     {
-        auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); allocs_.push_back(p); return p; };
+        const size_t nAtoms = (size_t)capacity_;
         double** d[] = {&snap_.A.x, &snap_.A.y, &snap_.A.z, &snap_.A.vx, &snap_.A.vy, &snap_.A.vz, &snap_.A.fx, &snap_.A.fy, &snap_.A.fz, &snap_.A.U, &snap_.A.rad};
-        for (auto pp : d) *pp = (double*)alloc(nd);
-        snap_.A.type = (int32_t*)alloc(ni); snap_.A.id = (int32_t*)alloc(ni);
-        snap_.stats = alloc(sizeof(DevStats)); snap_.counts = alloc(sizeof(Counts));
-        snap_.partials = (double*)alloc(sizeof(double) * (size_t)PS_COUNT * maxBlocks_);
+        for (auto pp : d) *pp = dev_alloc<double>(nAtoms);
+        snap_.A.type = dev_alloc<int32_t>(nAtoms); snap_.A.id = dev_alloc<int32_t>(nAtoms);
+        snap_.stats = dev_alloc<DevStats>(1); snap_.counts = dev_alloc<Counts>(1); snap_.partials = dev_alloc<double>((size_t)PS_COUNT * maxBlocks_);
     }
     const AtomArrays& A = cur();
     StateCopy C;
@@ -1511,12 +1497,12 @@ int Engine::graph_cycle() const
 
 bool Engine::can_graph() const
 {
-    // slab ranks: only with the loopback transport and only on request (debug bit 4096) - an experiment, see DESIGN.md section 6
-    const bool slabGraph = nranks_ > 1 && ownedXch_ && (debug_ & 4096) && !(P_.nEq > 0 || P_.tstat == AZTOT_TSTAT_NOSE);
+    // slab ranks: only with the loopback transport and only on request (DBG_SLAB_GRAPH) - an experiment, see DESIGN.md section 6
+    const bool slabGraph = nranks_ > 1 && ownedXch_ && (debug_ & DBG_SLAB_GRAPH) && !(P_.nEq > 0 || P_.tstat == AZTOT_TSTAT_NOSE);
     // Replaying captured cycles pays where a step is a handful of microsecond kernels.  On 1 M atoms the kernels are long enough for plain asynchronous
     // launches to keep the GPU busy, and each hipGraphLaunch costs a 40 us bubble in front of its first kernel (rocprofv3 kernel trace): 0.1594 ms/step
-    // replayed, 0.1575 launched one by one; 40 000 atoms: 0.0184 replayed, 0.0187 one by one.  (Debug bit 8388608: replay whatever the size.)
-    const bool worthIt = capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & 8388608);
+    // replayed, 0.1575 launched one by one; 40 000 atoms: 0.0184 replayed, 0.0187 one by one.  (DBG_GRAPH_ALWAYS: replay whatever the size.)
+    const bool worthIt = capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_GRAPH_ALWAYS);
     return opt_.use_graph && worthIt && (nranks_ == 1 || slabGraph) && !profile_ && !equil_phase();
 }
 
@@ -1636,7 +1622,7 @@ void Engine::prepare_next_call()
         const PairLists pl = pair_lists();
         P_.cycleStep = 0;
         HIP_CHECK(hipMemsetAsync(dNoList_ + 2, 0, sizeof(int32_t), stream_));
-        launch_build_lists(P_, dCellStart_, stream_, PairRange(), pl);
+        launch_build_lists(pair_launch(P_), PairRange(), pl);
         check_launch("list building");
         sync();
         {
@@ -1645,7 +1631,7 @@ void Engine::prepare_next_call()
             unlistedState_ = (nl[2] == 0) ? 1 : 2;
             // the first lists of an engine's life: size the LDS tiles from what the cells really hold right away (adapt_sort_interval does the same at
             // every look) - the next call then walks them at full occupancy
-            if (nl[5] == 0 && nl[6] == 0 && nl[3] > 0 && !(debug_ & 65536))
+            if (nl[5] == 0 && nl[6] == 0 && nl[3] > 0 && !(debug_ & DBG_SHORT_LISTS))
             {
                 const int candLds = tile_records_for(P_, pl, nl[3], candCap_, nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms);
                 const int iterLds = std::max(2 * kListMinIter, std::min(iterCap_, (nl[4] + nl[4] / 8 + 2 + 7) & ~7));
@@ -1701,7 +1687,7 @@ bool Engine::adapt_sort_interval()
         // 64 atoms) - then the plain steps go back to staging every cell
         int32_t nl[16];
         std::memcpy(nl, (const char*)hLook_ + sizeof(Counts), sizeof(nl));
-        if ((debug_ & 2097152) && nl[1] > 0)
+        if ((debug_ & DBG_LIST_STATS) && nl[1] > 0)
         {   // measurement aid: mean list length / tile size / atoms per cell over the cells recorded since the last look
             std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates, %.2f atoms\n", (double)nl[8] / nl[1], (double)nl[9] / nl[1], (double)nl[10] / nl[1]);
             HIP_CHECK(hipMemset(dNoList_ + 8, 0, sizeof(int32_t) * 3));
@@ -1721,7 +1707,7 @@ bool Engine::adapt_sort_interval()
             int iterLds = std::max(2 * kListMinIter, std::min(iterCap_, (nl[4] + nl[4] / 8 + 2 + 7) & ~7));
             if (nl[5] > 0) candLds = std::min(candCap_, std::max(candLds, candLds_ + 32));
             if (nl[6] > 0) iterLds = std::min(iterCap_, std::max(iterLds, iterLds_ + 8));
-            if (debug_ & 65536) { candLds = candLds_; iterLds = iterLds_; }
+            if (debug_ & DBG_SHORT_LISTS) { candLds = candLds_; iterLds = iterLds_; }
             // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
             // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
             {
@@ -1730,7 +1716,7 @@ bool Engine::adapt_sort_interval()
                 if (tileNow > 13.0 * 1024 || nl[4] > 96) wWant = std::max(wWant, 2);
                 if (tileNow > 26.0 * 1024 || nl[4] > 192) wWant = 4;
                 const bool forced = opt_.waves_per_cell == 1 || opt_.waves_per_cell == 2 || opt_.waves_per_cell == 4;
-                if (wWant > listWaves_ && !forced && !(debug_ & 65536))
+                if (wWant > listWaves_ && !forced && !(debug_ & DBG_SHORT_LISTS))
                 {
                     const int itersNew = std::max(2 * kListMinIter, ((int)(nl[4] * (double)listWaves_ / wWant * 1.3) + 8 + 7) & ~7);
                     const int candNew = std::max(candCap_, kListMinCand * wWant);
@@ -1746,7 +1732,7 @@ bool Engine::adapt_sort_interval()
             const bool capFull = (nl[5] > 0 && candLds_ == candCap_) || (nl[6] > 0 && iterLds_ == iterCap_);
             // (one GPU: ANY cell that does not fit costs an engine that runs without the clean-up launch a window of steps run again, so the arrays grow at once
             //  while they still can; slab ranks and the last growth wait until it is more than a handful)
-            if (capFull && !(debug_ & 65536) && (double)(nl[5] + nl[6]) > ((nranks_ == 1 && listGrowths_ < 3) ? 0.0 : 0.0005 * (double)nl[1]))
+            if (capFull && !(debug_ & DBG_SHORT_LISTS) && (double)(nl[5] + nl[6]) > ((nranks_ == 1 && listGrowths_ < 3) ? 0.0 : 0.0005 * (double)nl[1]))
             {   // the arrays themselves are too small: larger ones if the limits allow (twice), and the next step rebuilds; else - cells of more than 64 atoms
                 // never fit - the plain steps go back to staging once that is more than 2 % of the cells
                 const int cand = nl[5] > 0 ? std::min(kListCandMax, (candCap_ * 3 / 2 + 63) & ~63) : candCap_;
@@ -1759,7 +1745,7 @@ bool Engine::adapt_sort_interval()
                 candLds_ = candLds; iterLds_ = iterLds;
                 destroy_graphs(); graphCycle_ = 0;        // (launch parameters are baked into the graphs)
             }
-            if (listsOn_ && (double)nl[0] > 0.02 * (double)nl[1] && !(debug_ & 65536) && nl[5] + nl[6] < nl[0] / 2)
+            if (listsOn_ && (double)nl[0] > 0.02 * (double)nl[1] && !(debug_ & DBG_SHORT_LISTS) && nl[5] + nl[6] < nl[0] / 2)
             {   // mostly cells of more than 64 atoms: no list will ever hold them
                 listsOn_ = false; listsValid_ = false; destroy_graphs(); graphCycle_ = 0;
             }
@@ -1798,7 +1784,7 @@ bool Engine::adapt_sort_interval()
     int K = lazyK_;
     // one GPU without the clean-up launch: a violation, or a cell that kept no list, means the steps since the last look were not exact
     const bool goBack = optimistic_ && (c.lazyViolatedEver != 0 || unlistedAtLook_);
-    if (debug_ & 8192)
+    if (debug_ & DBG_FIXED_INTERVAL)
     {   // debug: fixed interval whatever the speeds (exercises the wider-stencil fallback); violations are only counted
         if (c.lazyViolatedEver)
         {
@@ -2033,7 +2019,7 @@ void Engine::set_state(const aztot_state& in)
     sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false;       // the next call rebuilds the cells
     if (in.vx || in.vy || in.vz || in.fx || in.fy || in.fz)
     {   // new velocities / forces: the interval measured on the old ones says nothing about them - every step rebuilds until the first look
-        if (lazyK_ != 1 && !(debug_ & 8192)) { lazyK_ = 1; destroy_graphs(); graphCycle_ = 0; }
+        if (lazyK_ != 1 && !(debug_ & DBG_FIXED_INTERVAL)) { lazyK_ = 1; destroy_graphs(); graphCycle_ = 0; }
         lazyMeasured_ = false; lazyWindow_ = 8; sinceLook_ = 0; lastLookLen_ = 0.0;
     }
     Counts c;
@@ -2111,20 +2097,13 @@ int Engine::rdf_setup(double rmax, double dr, bool nuclei)
     const size_t nEnt = (size_t)R.nBins * (size_t)(nPairS + nPairN);
     R.copies = (4 * nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget) ? 4 : (nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget ? 1 : 0);
     R.blocks = std::max(1, std::min(kRdfMaxBlocks, div_up(N, kBlock)));
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 8))); R.allocs.push_back(p); return p; };
     const size_t n = (size_t)std::max(N, 1);
-    R.cellOf = (int32_t*)alloc(n * 4); R.rankOf = (int32_t*)alloc(n * 4); R.kind = (int32_t*)alloc(n * 4);
-    R.x = (double*)alloc(n * 8); R.y = (double*)alloc(n * 8); R.z = (double*)alloc(n * 8);
-    R.cellCount = (int32_t*)alloc((size_t)G.nCell * 4);
-    R.cellStart = (int32_t*)alloc((size_t)(G.nCell + 1) * 4);
-    R.chunkTot = (int32_t*)alloc((size_t)div_up(G.nCell, kScanChunk) * 4);
-    R.histS = (unsigned long long*)alloc((size_t)R.nBins * nPairS * 8);
-    R.histN = (unsigned long long*)alloc((size_t)R.nBins * std::max(nPairN, 1LL) * 8);
-    R.scanCounts = (Counts*)alloc(sizeof(Counts));
-    R.scanStats = (DevStats*)alloc(sizeof(DevStats));
-    HIP_CHECK(hipMemsetAsync(R.cellCount, 0, (size_t)G.nCell * 4, stream_));
-    HIP_CHECK(hipMemsetAsync(R.scanCounts, 0, sizeof(Counts), stream_));
-    HIP_CHECK(hipMemsetAsync(R.scanStats, 0, sizeof(DevStats), stream_));
+    R.cellOf = dev_alloc<int32_t>(n, false, &R.allocs); R.rankOf = dev_alloc<int32_t>(n, false, &R.allocs); R.kind = dev_alloc<int32_t>(n, false, &R.allocs);
+    R.x = dev_alloc<double>(n, false, &R.allocs); R.y = dev_alloc<double>(n, false, &R.allocs); R.z = dev_alloc<double>(n, false, &R.allocs);
+    R.cellCount = dev_alloc<int32_t>((size_t)G.nCell, true, &R.allocs); R.cellStart = dev_alloc<int32_t>((size_t)(G.nCell + 1), false, &R.allocs);
+    R.chunkTot = dev_alloc<int32_t>((size_t)div_up(G.nCell, kScanChunk), false, &R.allocs);
+    R.histS = dev_alloc<unsigned long long>((size_t)R.nBins * nPairS, false, &R.allocs); R.histN = dev_alloc<unsigned long long>((size_t)R.nBins * std::max(nPairN, 1LL), false, &R.allocs);
+    R.scanCounts = dev_alloc<Counts>(1, true, &R.allocs); R.scanStats = dev_alloc<DevStats>(1, true, &R.allocs);
     rdf_reset();
     return R.nBins;
 }

@@ -381,9 +381,10 @@ __device__ __forceinline__ int wave_append(bool flag, int32_t* counter)
 // In slab mode the same kernel also packs this rank's message to each x-neighbour (slab.hip.h describes the protocol):
 // emigrants (full state) and the atoms of the hw boundary layers (position, type, id, radius), appended with one atomic per
 // wave and category.
-// STEPMODE 0: bin only (aztot_forces: wraps what a lazy run left unwrapped, counts nothing); 1: integrate + wrap + bin (a step that re-sorts:
-// every step unless the lazy re-sort is on); 2: integrate only (a plain step of the lazy re-sort: coordinates stay UNWRAPPED until the next sort,
+// STEPMODE STEP_BIN_ONLY: bin only (aztot_forces: wraps what a lazy run left unwrapped, counts nothing); STEP_RESORT: integrate + wrap + bin (a step that re-sorts:
+// every step unless the lazy re-sort is on); STEP_PLAIN: integrate only (a plain step of the lazy re-sort: coordinates stay UNWRAPPED until the next sort,
 // wall crossings are still counted in the step they happen, and the displacement since the last sort is checked against the cells' slack)
+enum StepMode { STEP_BIN_ONLY = 0, STEP_RESORT = 1, STEP_PLAIN = 2 };
 template <int STEPMODE>
 __global__ __launch_bounds__(kBlock) void k_integrate1_bin(StepParams P, SpecTable S, AtomArrays A, Counts* __restrict__ cnt,
                                                            int32_t* __restrict__ cellOf, int32_t* __restrict__ slotOf,
@@ -391,30 +392,30 @@ __global__ __launch_bounds__(kBlock) void k_integrate1_bin(StepParams P, SpecTab
                                                            MsgLayout lay, char* __restrict__ sendLeft, char* __restrict__ sendRight,
                                                            DevStats* __restrict__ st, RefPos R0)
 {
-    constexpr bool INTEGRATE = STEPMODE != 0;
-    constexpr bool BIN = STEPMODE != 2;
+    constexpr bool INTEGRATE = STEPMODE != STEP_BIN_ONLY;
+    constexpr bool BIN = STEPMODE != STEP_PLAIN;
     __shared__ double scratch[kBlock / kWave];
     const int begin = cnt->ownedBegin, end = cnt->ownedEnd;
     const int i = begin + blockIdx.x * kBlock + threadIdx.x;
     const bool pendingKick = INTEGRATE && st->pendingKick != 0;   // written only by kernels that run between two launches of this one
-    if (INTEGRATE && blockIdx.x == 0 && threadIdx.x == 0) { st->step += 1; if (STEPMODE == 1) st->stepAtSort = st->step; }   // the step in flight gets its 1-based number (main.cpp:92);
+    if (INTEGRATE && blockIdx.x == 0 && threadIdx.x == 0) { st->step += 1; if (STEPMODE == STEP_RESORT) st->stepAtSort = st->step; }   // the step in flight gets its 1-based number (main.cpp:92);
                                                                            // read only by the thermostat kernels at the end of the step
     double eField = 0.0, mom[6] = {0, 0, 0, 0, 0, 0}, cross[6] = {0, 0, 0, 0, 0, 0}, stepLen2 = 0.0;
     int anyCross = 0, myCell = 0, myLayer = 0, violated = 0;
-    if (STEPMODE == 1 && blockIdx.x == 0 && threadIdx.x == 0)
+    if (STEPMODE == STEP_RESORT && blockIdx.x == 0 && threadIdx.x == 0)
     {   // the cells are rebuilt in this step: nobody has moved since
         cnt->lazyViolated = 0;
         cnt->cycMaxRun = (unsigned long long)__double_as_longlong(0.81 * __longlong_as_double((long long)cnt->cycMaxRun));
     }
     // plain step s: what the atoms can have moved by before this step
     double roomLeft = -1.0;                                          // < 0: check every atom against its reference position
-    if (STEPMODE == 2 && P.pad2)
+    if (STEPMODE == STEP_PLAIN && P.boundSkip)
         roomLeft = sqrt(P.lazySlack2) - (double)(P.cycleStep - 1) * sqrt(__longlong_as_double((long long)__hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
     if (i < end)
     {
         const int t = A.type[i];
         double x = A.x[i], y = A.y[i], z = A.z[i];
-        if (STEPMODE == 0 && P.lazySlack2 > 0.0)
+        if (STEPMODE == STEP_BIN_ONLY && P.lazySlack2 > 0.0)
         {   // aztot_forces between two sorts of a lazy run: wrap first (crossings were counted when they happened)
             wrap_coord(x, P.L[0], P.invL[0]); wrap_coord(y, P.L[1], P.invL[1]); wrap_coord(z, P.L[2], P.invL[2]);
             A.x[i] = x; A.y[i] = y; A.z[i] = z;
@@ -477,7 +478,7 @@ __global__ __launch_bounds__(kBlock) void k_integrate1_bin(StepParams P, SpecTab
         {   // thousands of workgroups on one word would serialise (~90 atomics per microsecond): look first, only a new maximum is published
             const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
             if (bits > __hip_atomic_load(&cnt->maxStep2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->maxStep2, bits);
-            if (STEPMODE == 2 && P.pad2 && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
+            if (STEPMODE == STEP_PLAIN && P.boundSkip && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
         }
         if (!BIN && __syncthreads_or(violated) && threadIdx.x == 0)
         {   // (an earlier violation keeps its step; all writers of one launch write the same value)
@@ -556,7 +557,7 @@ __global__ __launch_bounds__(kBlock) void k_integrate_plain2(StepParams P, SpecT
     const bool pendingKick = st->pendingKick != 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->step += 1;
     double roomLeft = -1.0;
-    if (P.pad2)
+    if (P.boundSkip)
         roomLeft = sqrt(P.lazySlack2) - (double)(P.cycleStep - 1) * sqrt(__longlong_as_double((long long)__hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
     double mom[6] = {0, 0, 0, 0, 0, 0}, cross[6] = {0, 0, 0, 0, 0, 0}, stepLen2 = 0.0;
     int anyCross = 0, violated = 0;
@@ -614,7 +615,7 @@ __global__ __launch_bounds__(kBlock) void k_integrate_plain2(StepParams P, SpecT
         {
             const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
             if (bits > __hip_atomic_load(&cnt->maxStep2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->maxStep2, bits);
-            if (P.pad2 && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
+            if (P.boundSkip && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
         }
         if (__syncthreads_or(violated) && threadIdx.x == 0)
         {
@@ -1143,7 +1144,7 @@ __global__ __launch_bounds__(kBlock) void k_boundary_radi(StepParams P, SpecTabl
     const long long closing = st->stepAtSort + (long long)(P.cycleStep - 1);
     if (gid == 0) { st->pendingKick = 0; st->step = closing + 1; }
     double roomLeft = -1.0;
-    if (P.pad2)
+    if (P.boundSkip)
         roomLeft = sqrt(P.lazySlack2) - (double)(P.cycleStep - 1) * sqrt(__longlong_as_double((long long)__hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
     double kin = 0.0, uSum = 0.0, mom[6] = {0, 0, 0, 0, 0, 0}, cross[6] = {0, 0, 0, 0, 0, 0}, stepLen2 = 0.0;
     int anyCross = 0, violated = 0;
@@ -1197,7 +1198,7 @@ __global__ __launch_bounds__(kBlock) void k_boundary_radi(StepParams P, SpecTabl
         {
             const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
             if (bits > __hip_atomic_load(&cnt->maxStep2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->maxStep2, bits);
-            if (P.pad2 && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
+            if (P.boundSkip && bits > __hip_atomic_load(&cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&cnt->cycMaxRun, bits);
         }
         if (__syncthreads_or(violated) && threadIdx.x == 0)
         {

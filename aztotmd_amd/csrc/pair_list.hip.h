@@ -33,18 +33,18 @@ __host__ __device__ inline int list_atoms_per_wave(int nAtoms, int W) { return (
 __host__ __device__ inline int list_slices(int nAtomsOfWave) { const int n = kWave / (nAtomsOfWave > 0 ? nAtomsOfWave : 1); return n > kListMaxSlices ? kListMaxSlices : (n < 1 ? 1 : n); }
 
 // LDS of k_pair_list by kernel mode (LDS per wave bounds its occupancy, so every byte per candidate counts):
-//   one species, LJ (MODE 1)            records {x, y, z} of 24 B; a list entry is the record's byte offset
-//   table-driven modes (2, 3, 5)        [pair table 1 KiB][species bytes, kListTypeBytes][records of 24 B]; a list entry is the record NUMBER (the species byte
+//   one species, LJ (PM_ONE_LJ)         records {x, y, z} of 24 B; a list entry is the record's byte offset
+//   table-driven modes (PM_TAB*)        [pair table 1 KiB][species bytes, kListTypeBytes][records of 24 B]; a list entry is the record NUMBER (the species byte
 //                                       sits at a fixed offset + number, the record at number x 24 + base: one v_mad more per visit, 8 B less per candidate)
-//   radii (MODE 4) / generic (MODE 0)   [records of 24 B][radii, 8 B each][species bytes (MODE 0)]; entry = record number.  (Records of 32 B {x, y, z, radius}
+//   PM_ONE_SURK / PM_GENERIC            [records of 24 B][radii, 8 B each][species bytes (PM_GENERIC)]; entry = record number.  (Records of 32 B {x, y, z, radius}
 //                                       were tried first: a stride of 8 banks leaves 8 distinct bank groups for 64 lanes - 90 % of the LDS cycles of the
 //                                       case-study-2 kernel were bank conflicts; 24 B = 6 banks gives 32)
-inline bool pair_list_tab_mode(const StepParams& P) { return P.pad1 == 2 && !P.single_lj; }
+inline bool pair_list_tab_mode(const StepParams& P) { return P.potSet == POTSET_ONE_FAMILY && !P.single_lj; }
 inline size_t pair_list_lds_bytes(const StepParams& P, const PairLists& L)
 {
     const bool tab = pair_list_tab_mode(P);
-    const bool generic = !P.single_lj && P.pad1 != 2 && P.pad1 != 4;
-    const bool radii = !P.single_lj && !tab;                       // MODE 4 and MODE 0
+    const bool generic = !P.single_lj && P.potSet == POTSET_GENERIC;
+    const bool radii = !P.single_lj && !tab;                       // PM_ONE_SURK and PM_GENERIC
     size_t b = (size_t)(L.candLds + 1) * 24;
     if (tab) b += sizeof(double) * kLjSpecMax * kLjSpecMax * kPairTabStride + (((size_t)L.candLds + 1 + 15) & ~(size_t)15);
     if (radii) b += sizeof(double) * (size_t)(L.candLds + 1);
@@ -67,18 +67,18 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
                                                      double* __restrict__ partials, int maxBlocks, const Counts* __restrict__ counts, int blockBase, PairLists L,
                                                      NextStep N)
 {
-    constexpr bool kOneSpecies = (MODE == 1 || MODE == 4);           // no species table, no type ids
-    constexpr bool kRadii = (MODE == 0 || MODE == 4);
-    constexpr bool kTab = (MODE == 2 || MODE == 3 || MODE == 5);
+    constexpr bool kOneSpecies = pair_mode_one_species(MODE);
+    constexpr bool kRadii = pair_mode_reads_radii(MODE);
+    constexpr bool kTab = pair_mode_has_table(MODE);
     constexpr int RECB = 24;                                         // record {x, y, z} RELATIVE to the centre of the cell
-    constexpr int ESCALE = (MODE == 1) ? 1 : 24;                     // list entry -> byte offset of the record (only the one-species LJ kernel keeps byte offsets)
+    constexpr int ESCALE = (MODE == PM_ONE_LJ) ? 1 : 24;                     // list entry -> byte offset of the record (only the one-species LJ kernel keeps byte offsets)
     constexpr int kTabDoubles = kTab ? kLjSpecMax * kLjSpecMax * kPairTabStride : 0;
     extern __shared__ double ldsList[];
     double* const pairTab = ldsList;
     uint8_t* const ttypT = (uint8_t*)(ldsList + kTabDoubles);        // table modes: species ids by record number, at a compile-time offset
     char* const tb = (char*)(ldsList + kTabDoubles) + (kTab ? ((L.candLds + 1 + 15) & ~15) : 0);
-    double* const trad = (double*)(tb + (size_t)(L.candLds + 1) * RECB);         // MODE 0 / 4: radii (by record number)
-    uint8_t* const ttyp0 = (uint8_t*)(trad + (L.candLds + 1));                   // MODE 0 only: species ids (by record number)
+    double* const trad = (double*)(tb + (size_t)(L.candLds + 1) * RECB);         // modes that read radii (by record number)
+    uint8_t* const ttyp0 = (uint8_t*)(trad + (L.candLds + 1));                   // PM_GENERIC only: species ids (by record number)
 
     const int lane = threadIdx.x & (kWave - 1), wave = MULTI ? (int)(threadIdx.x >> 6) : 0;
     const int W = MULTI ? L.waves : 1;                               // waves of this workgroup = waves per cell (they share the tile, each serves its share of the atoms)
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         double radi = 0.0;
         int ti = 0;
         if (!kOneSpecies) ti = A.type[myl];
-        if ((MODE == 0 && P.use_radii) || MODE == 4) radi = A.rad[myl];
+        if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) radi = A.rad[myl];
         // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  Five groups are gathered whatever T is (stale
         // entries are atom indices too: the array starts out zeroed and only indices are ever written); all their loads travel together
         {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
                 const int j = (int)(e & 0x3FFFFFFu);
                 c.x = ld_f64(A.x, j); c.y = ld_f64(A.y, j); c.z = ld_f64(A.z, j);
                 c.typ = kOneSpecies ? 0 : ld_i32(A.type, j);
-                c.rad = ((MODE == 0 && P.use_radii) || MODE == 4) ? ld_f64(A.rad, j) : 0.0;
+                c.rad = ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) ? ld_f64(A.rad, j) : 0.0;
                 return c;
             };
             auto put = [&](auto IMG, int u, uint32_t e, const Cand& c) {
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
                 *(double*)r = xj - cc0; *(double*)(r + 8) = yj - cc1; *(double*)(r + 16) = zj - cc2;
                 if (kTab) ttypT[u * kWave + lane + 1] = (uint8_t)c.typ;
                 if (kRadii) trad[u * kWave + lane + 1] = c.rad;
-                if (MODE == 0) ttyp0[u * kWave + lane + 1] = (uint8_t)c.typ;
+                if (MODE == PM_GENERIC) ttyp0[u * kWave + lane + 1] = (uint8_t)c.typ;
             };
             // this wave's groups are wave + q W, q = 0, 1, ...  Five of them are gathered whatever T is - straight-line code, fifteen loads in flight together
             // (the builder fills all five groups of the array: behind the last candidate with the cell's first atom, one cache line for the whole wave)
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             *(double*)r = -1e30; *(double*)(r + 8) = -1e30; *(double*)(r + 16) = -1e30;
             if (kTab) ttypT[0] = 0;
             if (kRadii) trad[0] = 1.0;
-            if (MODE == 0) ttyp0[0] = 0;
+            if (MODE == PM_GENERIC) ttyp0[0] = 0;
         }
         __syncthreads();                                                // (one wave: no more than the wave barrier it replaces; the branch is uniform over the workgroup)
 
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         int nDropHalf = 0;
         double ljDropR2 = P.ljDropR2;
         if (kTab) asm volatile("" : "+v"(ljDropR2));                   // (table-driven modes: a vector register, like the uniforms of PairHot - see there)
-        const PairHot hot = kTab ? pair_hot_in_vgprs(P, lj) : (MODE == 1 ? pair_hot_lj_in_vgprs(P, lj) : pair_hot(P, lj));
+        const PairHot hot = kTab ? pair_hot_in_vgprs(P, lj) : (MODE == PM_ONE_LJ ? pair_hot_lj_in_vgprs(P, lj) : pair_hot(P, lj));
         const int nChunks = (nIter + 7) >> 3;
         // software-pipelined: the candidate of iteration t + 1 is read from LDS before the potential of iteration t is evaluated (entries behind a lane's
         // last one point at the dummy - the builder fills the list buffer with it - so the read ahead is always a valid one)
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             z = *(const double*)(tb + ko + 16);
             if (kTab) ty = ttypT[en];
             if (kRadii) rd = trad[en];
-            if (MODE == 0) ty = ttyp0[en];
+            if (MODE == PM_GENERIC) ty = ttyp0[en];
         };
         fetch(nIter > 0 ? (w.x & 0xFFFFu) : dummyOff, xj, yj, zj, tj, radj);
         for (int c = 0; c < nChunks; c++)
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             }
             w = wn;
         }
-        if (MODE != 0) acc.dropped += 0.5 * (double)nDropHalf;
+        if (MODE != PM_GENERIC) acc.dropped += 0.5 * (double)nDropHalf;
 
         // fold the slices of every atom (neighbouring lanes) in a fixed tree order and write the force: clear_force + pair sums
         if (NS == 4)
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     }
     // (the reductions are ~14 vector instructions each: skipped where the sum is known to be zero)
     if (ENG) eV = wave_sum(eV);
-    if (ENG && MODE != 1 && MODE != 4) eC = wave_sum(eC);
+    if (ENG && !pair_mode_one_species(MODE)) eC = wave_sum(eC);
     if (__any(dropped != 0.0)) dropped = wave_sum(dropped);
     // every wave books into its own partial-sum slot (fixed order of the final sums whatever W is)
     const size_t pb = (size_t)blockBase + (size_t)blockIdx.x * W + wave;
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         }
     }
     if (overflow) { no_list(5); return; }
-    if ((P.pad0 & 3) == 1) return;                                 // (phase timing: staging only)
+    if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 1) return;                                 // (phase timing: staging only)
 
     // ---- candidates: written out in whole groups of 64 (k_pair_list gathers whole groups: the last one is filled with a valid atom, the cell's first)
     {
@@ -608,7 +608,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         if (validA && kq == 0) { entN[a] = myOff; entC[a] = total; }
         nIter = max(nIter, ((total + NS - 1) * rcpNS) >> 16);
         if (hitBase > G.hitCap) { tooLong = 1; break; }              // (wave-uniform)
-        if ((P.pad0 & 3) == 2) continue;                           // (phase timing: no compaction)
+        if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 2) continue;                           // (phase timing: no compaction)
         // candidate k = 128 wd + kq + 4 p sits in record k + 1 of k_pair_list's tile
         uint16_t* dst = hits + myOff + below;
         for (int wd = 0; wd < nW; wd++)
@@ -624,10 +624,10 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if ((P.pad0 & 3) >= 2) return;                                 // (phase timing: no read-out)
+    if ((P.debugMask & DBG_BUILD_PHASE_MASK) >= 2) return;                                 // (phase timing: no read-out)
     nIter = wave_max_int(nIter);
-    // (debug bit 65536, tests: lists hold 14 iterations only - part of a liquid's cells then keep no list and go through the clean-up launch)
-    const bool usable = !tooLong && nIter <= ((P.pad0 & 65536) ? 14 : L.iterCap);
+    // (DBG_SHORT_LISTS, tests: lists hold 14 iterations only - part of a liquid's cells then keep no list and go through the clean-up launch)
+    const bool usable = !tooLong && nIter <= ((P.debugMask & DBG_SHORT_LISTS) ? 14 : L.iterCap);
     if (usable)
     {   // every lane of k_pair_list's layout collects ITS entries: lane = slot * NS + slice of wave w walks entries slice, slice + NS, ... of atom w aw + slot;
         // 0 = no candidate
@@ -661,33 +661,34 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         L.meta[4 * cell + 3] = nthis | (rcpNS << 12);
         if (T > L.noList[3]) atomicMax(&L.noList[3], T);           // (a read first: after the first few cells nobody has a new record to report)
         if (usable && nIter > L.noList[4]) atomicMax(&L.noList[4], nIter);
-        if (P.pad0 & 2097152) { atomicAdd(&L.noList[8], nIter); atomicAdd(&L.noList[9], T); atomicAdd(&L.noList[10], nthis); }      // measurement aid (slow)
+        if (P.debugMask & DBG_LIST_STATS) { atomicAdd(&L.noList[8], nIter); atomicAdd(&L.noList[9], T); atomicAdd(&L.noList[10], nthis); }      // measurement aid (slow)
         if (!usable) { atomicAdd(&L.noList[0], 1); atomicAdd(&L.noList[2], 1); atomicAdd(&L.noList[6], 1); }
     }
 }
 
 // the step that rebuilds the cells: candidates and pair lists of every cell (no forces; k_pair_list follows)
-inline void launch_build_lists(const StepParams& P, const int32_t* cellStart, hipStream_t stream, PairRange R, PairLists L)
+inline void launch_build_lists(const PairLaunch& C, PairRange R, PairLists L)
 {
-    pair_range_default(P, R);
+    pair_range_default(C.P, R);
     if (R.n == 0) return;
     const BuildLds G(L.candLds, L.iterLds, L.waves);
-    hipLaunchKernelGGL(k_build_lists, dim3(pair_range_grid(R.n)), dim3(kWave), G.bytes(), stream, P, cellStart, R.first, R.n, L);
+    hipLaunchKernelGGL(k_build_lists, dim3(pair_range_grid(R.n)), dim3(kWave), G.bytes(), C.stream, C.P, C.cellStart, R.first, R.n, L);
 }
 inline size_t build_lists_lds_bytes(const PairLists& L) { return BuildLds(L.candLds, L.iterLds, L.waves).bytes(); }
 
 template <int MODE, int VDW>
-inline void launch_pair_list_as(const StepParams& P, const SpecTable& S, const DevPot* pots, AtomArrays A, const Counts* cnt, const int32_t* cellStart, double* partials,
-                                int maxBlocks, hipStream_t stream, PairRange R, PairLists L, NextStep N, bool energies)
+inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, NextStep N, bool energies)
 {
-    const size_t lds = pair_list_lds_bytes(P, L);
+    const size_t lds = pair_list_lds_bytes(C.P, L);
     const dim3 grid(pair_range_grid(R.n)), block(kWave * L.waves);
-#define AZTOT_LAUNCH_LIST(E, M, T) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T>), grid, block, lds, stream, P, S, pots, A, cellStart, R.first, R.n, partials, maxBlocks, cnt, R.blockBase, L, N)
+    // thermostat-fused epilogue: modes that do not read radii (the thermostat rewrites them while other waves would still be gathering), never on a step
+    // whose energies are wanted (Engine::launch_step_kernels)
+    constexpr bool kCanFuseTstat = !pair_mode_reads_radii(MODE);
+#define AZTOT_LAUNCH_LIST(E, M, T) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T>), grid, block, lds, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials, C.maxBlocks, C.cnt, R.blockBase, L, N)
     if (N.photons)
-    {   // thermostat-fused epilogue: modes that do not read radii (the thermostat rewrites them while other waves would still be gathering), never on a step
-        // whose energies are wanted (Engine::launch_step_kernels)
-        if (energies || MODE == 0 || MODE == 4) throw std::runtime_error("k_pair_list: the thermostat cannot be fused into this launch");
-        if (MODE != 0 && MODE != 4) { if (L.waves == 1) AZTOT_LAUNCH_LIST(false, false, (MODE != 0 && MODE != 4)); else AZTOT_LAUNCH_LIST(false, true, (MODE != 0 && MODE != 4)); }
+    {
+        if (energies || !kCanFuseTstat) throw std::runtime_error("k_pair_list: the thermostat cannot be fused into this launch");
+        if (L.waves == 1) AZTOT_LAUNCH_LIST(false, false, kCanFuseTstat); else AZTOT_LAUNCH_LIST(false, true, kCanFuseTstat);
     }
     else if (L.waves == 1) { if (energies) AZTOT_LAUNCH_LIST(true, false, false); else AZTOT_LAUNCH_LIST(false, false, false); }
     else { if (energies) AZTOT_LAUNCH_LIST(true, true, false); else AZTOT_LAUNCH_LIST(false, true, false); }
@@ -696,23 +697,20 @@ inline void launch_pair_list_as(const StepParams& P, const SpecTable& S, const D
 
 // a plain step: the list kernel for every cell (launch_pair_list), then the clean-up launch of the staging kernel for the cells that keep no list
 // (launch_pair_cleanup; it books into the partial-sum slots behind the list kernel's).  Each returns the number of partial-sum slots it uses.
-inline int launch_pair_list(const StepParams& P, const SpecTable& S, const DevPot* pots, AtomArrays A, const Counts* cnt, const int32_t* cellStart,
-                            double* partials, int maxBlocks, hipStream_t stream, PairRange R, PairLists L, NextStep N = NextStep(), bool energies = true)
+inline int launch_pair_list(const PairLaunch& C, PairRange R, PairLists L, NextStep N = NextStep(), bool energies = true)
 {
-    pair_range_default(P, R);
+    pair_range_default(C.P, R);
     if (R.n == 0) return 0;
-    auto list = [&]() { AZTOT_PAIR_DISPATCH(launch_pair_list_as, P, S, pots, A, cnt, cellStart, partials, maxBlocks, stream, R, L, N, energies); };
-    list();
+    AZTOT_PAIR_DISPATCH(C.P, launch_pair_list_as, C, R, L, N, energies);
     return pair_range_grid(R.n) * L.waves;
 }
 
-inline int launch_pair_cleanup(const StepParams& P, const SpecTable& S, const DevPot* pots, AtomArrays A, const Counts* cnt, const int32_t* cellStart,
-                               double* partials, int maxBlocks, hipStream_t stream, PairRange R, PairLists L, NextStep N = NextStep())
+inline int launch_pair_cleanup(const PairLaunch& C, PairRange R, PairLists L, NextStep N = NextStep())
 {
-    pair_range_default(P, R);
+    pair_range_default(C.P, R);
     if (R.n == 0) return 0;
     R.blockBase += pair_range_grid(R.n) * L.waves;
-    launch_pair_tile(P, S, pots, A, cnt, cellStart, partials, maxBlocks, stream, R, L, 2, N);
+    launch_pair_tile(C, R, L, 2, N);
     return pair_cleanup_grid(R.n);
 }
 

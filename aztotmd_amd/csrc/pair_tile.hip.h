@@ -30,6 +30,24 @@ static_assert(kTileLds % 32 == 16, "coordinate arrays must be staggered by half 
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
 
+// Template parameters MODE and VDW of the pair kernels (k_pair_tile, k_pair_list, pair_body): `int`s with named values; what the kernels ask about them is asked here, once.
+//   PM_GENERIC any mix of potentials and species, radii: the switch-based pair_visit ; PM_ONE_LJ one species, Lennard-Jones only, no electrostatics ;
+//   PM_TAB <= 4 species, one potential family VDW, per-species-pair table in LDS, electrostatics none | direct | Fennell chosen at run time ; PM_TAB_EWALD as PM_TAB
+//   with the real-space term of the Ewald sum ; PM_TAB_FENNELL as PM_TAB with Fennell/DSF known when the kernel is compiled ; PM_ONE_SURK one species, surk with
+//   thermostat radii (case study 2)
+enum PairMode { PM_GENERIC = 0, PM_ONE_LJ = 1, PM_TAB = 2, PM_TAB_EWALD = 3, PM_ONE_SURK = 4, PM_TAB_FENNELL = 5 };
+// StepParams::vdwFamily.  1..4: the AZTOT_VDW_* type of the one family; VDW_MIXED: the four mixed, type looked up per species pair; VDW_LJ_NOCUT: Lennard-Jones
+// whose per-pair cut-off test always passes (Engine::construct)
+enum PairVdw { VDW_ANY = 0, VDW_LNJS = 1, VDW_BUCK = 2, VDW_P746 = 3, VDW_BMHS = 4, VDW_MIXED = 5, VDW_LJ_NOCUT = 6, VDW_SURK = 7 };
+constexpr bool pair_mode_has_table(int mode) { return mode == PM_TAB || mode == PM_TAB_EWALD || mode == PM_TAB_FENNELL; }
+constexpr bool pair_mode_reads_radii(int mode) { return mode == PM_GENERIC || mode == PM_ONE_SURK; }
+constexpr bool pair_mode_one_species(int mode) { return mode == PM_ONE_LJ || mode == PM_ONE_SURK; }      // no species table, no type ids
+constexpr bool pair_mode_ewald(int mode) { return mode == PM_TAB_EWALD; }          // Coulomb flavour fixed when the kernel is compiled ...
+constexpr bool pair_mode_fennell(int mode) { return mode == PM_TAB_FENNELL; }      // ... (PM_TAB looks at StepParams::elec_type)
+constexpr bool pair_vdw_is_lj(int vdw) { return vdw == VDW_LNJS || vdw == VDW_LJ_NOCUT; }
+constexpr bool pair_vdw_no_cut_test(int vdw) { return vdw == VDW_LJ_NOCUT; }
+constexpr bool pair_vdw_mixed(int vdw) { return vdw == VDW_MIXED; }
+
 
 // the tile kernel needs every neighbour cell to be reached through exactly one periodic image
 inline bool pair_tile_supported(const StepParams& P)
@@ -75,7 +93,7 @@ __device__ __forceinline__ int ld_i32(const int32_t* __restrict__ base, int j)
 // v_rcp_f64, branch-free potential.
 constexpr int kPairTabStride = 8;   // {p0..p4, r2cut, kqq, potential type} per ordered species pair.  Not one byte more: the Coulomb
                                     // kernels sit at 10 192 B of LDS, and 10 240 B is the limit for 16 waves per CU (+64 B cost 7 %)
-constexpr int kLjSpecMax = 4;      // MODE 2 keeps the per-species-pair Lennard-Jones / charge-product table in LDS
+constexpr int kLjSpecMax = 4;      // the table modes keep the per-species-pair Lennard-Jones / charge-product table in LDS
 
 // One pair visit of the specialised tile kernels: potential + electrostatics of the pair (i, candidate) at separation (dx, dy, dz), r2 = |d|^2.
 // `live` = the lane really has a candidate (only the unmasked Coulomb forms of tile_passes pass false).  Shared by the staging kernel below and
@@ -109,7 +127,7 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
                                           bool live, double dx, double dy, double dz, double r2, int ti, int tj, double radi, double radj, double ljDropR2,
                                           int& nDropHalf, PairAcc& ra, const PairHot& H)
 {
-    if (MODE == 1)
+    if (MODE == PM_ONE_LJ)
     {   // fer_lj vdw.cpp:16-26 ; pair_inter integrators.cpp:139-185.  The atom itself (r2 == 0 exactly: its own
         // cell is part of the tile, unshifted), candidates the conservative filter let through and dead lanes
         // are pushed out to a huge r2, where sr6 underflows to exactly 0 and with it energy and force.
@@ -141,7 +159,7 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
             ra.fx = fma(fm, dx, ra.fx); ra.fy = fma(fm, dy, ra.fy); ra.fz = fma(fm, dz, ra.fz);
         }
     }
-    else if (MODE == 4)
+    else if (MODE == PM_ONE_SURK)
     {   // one species, radius-dependent 'surk' potential (surk_pot cuVdW.cu:236-257; cuPairs.cu:145-146), no electrostatics: case
         // study 2.  U = a b r^-6 (C1 a^2 b^2 / r - C2 / (ka a + kb b)) with a, b the radii the radiative thermostat writes
         // (cuTemp.cu:757-759); same operation order as the generic kernel's vdw_force, branch-free like the Lennard-Jones body
@@ -159,29 +177,29 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
         const double fm = tooBig ? 0.0 : f;
         ra.fx = fma(fm, dx, ra.fx); ra.fy = fma(fm, dy, ra.fy); ra.fz = fma(fm, dz, ra.fz);
     }
-    else if (MODE >= 2)
+    else if (pair_mode_has_table(MODE))
     {   // one potential family for every species pair (VDW: 1 lnjs, 2 buck, 3 p746, 4 bmhs - fer_* of vdw.cpp:16-157), electrostatics
         // none, direct, Fennell/DSF (fennel elec.cpp:430-444) or the real-space Ewald term; parameters per species pair come from a
         // small LDS table {p0..p4, r2cut, kqq, aux}.  Branch-free: a pair outside its potential's cut-off is multiplied away.
-        // MODE 5 = MODE 2 with the electrostatics known when the kernel is compiled (Fennell/DSF): no wave-uniform branches inside the pair loop, which cost
-        // MODE 2 its instruction scheduling (every table read waited for on the spot) and, with three variants of the body alive, its scalar registers
+        // PM_TAB_FENNELL = PM_TAB with the electrostatics known when the kernel is compiled (Fennell/DSF): no wave-uniform branches inside the pair loop, which cost
+        // PM_TAB its instruction scheduling (every table read waited for on the spot) and, with three variants of the body alive, its scalar registers
         const double* pp = pairTab + (ti * P.nSpec + tj) * kPairTabStride;
-        // (Lennard-Jones family: slots 3 and 4 hold the force polynomial's constants 24 eps sigma^6 and 48 eps sigma^12, Engine::allocate - see MODE 1)
-        constexpr bool kLJ = (VDW == 1 || VDW == 6);                  // VDW 6: Lennard-Jones whose per-pair cut-off test always passes (Engine::construct)
-        const double tabP1 = kLJ ? pp[3] : pp[1], tabP2 = kLJ ? pp[4] : pp[2], tabCut = (VDW == 6) ? 0.0 : pp[5], tabKqq = pp[6];      // read whatever the pair turns out to be: the reads travel together
+        // (Lennard-Jones family: slots 3 and 4 hold the force polynomial's constants 24 eps sigma^6 and 48 eps sigma^12, Engine::allocate - see PM_ONE_LJ)
+        constexpr bool kLJ = pair_vdw_is_lj(VDW);
+        const double tabP1 = kLJ ? pp[3] : pp[1], tabP2 = kLJ ? pp[4] : pp[2], tabCut = pair_vdw_no_cut_test(VDW) ? 0.0 : pp[5], tabKqq = pp[6];      // read whatever the pair turns out to be: the reads travel together
         // (MASKED = the list kernel: an atom is never on its own list and idle lanes never meet the dummy candidate at r = 0, so r^2 > 0 needs no test)
         const bool pairOk = live & (MASKED || r2 > 0.0) & (r2 <= H.r2Max);
         if (MASKED && !pairOk) return;
         const double r2s = (MASKED || pairOk) ? r2 : 1e300;
-        const bool coul = (MODE == 3) || (MODE == 5) || (P.elec_type != 0);               // wave-uniform
+        const bool coul = pair_mode_ewald(MODE) || pair_mode_fennell(MODE) || (P.elec_type != AZTOT_ELEC_NONE);               // wave-uniform
         const bool needR = coul || !kLJ;
         const double ir = needR ? fast_rsqrt(r2s) : 0.0;
         const double r2i = needR ? ir * ir : fast_rcp(r2s);
         const double r = r2s * ir;
-        const bool vdwOk = (VDW == 6) || r2s <= tabCut;
+        const bool vdwOk = pair_vdw_no_cut_test(VDW) || r2s <= tabCut;
         double f;
         if (kLJ)
-        {   // fer_lj vdw.cpp:16-26 (p0 = 4 eps, p1 = sigma^2, p2 = 24 eps) as the polynomial f = u^4 (A2 u^3 - A1) in u = 1 / r^2, as in MODE 1
+        {   // fer_lj vdw.cpp:16-26 (p0 = 4 eps, p1 = sigma^2, p2 = 24 eps) as the polynomial f = u^4 (A2 u^3 - A1) in u = 1 / r^2, as in PM_ONE_LJ
             const double u2 = r2i * r2i, u3 = u2 * r2i;
             const double fl = (u2 * u2) * fma(tabP2, u3, -tabP1);
             f = vdwOk ? fl : 0.0;
@@ -195,26 +213,26 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
         {
             const double w = vdwOk ? 1.0 : 0.0;
             const double r4i = r2i * r2i, r6i = r4i * r2i;
-            const int pt = (VDW == 5) ? (int)pp[7] : VDW;                  // VDW 5: the families are mixed - per-pair type, divergent
+            const int pt = pair_vdw_mixed(VDW) ? (int)pp[7] : VDW;          // the families are mixed: per-pair type, divergent
             double e;
-            if (pt == 1)
+            if (pt == VDW_LNJS)
             {   // fer_lj vdw.cpp:16-26
                 const double sr2 = pp[1] * r2i, sr6 = sr2 * sr2 * sr2;
                 e = pp[0] * sr6 * (sr6 - 1.0);
                 f = pp[2] * r2i * sr6 * (2.0 * sr6 - 1.0);
             }
-            else if (pt == 2)
+            else if (pt == VDW_BUCK)
             {   // fer_buckingham vdw.cpp:60-70: A exp(-r/rho) - C/r^6 ; 1/rho in slot 3
                 const double ex = pp[0] * exp_nonpos(-r * pp[3]);
                 e = ex - pp[2] * r6i;
                 f = ex * ir * pp[3] - 6.0 * pp[2] * r4i * r4i;
             }
-            else if (pt == 3)
+            else if (pt == VDW_P746)
             {   // fer_746 vdw.cpp:144-157: p0/r^7 - p1/r^4 - p2/r^6
                 e = r4i * (pp[0] * r2i * ir - pp[1] - pp[2] * r2i);
                 f = r6i * (7.0 * pp[0] * r2i * ir - 4.0 * pp[1] - 6.0 * pp[2] * r2i);
             }
-            else if (pt == 4)
+            else if (pt == VDW_BMHS)
             {   // fer_bhm vdw.cpp:102-112: A exp(B (sigma - r)) - C/r^6 - D/r^8
                 const double ex = pp[0] * exp_nonpos(pp[1] * (pp[2] - r));
                 e = ex - pp[3] * r6i - pp[4] * r4i * r4i;
@@ -224,7 +242,7 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
             ra.eV = fma(0.5 * w, e, ra.eV);
             f *= w;
         }
-        if (MODE == 5 || (MODE == 2 && P.elec_type == 3))
+        if (pair_mode_fennell(MODE) || (MODE == PM_TAB && P.elec_type == AZTOT_ELEC_FENNEL))
         {
             const double kqq = (MASKED || pairOk) ? tabKqq : 0.0;
             const double ar = H.alpha * r;
@@ -233,7 +251,7 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
             ra.eC = fma(0.5 * kqq, erfcar * ir - P.el_scale + H.elScale2 * (r - P.rReal), ra.eC);
             f = fma(kqq * ir, (erfcar * r2i + H.daipi2 * ex * ir) - H.elScale2, f);
         }
-        else if (MODE == 3)
+        else if (pair_mode_ewald(MODE))
         {   // real-space term of the Ewald sum: coul_iter elec.cpp:344-369 (real_ewald cuElec.cu:94-113)
             const double kqq = (MASKED || pairOk) ? tabKqq : 0.0;
             const double ar = H.alpha * r;
@@ -242,7 +260,7 @@ __device__ __forceinline__ void pair_body(const StepParams& P, const SpecTable& 
             ra.eC = fma(0.5 * kqq, erfcar * ir, ra.eC);
             f = fma(kqq * ir * r2i, fma(H.daipi2 * r, ex, erfcar), f);
         }
-        else if (MODE == 2 && P.elec_type == 1)
+        else if (MODE == PM_TAB && P.elec_type == AZTOT_ELEC_DIRECT)
         {   // direct_coul elec.cpp:415-428
             const double kqq = (MASKED || pairOk) ? tabKqq : 0.0;
             ra.eC = fma(0.5 * kqq, ir, ra.eC);
@@ -345,9 +363,9 @@ __device__ __forceinline__ void tile_passes(const StepParams& P, const SpecTable
     constexpr int NS = kWave >> LG;
     const int iters = ((T + NS - 1) / NS + 3) & ~3;        // per-lane candidates, rounded up to the unroll factor
     const double r2Filter = P.r2Max * (1.0 + 1e-13);       // conservative pass-1 threshold
-    const double ljDropR2 = P.ljDropR2;                   // MODE 1: no pair beyond this r^2 can break the f^2 > 1e10 rule (Engine::construct)
+    const double ljDropR2 = P.ljDropR2;                   // PM_ONE_LJ: no pair beyond this r^2 can break the f^2 > 1e10 rule (Engine::construct)
     int nDropHalf = 0;
-    if (P.pad0 & 2048) return;                             // measurement aid (bench.py --debug 2048): staging only, forces are wrong
+    if (P.debugMask & DBG_STAGE_ONLY) return;                             // measurement aid (DBG_STAGE_ONLY): staging only, forces are wrong
     for (int rb = 0; rb < iters; rb += 32 * NW)
     {
         uint32_t m[4] = {0u, 0u, 0u, 0u};
@@ -371,7 +389,7 @@ __device__ __forceinline__ void tile_passes(const StepParams& P, const SpecTable
             else lst = dry ? 0u : lst;
             kbase += dry ? 32 * NS : 0;
             // (the Coulomb bodies are the exception: measured on C3 they lose 3 % to the EXEC-masked form, so they keep the dummy candidate)
-            constexpr bool kMaskBody = (MODE == 1 || MODE == 4);
+            constexpr bool kMaskBody = pair_mode_one_species(MODE);
             const bool live = cur != 0u;
             if (kMaskBody ? live : true)
             {
@@ -382,14 +400,14 @@ __device__ __forceinline__ void tile_passes(const StepParams& P, const SpecTable
             const double r2 = dx * dx + dy * dy + dz * dz;
             int tj = 0;
             double radj = 0.0;
-            if (MODE == 0 || MODE == 2 || MODE == 3 || MODE == 5) tj = ttyp[k];
-            if (MODE == 0 || MODE == 4) radj = trad[k];
+            if (!pair_mode_one_species(MODE)) tj = ttyp[k];
+            if (pair_mode_reads_radii(MODE)) radj = trad[k];
             pair_body<MODE, VDW>(P, S, pots, lj, pairTab, live, dx, dy, dz, r2, ti, tj, radi, radj, ljDropR2, nDropHalf, ra, pair_hot(P, lj));
             }
         } while (__any((cur | nxt | lst | ult) != 0u));
     }
 
-    if (MODE != 0) acc.dropped += 0.5 * (double)nDropHalf;     // dropped pairs, counted per lane in "half pair" units (every pair is visited from both ends)
+    if (MODE != PM_GENERIC) acc.dropped += 0.5 * (double)nDropHalf;     // dropped pairs, counted per lane in "half pair" units (every pair is visited from both ends)
 }
 
 // Lists of the lazy re-sort, written by k_build_lists and read by k_pair_list (both in pair_list.hip.h); the clean-up launch of k_pair_tile looks at the
@@ -510,10 +528,8 @@ __device__ __forceinline__ void next_step_finish(const StepParams& P, const Next
 }
 
 template <int MODE, int VDW, bool CLEANUP>
-                      // MODE 0: generic (any mix, radii) ; 1: one species, Lennard-Jones only ; 2: <= 4 species, one potential family VDW, elec none|dir|Fennell ;
-                      // 3: as 2 with the real-space term of the Ewald sum ; 4: one species, surk with thermostat radii (case study 2).
                       // CLEANUP: the clean-up launch behind k_pair_list - a small grid that strides over the cells and stages those without a list.
-__global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 1) void k_pair_tile(StepParams P, SpecTable S, const DevPot* __restrict__ pots, AtomArrays A,
+__global__ __launch_bounds__(kWave, pair_mode_has_table(MODE) ? 3 : 1) void k_pair_tile(StepParams P, SpecTable S, const DevPot* __restrict__ pots, AtomArrays A,
                                                      const int32_t* __restrict__ cellStart, int firstCell, int nCellsRun,
                                                      double* __restrict__ partials, int maxBlocks, const Counts* __restrict__ counts, int blockBase,
                                                      PairLists L, NextStep N, SplitArgs Z)
@@ -527,15 +543,15 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
         for (int k = 0; k < 3; k++) { P.hw[k] += 1; P.nOff[k] = 2 * P.hw[k] + 1; }
         P.pruneR2 = 1e300;
     }
-    constexpr bool kOneSpecies = (MODE == 1 || MODE == 4);           // no species table, no type ids
+    constexpr bool kOneSpecies = pair_mode_one_species(MODE);
     __shared__ double txyz[3 * kTileLds];                            // candidate coordinates RELATIVE to the centre of the centre cell
     __shared__ float tw[kTileLds];                                   // -(x^2 + y^2 + z^2) of the same, f32: 4th operand row of the filter
     double* const tx = txyz;
     double* const ty = txyz + kTileLds;
     double* const tz = txyz + 2 * kTileLds;
     __shared__ uint8_t ttyp[!kOneSpecies ? kTileLds : 1];               // species ids (< 16)
-    __shared__ double trad[(MODE == 0 || MODE == 4) ? kTileLds : 1];
-    __shared__ double pairTab[(MODE == 2 || MODE == 3 || MODE == 5) ? kLjSpecMax * kLjSpecMax * kPairTabStride : 1];
+    __shared__ double trad[pair_mode_reads_radii(MODE) ? kTileLds : 1];
+    __shared__ double pairTab[pair_mode_has_table(MODE) ? kLjSpecMax * kLjSpecMax * kPairTabStride : 1];
     __shared__ int32_t entJ[kWave], entN[kWave], entC[kWave];       // staging table: first atom, count (<= 64), image-shift code
 
     const int lane = threadIdx.x;
@@ -544,7 +560,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
     NextAcc nacc;
     next_acc_clear(nacc);
     const DevPot lj = pots[0];
-    if (MODE == 2 || MODE == 3 || MODE == 5)
+    if (pair_mode_has_table(MODE))
     {
         const int np = P.nSpec * P.nSpec;
         if (lane < np)
@@ -621,7 +637,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
             {
                 xi = A.x[myi] - cc0; yi = A.y[myi] - cc1; zi = A.z[myi] - cc2;
                 if (!kOneSpecies) ti = A.type[myi];
-                if ((MODE == 0 && P.use_radii) || MODE == 4) radi = A.rad[myi];
+                if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) radi = A.rad[myi];
             }
             // matrix-filter operand of this lane (used when the cell has <= 16 atoms): component `slice` of (2 xi, 2 yi, 2 zi, thr - |ri|^2).
             // Idle atom slots sit at 1e30: their column of the filter is -inf ("outside") whatever the candidate
@@ -642,7 +658,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
                 {
                     tx[T + lane] = -1e30; ty[T + lane] = 0.0; tz[T + lane] = 0.0; tw[T + lane] = -3e38f;
                     if (!kOneSpecies) ttyp[T + lane] = 0;          // a valid species: the parameter table is indexed with it
-                    if (MODE == 0 || MODE == 4) trad[T + lane] = 1.0;
+                    if (pair_mode_reads_radii(MODE)) trad[T + lane] = 1.0;
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (lg == 4) tile_passes<MODE, VDW, 4>(P, S, pots, lj, tx, ty, tz, tw, ttyp, trad, pairTab, T, slice, xi, yi, zi, ti, radi, filtB, filtC, acc);
@@ -731,7 +747,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
                             {
                                 xj = ld_f64(A.x, j); yj = ld_f64(A.y, j); zj = ld_f64(A.z, j);
                                 if (!kOneSpecies) typ0 = ld_i32(A.type, j);
-                                if ((MODE == 0 && P.use_radii) || MODE == 4) rad0 = ld_f64(A.rad, j);
+                                if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) rad0 = ld_f64(A.rad, j);
                             }
                             if (code0 != 0x15)
                             {
@@ -752,7 +768,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
                                 tx[pp] = xj; ty[pp] = yj; tz[pp] = zj;
                                 tw[pp] = -(float)(xj * xj + yj * yj + zj * zj);
                                 if (!kOneSpecies) ttyp[pp] = (uint8_t)typ0;
-                                if (MODE == 0 || MODE == 4) trad[pp] = rad0;
+                                if (pair_mode_reads_radii(MODE)) trad[pp] = rad0;
                             }
                             T += nk;
                             e += 1;
@@ -771,7 +787,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
                             {
                                 gx[u] = ld_f64(A.x, j); gy[u] = ld_f64(A.y, j); gz[u] = ld_f64(A.z, j);
                                 if (!kOneSpecies) gtyp[u] = ld_i32(A.type, j);
-                                if ((MODE == 0 && P.use_radii) || MODE == 4) grad[u] = ld_f64(A.rad, j);
+                                if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) grad[u] = ld_f64(A.rad, j);
                             }
                         }
 #pragma unroll
@@ -800,7 +816,7 @@ __global__ __launch_bounds__(kWave, (MODE == 2 || MODE == 3 || MODE == 5) ? 3 : 
                                     tx[pp] = xj; ty[pp] = yj; tz[pp] = zj;
                                     tw[pp] = -(float)(xj * xj + yj * yj + zj * zj);
                                     if (!kOneSpecies) ttyp[pp] = (uint8_t)gtyp[u];
-                                    if (MODE == 0 || MODE == 4) trad[pp] = grad[u];
+                                    if (pair_mode_reads_radii(MODE)) trad[pp] = grad[u];
                                 }
                                 T += __popcll(mask);
                             }
@@ -923,49 +939,48 @@ inline void pair_range_default(const StepParams& P, PairRange& R)
     if (R.n < 0) { R.n = pair_tile_cells(P); R.first = (P.nranks > 1) ? P.hw[0] * plane : 0; R.blockBase = 0; }
 }
 
+// what the pair launches of one step have in common (Engine::pair_launch)
+struct PairLaunch { const StepParams& P; const SpecTable& S; const DevPot* pots; AtomArrays A; const Counts* cnt; const int32_t* cellStart; double* partials; int maxBlocks; hipStream_t stream; };
+
 // listMode 0: stage every cell ; 2: clean-up launch - a small grid that stages the cells without a list
 template <int MODE, int VDW>
-inline void launch_pair_tile_as(const StepParams& P, const SpecTable& S, const DevPot* pots, AtomArrays A, const Counts* cnt, const int32_t* cellStart, double* partials,
-                                int maxBlocks, hipStream_t stream, PairRange R, PairLists L, int listMode, NextStep N, SplitArgs Z)
+inline void launch_pair_tile_as(const PairLaunch& C, PairRange R, PairLists L, int listMode, NextStep N, SplitArgs Z)
 {
-    pair_range_default(P, R);
+    pair_range_default(C.P, R);
     if (R.n == 0) return;
     if (listMode == 2)
-        hipLaunchKernelGGL((k_pair_tile<MODE, VDW, true>), dim3(pair_cleanup_grid(R.n)), dim3(kWave), 0, stream, P, S, pots, A, cellStart, R.first, R.n, partials, maxBlocks,
-                           cnt, R.blockBase, L, N, SplitArgs());
+        hipLaunchKernelGGL((k_pair_tile<MODE, VDW, true>), dim3(pair_cleanup_grid(R.n)), dim3(kWave), 0, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials,
+                           C.maxBlocks, C.cnt, R.blockBase, L, N, SplitArgs());
     else
-        hipLaunchKernelGGL((k_pair_tile<MODE, VDW, false>), dim3(pair_range_grid(R.n) * Z.n), dim3(kWave), 0, stream, P, S, pots, A, cellStart, R.first, R.n, partials,
-                           maxBlocks, cnt, R.blockBase, L, NextStep(), Z);
+        hipLaunchKernelGGL((k_pair_tile<MODE, VDW, false>), dim3(pair_range_grid(R.n) * Z.n), dim3(kWave), 0, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials,
+                           C.maxBlocks, C.cnt, R.blockBase, L, NextStep(), Z);
 }
 
-// dispatch on the potential set.  P.pad1 == 2: every defined pair potential belongs to the family P.vdwFamily (1 lnjs, 2 buck, 3 p746, 4 bmhs; 5 = a mix of
-// them, selected per species pair), <= 4 species, no radii, electrostatics none / direct / Fennell / Ewald with alpha rReal <= 4 (Engine::Engine decides)
-#define AZTOT_PAIR_DISPATCH(LAUNCH, ...)                                                                   \
-    do {                                                                                                   \
-        if (P.single_lj) { LAUNCH<1, 1>(__VA_ARGS__); return; }                                            \
-        if (P.pad1 == 4) { LAUNCH<4, 7>(__VA_ARGS__); return; }     /* one species, surk + radii */        \
-        if (P.pad1 == 2)                                                                                   \
-        {                                                                                                  \
-            const bool ew = P.elec_type == 2;                                                              \
-            switch (P.vdwFamily)                                                                           \
-            {                                                                                              \
-            case 1: if (ew) LAUNCH<3, 1>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 1>(__VA_ARGS__); else LAUNCH<2, 1>(__VA_ARGS__); return; \
-            case 2: if (ew) LAUNCH<3, 2>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 2>(__VA_ARGS__); else LAUNCH<2, 2>(__VA_ARGS__); return; \
-            case 3: if (ew) LAUNCH<3, 3>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 3>(__VA_ARGS__); else LAUNCH<2, 3>(__VA_ARGS__); return; \
-            case 4: if (ew) LAUNCH<3, 4>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 4>(__VA_ARGS__); else LAUNCH<2, 4>(__VA_ARGS__); return; \
-            case 5: if (ew) LAUNCH<3, 5>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 5>(__VA_ARGS__); else LAUNCH<2, 5>(__VA_ARGS__); return; \
-            case 6: if (ew) LAUNCH<3, 6>(__VA_ARGS__); else if (P.elec_type == 3) LAUNCH<5, 6>(__VA_ARGS__); else LAUNCH<2, 6>(__VA_ARGS__); return; \
-            }                                                                                              \
-        }                                                                                                  \
-        LAUNCH<0, 0>(__VA_ARGS__);                                                                         \
+// Dispatch on the potential set of P: LAUNCH<MODE, VDW>(...) for one of <PM_ONE_LJ, VDW_LNJS>, <PM_ONE_SURK, VDW_SURK>, <PM_GENERIC, VDW_ANY> or - POTSET_ONE_FAMILY:
+// every defined pair potential belongs to the family P.vdwFamily (VDW_LNJS .. VDW_LJ_NOCUT), <= 4 species, no radii, electrostatics none / direct / Fennell /
+// Ewald with alpha rReal <= 4 (Engine::construct decides) - {PM_TAB, PM_TAB_EWALD, PM_TAB_FENNELL} x that family.
+template <int V> using PairConst = std::integral_constant<int, V>;
+#define AZTOT_PAIR_DISPATCH(P, LAUNCH, ...)                                                                                                       \
+    do {                                                                                                                                          \
+        auto as = [&](auto mode, auto vdw) { LAUNCH<decltype(mode)::value, decltype(vdw)::value>(__VA_ARGS__); return true; };                    \
+        auto family = [&](auto vdw) {                                                                                                             \
+            if (P.vdwFamily != decltype(vdw)::value) return false;                                                                                \
+            if (P.elec_type == AZTOT_ELEC_EWALD) return as(PairConst<PM_TAB_EWALD>(), vdw);                                                       \
+            if (P.elec_type == AZTOT_ELEC_FENNEL) return as(PairConst<PM_TAB_FENNELL>(), vdw);                                                    \
+            return as(PairConst<PM_TAB>(), vdw);                                                                                                  \
+        };                                                                                                                                        \
+        auto families = [&](auto... vdw) { return (... || family(vdw)); };             /* (left fold: the first family is instantiated first) */                \
+        if (P.single_lj) as(PairConst<PM_ONE_LJ>(), PairConst<VDW_LNJS>());                                                                       \
+        else if (P.potSet == POTSET_ONE_SURK) as(PairConst<PM_ONE_SURK>(), PairConst<VDW_SURK>());                                                \
+        else if (!(P.potSet == POTSET_ONE_FAMILY && families(PairConst<VDW_LNJS>(), PairConst<VDW_BUCK>(), PairConst<VDW_P746>(), PairConst<VDW_BMHS>(),       \
+                                                             PairConst<VDW_MIXED>(), PairConst<VDW_LJ_NOCUT>())))                                 \
+            as(PairConst<PM_GENERIC>(), PairConst<VDW_ANY>());                                                                                    \
     } while (0)
 
-inline void launch_pair_tile(const StepParams& P, const SpecTable& S, const DevPot* pots, AtomArrays A, const Counts* cnt, const int32_t* cellStart,
-                             double* partials, int maxBlocks, hipStream_t stream, PairRange R = PairRange(), PairLists L = PairLists(), int listMode = 0,
-                             NextStep N = NextStep(), SplitArgs Z = SplitArgs())
+inline void launch_pair_tile(const PairLaunch& C, PairRange R = PairRange(), PairLists L = PairLists(), int listMode = 0, NextStep N = NextStep(), SplitArgs Z = SplitArgs())
 {
     if (!L.cand) listMode = 0;
-    AZTOT_PAIR_DISPATCH(launch_pair_tile_as, P, S, pots, A, cnt, cellStart, partials, maxBlocks, stream, R, L, listMode, N, Z);
+    AZTOT_PAIR_DISPATCH(C.P, launch_pair_tile_as, C, R, L, listMode, N, Z);
 }
 
 }  // namespace aztot

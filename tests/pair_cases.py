@@ -13,7 +13,7 @@ Per species pair the separations are log-spaced from just outside the radius whe
 before every cut-off, plus two pairs at f^2 = 1e10 (1 -+ 1e-6) (the drop rule of integrators.cpp:170) and the case's own edge points.
 Cut-off ties: axis-aligned pairs on dyadic coordinates with r^2 == rc^2 exactly and the nearest representable separations on either side.
 Cases with `filler` also carry a lattice of neutral atoms of a species without any potential: they add exactly nothing to any force, make the
-cells dense enough for the pair lists to overflow under debug bit 65536 (so cells go through the clean-up launch), and are the neutral species
+cells dense enough for the pair lists to overflow under DBG_SHORT_LISTS (so cells go through the clean-up launch), and are the neutral species
 among charged ones / the species pair without a potential.
 
 No mpmath here: the GPU test imports this module to rebuild the systems whose reference values tests/golden/pair_functions.npz holds.
@@ -55,7 +55,7 @@ def _spec(name):
             s["edges"] = {(0, 0): [1.5, 2.0, 2.5, 3.0]}                       # r < sigma: exp_nonpos with a positive argument
         if fam == "buck":
             s["edges"] = {(0, 0): [6.0, 6.9]}
-    elif name == "lnjs_fenn_vdw6":     # every pair LJ, cut-offs >= rReal: VDW 6 (cut-off test compiled out), and debug bit 1024 keeps it
+    elif name == "lnjs_fenn_vdw6":     # every pair LJ, cut-offs >= rReal: VDW_LJ_NOCUT (cut-off test compiled out), and DBG_KEEP_VDW_CUT_TEST keeps it
         s.update(species=[(39.9, 0.3), (20.2, -0.3)], vdw=[(a, b, 1, 7.5, [LJ[0], LJ[1]]) for a, b in _pairs(2)], elec=3, rReal=7.5, alpha=0.35, keepcut=True)
         s["ties"] = [(0, 0, 7.5)]
     elif name == "lnjs_fenn_4sp":      # the last uniform case
@@ -87,7 +87,7 @@ def _spec(name):
     elif name == "lj1":                # MODE 1: one species, LJ, no charges
         s.update(species=[(39.9, 0.0)], vdw=[(0, 0, 1, 6.5, list(LJ))])
         s["ties"] = [(0, 0, 6.5)]
-    elif name == "surk1":              # MODE 4 (and the generic body under debug bit 512): radii from the engine's state
+    elif name == "surk1":              # PM_ONE_SURK (and the generic body under DBG_GENERIC_PAIR): radii from the engine's state
         s.update(species=[(39.9, 0.0)], vdw=[(0, 0, 7, 6.0, [75.0, 8.0, 1.0, 1.0])], radii=[(2.73, 4.731, 0.2)])
         s["ties"] = [(0, 0, 6.0)]
     elif name.startswith(("fenn_ar", "ewald_ar")):     # alpha rReal = 3.99, 4.0 (fit, inclusive), 4.2 (libm erfc, generic fallback)

@@ -3,7 +3,7 @@ every kernel (main.cu:281-410, main.cpp:89-142), so whatever a caller does betwe
 the forces, restart the clock - the trajectory must be the one the every-step schedule produces.  Engines compared here:
 
   default     adaptive lazy re-sort, pair lists, no clean-up launch where the engine runs optimistically, end of a call deferred (Engine::settle)
-  eager       the same with every call settled on the spot (AZTOT_DEBUG bit 268435456) and the clean-up launch always in place (bit 4)
+  eager       the same with every call settled on the spot (DBG_SETTLE_EVERY_CALL) and the clean-up launch always in place (DBG_ALWAYS_CLEANUP)
   every-step  cells rebuilt on every step (`sort_every = 1`: the reference's schedule, main.cu:300-326)
 
 plus the windows-run-again stress of tools/stress_repair.py as a test (random systems, sort interval held above what the speeds allow).
@@ -12,13 +12,11 @@ import numpy as np
 import pytest
 
 from aztotmd_amd import api, inputs
+from aztotmd_amd.api import DebugBit
 from util import add_random_dynamics, rel_err
 
 pytestmark = pytest.mark.gpu
 KEYS = ("x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz", "U", "radius")
-SETTLE_EVERY_CALL = 268435456
-ALWAYS_CLEANUP = 4
-FIXED_INTERVAL = 8192
 
 
 def systems(name):
@@ -62,7 +60,7 @@ def test_random_call_patterns(name, seed):
     rng = np.random.default_rng(900 + seed)
     case = systems(name)
     engs = [api.Engine(api.Model.from_case(case)),
-            api.Engine(api.Model.from_case(case), debug=SETTLE_EVERY_CALL | ALWAYS_CLEANUP),
+            api.Engine(api.Model.from_case(case), debug=DebugBit.DBG_SETTLE_EVERY_CALL | DebugBit.DBG_ALWAYS_CLEANUP),
             api.Engine(api.Model.from_case(case), sort_every=1)]
     total = 0
     log = []
@@ -120,9 +118,9 @@ def test_deferred_end_of_call_is_bit_identical(name):
     (so that both engines rebuild at the same steps) a loop of single-step calls with nothing read in between must leave, bit for bit, the state of the
     engine that settles every call - and of one long call."""
     case = systems(name)
-    kw = dict(sort_every=8, debug=FIXED_INTERVAL | ALWAYS_CLEANUP)
+    kw = dict(sort_every=8, debug=DebugBit.DBG_FIXED_INTERVAL | DebugBit.DBG_ALWAYS_CLEANUP)
     a = api.Engine(api.Model.from_case(case), **kw)
-    b = api.Engine(api.Model.from_case(case), sort_every=8, debug=FIXED_INTERVAL | ALWAYS_CLEANUP | SETTLE_EVERY_CALL)
+    b = api.Engine(api.Model.from_case(case), sort_every=8, debug=DebugBit.DBG_FIXED_INTERVAL | DebugBit.DBG_ALWAYS_CLEANUP | DebugBit.DBG_SETTLE_EVERY_CALL)
     c = api.Engine(api.Model.from_case(case), **kw)
     a.step(8); b.step(8); c.step(8)                     # (the first call measures and records the first lists on all three)
     for _ in range(37):
@@ -154,7 +152,7 @@ def test_statistics_after_a_call_served_entirely_by_replayed_cycles(name):
     kernel; a following call made of whole replayed cycles (hipGraphs: no host code per step) then summed those stale slots into the statistics. A graph slot
     now carries the host's notes of its last step (Engine::LaunchNotes)."""
     case = systems(name)
-    a = api.Engine(api.Model.from_case(case), sort_every=8, debug=FIXED_INTERVAL)
+    a = api.Engine(api.Model.from_case(case), sort_every=8, debug=DebugBit.DBG_FIXED_INTERVAL)
     b = api.Engine(api.Model.from_case(case), sort_every=1)
     for e in (a, b):
         e.step(8)
@@ -189,8 +187,8 @@ def stress_case(seed):
 
 def run_stress(seed):
     case, calls = stress_case(seed)
-    a = api.Engine(api.Model.from_case(case), sort_every=16, debug=FIXED_INTERVAL)                     # no clean-up launch: violations repaired from snapshots
-    b = api.Engine(api.Model.from_case(case), sort_every=16, debug=FIXED_INTERVAL | ALWAYS_CLEANUP)    # the launch behind every step
+    a = api.Engine(api.Model.from_case(case), sort_every=16, debug=DebugBit.DBG_FIXED_INTERVAL)                     # no clean-up launch: violations repaired from snapshots
+    b = api.Engine(api.Model.from_case(case), sort_every=16, debug=DebugBit.DBG_FIXED_INTERVAL | DebugBit.DBG_ALWAYS_CLEANUP)    # the launch behind every step
     c = api.Engine(api.Model.from_case(case), sort_every=1)
     for n in calls:
         a.step(n); b.step(n); c.step(n)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from aztotmd_amd import api, inputs
+from aztotmd_amd.api import DebugBit
 from oracle import oracle, parse
 from util import FRC, VEL, case_from_parsed, materialise_case_study, per_atom_err, rel_err
 
@@ -65,8 +66,8 @@ def test_full_size_steps_match_the_serial_cpu_path(name):
     n = len(case["types"])
     assert n == 1000188
     ref, eref, who = cpu_steps(case, 3)
-    # the reference's schedule: cells rebuilt every step; debug bit 8388608: hipGraph replay although the engine would launch a system of this size eagerly
-    e = api.Engine(api.Model.from_case(case), initial_forces=0, sort_every=1, debug=8388608)
+    # the reference's schedule: cells rebuilt every step; DBG_GRAPH_ALWAYS: hipGraph replay although the engine would launch a system of this size eagerly
+    e = api.Engine(api.Model.from_case(case), initial_forces=0, sort_every=1, debug=DebugBit.DBG_GRAPH_ALWAYS)
     e.step(3)
     s, st = e.state(), e.stats()
     assert st["n_cells"] == 42 ** 3 and st["n_cells"] > 16384           # the multi-workgroup scan is the one that ran
@@ -83,8 +84,8 @@ def test_full_size_steps_match_the_serial_cpu_path(name):
     for k in ("fx", "fy", "fz"):
         assert abs(s[k].sum()) < 1e-8                                    # Newton 3 over 1 M atoms
     check_cell_table(e, s, case["box"])
-    # the deferred half-kick path must give the same trajectory as k_integrate2 every step (debug bit 128), bit for bit
-    e2 = api.Engine(api.Model.from_case(case), initial_forces=0, debug=128, use_graph=0, sort_every=1)
+    # the deferred half-kick path must give the same trajectory as k_integrate2 every step (DBG_KICK_EVERY_STEP), bit for bit
+    e2 = api.Engine(api.Model.from_case(case), initial_forces=0, debug=DebugBit.DBG_KICK_EVERY_STEP, use_graph=0, sort_every=1)
     e2.step(3)
     s2 = e2.state()
     for k in XVF:
@@ -121,11 +122,11 @@ def test_lazy_resort_at_full_size(name):
 
 
 def test_slack_violation_at_full_size():
-    """1 000 188 atoms at 3 000 K with the interval held at 16 steps (debug bit 8192) although the atoms use up the 0.05 A slack in two or three: atoms
+    """1 000 188 atoms at 3 000 K with the interval held at 16 steps (DBG_FIXED_INTERVAL) although the atoms use up the 0.05 A slack in two or three: atoms
     DO leave the slack between two rebuilds, the list kernel stands down, and the clean-up launch (one residency's worth of workgroups striding over all
     74 088 cells) stages every cell with the wider stencil.  Same trajectory as the every-step schedule, summation order aside."""
     case = inputs.lj_case((63, 63, 63), seed=20240502, vel_T=3000.0)
-    a = api.Engine(api.Model.from_case(case), sort_every=16, debug=8192)
+    a = api.Engine(api.Model.from_case(case), sort_every=16, debug=DebugBit.DBG_FIXED_INTERVAL)
     b = api.Engine(api.Model.from_case(case), sort_every=1)
     for n in (10, 22, 5):
         a.step(n); b.step(n)

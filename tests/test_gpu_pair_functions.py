@@ -8,10 +8,11 @@ that serves it, and the test asserts from the kernel timers that the path really
   atom     pair_variant=1                                  (k_pair_atom, generic pair_visit)
   tile     pair_variant=2, aztot_forces                   (k_pair_tile, pair_body<MODE, VDW>)
   list     pair_variant=2 after step(k), lists in force   (k_pair_list, pair_body<MODE, VDW, MASKED>)
-  generic  debug bit 512                                  (k_pair_tile with the generic pair_visit; not for one-species LJ, whose MODE 1 kernel
+  generic  DBG_GENERIC_PAIR                                (k_pair_tile with the generic pair_visit; not for one-species LJ, whose PM_ONE_LJ kernel
                                                            the bit does not switch off, so there it would repeat the tile path)
-  keepcut  debug bit 1024 where VDW 6 applies             (Lennard-Jones with the per-pair cut-off test kept)
-  short    debug bits 65536 + 4 (cases with filler atoms) (k_pair_list + k_pair_tile<CLEANUP> for the cells whose list overflowed)
+  keepcut  DBG_KEEP_VDW_CUT_TEST where VDW_LJ_NOCUT applies (Lennard-Jones with the per-pair cut-off test kept)
+  short    DBG_SHORT_LISTS + DBG_ALWAYS_CLEANUP            (cases with filler atoms: k_pair_list + k_pair_tile<CLEANUP> for the cells whose list
+                                                           overflowed; DBG_ALWAYS_CLEANUP: the clean-up launch runs on every list step)
 The kernel timers name the launch, not the specialisation inside it: which MODE / VDW body runs follows from the case (pair_cases.py) and the
 debug bits above.
 """
@@ -22,6 +23,7 @@ import pytest
 
 import pair_cases as pc
 from aztotmd_amd import api
+from aztotmd_amd.api import DebugBit
 
 pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pair_functions.npz")
@@ -68,10 +70,10 @@ def paths(name):
 def run_path(case, path):
     """(engine, state, stats, kernel names) of the evaluation whose forces state() returns; stats()["pairs_dropped"] counts that evaluation's drops"""
     kw = dict(pair_variant=1 if path == "atom" else 2, profile=1)
-    kw["debug"] = {"generic": 512, "keepcut": 1024, "short": 65536 | 4}.get(path, 0)     # (4: the clean-up launch runs on every list step)
-    if path in ("list", "short"):             # frozen atoms give the adaptive interval nothing to measure: re-sort every 32 steps (debug bit 8192)
+    kw["debug"] = {"generic": DebugBit.DBG_GENERIC_PAIR, "keepcut": DebugBit.DBG_KEEP_VDW_CUT_TEST, "short": DebugBit.DBG_SHORT_LISTS | DebugBit.DBG_ALWAYS_CLEANUP}.get(path, 0)
+    if path in ("list", "short"):             # frozen atoms give the adaptive interval nothing to measure: re-sort every 32 steps (DBG_FIXED_INTERVAL)
         kw.update(sort_every=32)
-        kw["debug"] |= 8192
+        kw["debug"] |= DebugBit.DBG_FIXED_INTERVAL
     e = api.Engine(api.Model.from_case(case), **kw)
     if path in ("list", "short"):
         e.step(12)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from aztotmd_amd import api, inputs
+from aztotmd_amd.api import DebugBit
 from oracle import oracle
 from util import FRC, VEL, add_random_dynamics, family_with_coulomb, mixed_case, per_atom_err, random_case, reference_dumps, rel_err
 
@@ -403,7 +404,7 @@ def test_surk_radius_potential_with_thermostat():
 
 @pytest.mark.parametrize("cell", [2.7, 6.0])
 def test_surk_tile_mode_equals_generic_kernel_and_oracle(cell):
-    """the specialised one-species surk + radii tile mode (case study 2 / BASELINE config 5) against the generic kernel (debug bit 512),
+    """the specialised one-species surk + radii tile mode (case study 2 / BASELINE config 5) against the generic kernel (DBG_GENERIC_PAIR),
     the per-atom kernel and the oracle: forces 1e-11, 20 thermostatted steps 1e-9; on the case study's 2.7 A cells (7^3 stencil) and on
     cut-off sized cells"""
     pos, box = inputs.fcc_positions((7, 7, 8), 2.9, 0.12, 9)
@@ -415,7 +416,7 @@ def test_surk_tile_mode_equals_generic_kernel_and_oracle(cell):
     o = oracle.Oracle(case)
     o.forces(0)
     so, sto = o.state(), o.stats()
-    engines = [engine(case), engine(case, debug=512), engine(case, pair_variant=1)]
+    engines = [engine(case), engine(case, debug=DebugBit.DBG_GENERIC_PAIR), engine(case, pair_variant=1)]
     for e in engines:
         s, st = e.state(), e.stats()
         for k in FKEYS:
@@ -478,11 +479,11 @@ def test_bitwise_reproducible_and_graph_equals_eager():
 @pytest.mark.parametrize("variant", [1, 2])
 def test_second_half_kick_ownership(variant):
     """On plain NVE steps integrate2's work is done by the tile kernel's epilogue (small systems), by the next step's
-    k_integrate1_bin (large systems; debug bit 256 forces that path here) or by k_integrate2 itself (debug bit 128): the three must
+    k_integrate1_bin (large systems; DBG_LARGE_KICK_PATH forces that path here) or by k_integrate2 itself (DBG_KICK_EVERY_STEP): the three must
     agree bit for bit in x, v, f and in the energies, across graph replays (10 + 20 steps), odd step counts and repeated calls."""
     case = inputs.lj_case((6, 6, 6), a=5.3, seed=17, rc=7.0, cell_list=7.0, vel_T=150.0)
     ref = None
-    for dbg in (128, 256, 0):
+    for dbg in (DebugBit.DBG_KICK_EVERY_STEP, DebugBit.DBG_LARGE_KICK_PATH, 0):
         e = engine(case, debug=dbg, pair_variant=variant)
         kin = []
         for n in (10, 20, 7, 1):
@@ -505,12 +506,12 @@ def test_second_half_kick_ownership(variant):
 @pytest.mark.parametrize("mode", ["adaptive", "forced"])
 def test_lazy_resort_is_exact(mode, variant):
     """lazy re-sort against the every-step schedule and the oracle on a hot liquid (3 000 K: atoms cross walls and change cells all the time).
-    'adaptive': the default - the interval follows the largest step seen.  'forced': debug bit 8192 holds the interval at 32 steps although the atoms
+    'adaptive': the default - the interval follows the largest step seen.  'forced': DBG_FIXED_INTERVAL holds the interval at 32 steps although the atoms
     are far too fast for it, so atoms DO leave their cell's slack between sorts and the pair kernels fall back to the wider stencil - the result must
     not change.  60 steps in five calls; x / v / f 1e-9 against the oracle, wall counters and per-species crossings equal."""
     case = inputs.lj_case((7, 7, 7), a=5.4, seed=23, rc=6.5, cell_list=6.9, vel_T=3000.0 if mode == "adaptive" else 9000.0)
     case["dt"] = 0.001 if mode == "adaptive" else 0.002           # 'forced': up to 0.05 A per step against a slack of 0.08 A, held for 32 steps
-    kw = dict(sort_every=32, debug=8192) if mode == "forced" else {}
+    kw = dict(sort_every=32, debug=DebugBit.DBG_FIXED_INTERVAL) if mode == "forced" else {}
     a = engine(case, pair_variant=variant, **kw)
     b = engine(case, pair_variant=variant, sort_every=1)
     o = oracle.Oracle(case)
@@ -540,7 +541,7 @@ def test_lazy_resort_is_exact(mode, variant):
 @pytest.mark.parametrize("kind", ["lj", "lj_fennell", "buck", "elin", "part_unlisted", "dense_cells"])
 def test_pair_lists_between_two_rebuilds(kind):
     """The steps between two rebuilds of the cell list walk the pair lists the rebuild recorded (k_pair_tile<BUILD> -> k_pair_list) instead of staging and
-    filtering every cell again: same forces as the every-step schedule (summation order aside) and as the oracle.  'part_unlisted': debug bit 65536
+    filtering every cell again: same forces as the every-step schedule (summation order aside) and as the oracle.  'part_unlisted': DBG_SHORT_LISTS
     caps the lists at 14 iterations, so part of the cells keep no list and go through the clean-up launch of the staging kernel while the others
     walk their lists; 'dense_cells': cells of 3 rc hold ~108 atoms (> 64: no cell keeps a list, everything goes through the clean-up launch until the
     engine notices and stops recording)."""
@@ -548,7 +549,7 @@ def test_pair_lists_between_two_rebuilds(kind):
     if kind in ("lj", "part_unlisted"):
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=31, rc=7.5, cell_list=7.9, vel_T=120.0)
         if kind == "part_unlisted":
-            kw = dict(debug=65536)
+            kw = dict(debug=DebugBit.DBG_SHORT_LISTS)
     elif kind == "lj_fennell":
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=32, rc=7.5, cell_list=7.9, vel_T=120.0, charges=(0.3, -0.3), elec="fenn", r_real=7.5, alpha=0.3)
     elif kind in ("buck", "elin"):           # one potential family in the LDS table / the generic switch-based body
@@ -583,24 +584,24 @@ def test_pair_lists_between_two_rebuilds(kind):
 def test_next_step_fused_into_the_pair_kernel(kind):
     """On plain NVE steps of a lazy run that walks pair lists the pair kernel's epilogue also opens the next step (deferred second half-kick, first half-kick,
     drift, wall counters, displacement check: everything k_integrate1_bin<2> does), writing the new positions to a second set of coordinate arrays.  Same
-    operations in the same order: positions, velocities and forces must be BIT-IDENTICAL to a run with the fusion switched off (debug bit 131072), whatever
+    operations in the same order: positions, velocities and forces must be BIT-IDENTICAL to a run with the fusion switched off (DBG_NO_FUSE_NEXT), whatever
     the pattern of calls (graph replay of whole cycles, eager remainders, single steps); wall counters equal, wall momenta to summation order.  'hot': a
-    9 000 K gas held at a 32-step interval (debug bit 8192) - atoms leave the slack, the violation is flagged one step ahead by the epilogue and the
+    9 000 K gas held at a 32-step interval (DBG_FIXED_INTERVAL) - atoms leave the slack, the violation is flagged one step ahead by the epilogue and the
     clean-up launch (which carries the same epilogue) takes over."""
     kw = {}
     if kind in ("lj", "part_unlisted"):
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=41, rc=7.5, cell_list=7.9, vel_T=300.0)
         if kind == "part_unlisted":
-            kw = dict(debug=65536)
+            kw = dict(debug=DebugBit.DBG_SHORT_LISTS)
     elif kind == "lj_fennell":
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=42, rc=7.5, cell_list=7.9, vel_T=300.0, charges=(0.3, -0.3), elec="fenn", r_real=7.5, alpha=0.3)
     else:
         case = inputs.lj_case((7, 7, 7), a=5.4, seed=23, rc=6.5, cell_list=6.9, vel_T=9000.0)
         case["dt"] = 0.002
-        kw = dict(sort_every=32, debug=8192)
+        kw = dict(sort_every=32, debug=DebugBit.DBG_FIXED_INTERVAL)
     a = engine(case, pair_variant=2, **kw)
     kb = dict(kw)
-    kb["debug"] = kb.get("debug", 0) | 131072
+    kb["debug"] = kb.get("debug", 0) | DebugBit.DBG_NO_FUSE_NEXT
     b = engine(case, pair_variant=2, **kb)
     o = oracle.Oracle(case)
     o.forces(1)
@@ -626,7 +627,7 @@ def test_next_step_fused_into_the_pair_kernel(kind):
 def test_pair_energies_only_where_somebody_can_see_them(kind):
     """The statistics of an aztot_step call are those of its last step (the reference prints energies every `stat` steps, cuStat.cu:308-330), so the
     list kernel of every other step of the call books no pair energies (k_pair_list<.., ENG = false>).  Nothing observable may change: positions,
-    velocities and forces BIT-IDENTICAL to a run whose every step books them (debug bit 134217728), and the energies after every call equal to the last
+    velocities and forces BIT-IDENTICAL to a run whose every step books them (DBG_ENERGIES_EVERY_STEP), and the energies after every call equal to the last
     bit (the last step runs the same instantiation in both), whatever the pattern of calls; both agree with the oracle."""
     if kind == "lj":
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=61, rc=7.5, cell_list=7.9, vel_T=200.0)
@@ -643,7 +644,7 @@ def test_pair_energies_only_where_somebody_can_see_them(kind):
                 "cell_list": 6.5, "use_clist": 1, "elec_type": 0}
     pv = {} if kind == "surk" else dict(pair_variant=2)
     a = engine(case, **pv)
-    b = engine(case, debug=134217728, **pv)
+    b = engine(case, debug=DebugBit.DBG_ENERGIES_EVERY_STEP, **pv)
     o = oracle.Oracle(case)
     o.forces(1)
     for n in (10, 1, 37, 2, 33, 5):
@@ -706,14 +707,14 @@ def test_sort_interval_runs_on_across_calls():
 def test_kick_and_radiative_thermostat_in_one_launch():
     """Radiative thermostat without equilibration scaling: k_integrate2 and k_post run as ONE launch (nothing global happens between the second half-kick and
     the thermostat), and when a plain step follows, the same launch opens it (k_boundary_radi: first half-kick, drift, wall counters, displacement check).
-    Same operations in the same order: bit-identical to the two-launch form (debug bit 4194304) and to the form without the boundary kernel (33554432),
+    Same operations in the same order: bit-identical to the two-launch form (DBG_KICK_POST_SPLIT) and to the form without the boundary kernel (DBG_NO_BOUNDARY_RADI),
     per-atom internal energies and radii included, and equal to the oracle."""
     case = inputs.lj_case((8, 8, 8), a=5.6, seed=61, rc=7.5, cell_list=7.9, vel_T=60.0, T=60.0, tstat="radi", radii=[(2.73, 4.731, 0.2)])       # 5 cells per axis: the lazy re-sort engages
-    # (debug bit 131072: without the pair kernel's fused epilogue, which since round 3 closes and opens such steps itself where no clean-up launch follows -
+    # (DBG_NO_FUSE_NEXT: without the pair kernel's fused epilogue, which since round 3 closes and opens such steps itself where no clean-up launch follows -
     #  test_radiative_thermostat_fused_into_the_pair_kernel; this test is about the boundary kernel that serves everywhere else)
-    a = engine(case, pair_variant=2, debug=131072)
-    b = engine(case, pair_variant=2, debug=4194304 | 131072)
-    c = engine(case, pair_variant=2, debug=33554432 | 131072)      # one launch for kick + thermostat, but no k_boundary_radi (which also opens the next plain step)
+    a = engine(case, pair_variant=2, debug=DebugBit.DBG_NO_FUSE_NEXT)
+    b = engine(case, pair_variant=2, debug=DebugBit.DBG_KICK_POST_SPLIT | DebugBit.DBG_NO_FUSE_NEXT)
+    c = engine(case, pair_variant=2, debug=DebugBit.DBG_NO_BOUNDARY_RADI | DebugBit.DBG_NO_FUSE_NEXT)      # one launch for kick + thermostat, but no k_boundary_radi (which also opens the next plain step)
     o = oracle.Oracle(case)
     o.forces(1)
     for n in (3, 20, 1, 16, 37):
@@ -737,14 +738,14 @@ def test_kick_and_radiative_thermostat_in_one_launch():
 def test_pair_lists_with_thermostat_radii(generic):
     """Pair lists where the potential depends on per-atom radii the radiative thermostat rewrites every step ('surk', case study 2 style, on cut-off sized
     cells so that a tile holds the stencil): the list kernel gathers the radii afresh with the coordinates.  Specialised surk mode and the generic
-    switch-based body (debug bit 512) against the every-step schedule and the oracle."""
+    switch-based body (DBG_GENERIC_PAIR) against the every-step schedule and the oracle."""
     pos, box = inputs.fcc_positions((7, 7, 7), 5.8, 0.1, 15)
     N = len(pos)
     case = {"box": box.tolist(), "dt": 0.001, "species": [(39.9, 0.0)], "names": ["Ar"], "types": np.zeros(N, dtype=np.int32),
             "vdw": [(0, 0, 7, 6.0, [75.0, 8.0, 1.0, 1.0])], "radii": [(2.73, 4.731, 0.2)], "x": pos[:, 0].copy(), "y": pos[:, 1].copy(),
             "z": pos[:, 2].copy(), "vx": np.zeros(N), "vy": np.zeros(N), "vz": np.zeros(N), "T": 300.0, "tstat_type": 2,
             "cell_list": 6.5, "use_clist": 1, "elec_type": 0}
-    dbg = 512 if generic else 0
+    dbg = DebugBit.DBG_GENERIC_PAIR if generic else 0
     a = engine(case, debug=dbg)
     b = engine(case, debug=dbg, sort_every=1)
     o = oracle.Oracle(case)
@@ -1069,9 +1070,9 @@ def test_pressure_from_wall_momentum():
 @pytest.mark.parametrize("kind", ["lj", "radi", "fennell"])
 def test_window_run_again_without_the_cleanup_launch_is_exact(kind):
     """Small systems on one GPU run their plain steps WITHOUT the clean-up launch behind k_pair_list (Engine::choose_optimism); a look that finds a skin violation
-    (or a cell that kept no list) goes back to the snapshot the last clean look left and runs the window again with the launch in place.  Debug bit 8192 holds the
+    (or a cell that kept no list) goes back to the snapshot the last clean look left and runs the window again with the launch in place.  DBG_FIXED_INTERVAL holds the
     interval at 32 steps on atoms far too fast for it, so windows ARE run again - and the result must be what an engine that launches the clean-up kernel behind
-    every step (debug bit 4) arrives at: the same trajectory (positions, velocities, forces, the radiative thermostat's per-atom energy and radius), the same
+    every step (DBG_ALWAYS_CLEANUP) arrives at: the same trajectory (positions, velocities, forces, the radiative thermostat's per-atom energy and radius), the same
     energies, wall counters and per-species crossings, to summation order (the repaired steps are the same kernels in both engines); and both equal the
     every-step schedule to 1e-9.  'radi': the snapshot has to carry the thermostat's state and the step number its random numbers are keyed by."""
     if kind == "radi":
@@ -1081,8 +1082,8 @@ def test_window_run_again_without_the_cleanup_launch_is_exact(kind):
     else:
         case = inputs.lj_case((7, 7, 7), a=5.4, seed=23, rc=6.5, cell_list=6.9, vel_T=9000.0)
     case["dt"] = 0.002
-    a = engine(case, sort_every=32, debug=8192)
-    b = engine(case, sort_every=32, debug=8192 | 4)
+    a = engine(case, sort_every=32, debug=DebugBit.DBG_FIXED_INTERVAL)
+    b = engine(case, sort_every=32, debug=DebugBit.DBG_FIXED_INTERVAL | DebugBit.DBG_ALWAYS_CLEANUP)
     c = engine(case, sort_every=1)
     for n in (3, 40, 9, 70, 33):               # (an engine's first two looks are spent with the launch in place: the later calls are the ones that run without it)
         a.step(n); b.step(n); c.step(n)
@@ -1106,7 +1107,7 @@ def test_radiative_thermostat_fused_into_the_pair_kernel(kind):
     """Runs with the radiative thermostat whose pair kernel reads no radii (case study 1): on plain steps of a lazy run without a clean-up launch the epilogue of
     k_pair_list closes the step as k_integrate2_post does (second half-kick, then the thermostat on the fully kicked velocity, random draws keyed by the number of
     the step being closed) and opens the next one - one launch per step instead of two.  Same operations in the same order: positions, velocities, forces and
-    the thermostat's per-atom energy and radius must be BIT-IDENTICAL to a run with the fusion switched off (debug bit 131072), whatever the pattern of calls;
+    the thermostat's per-atom energy and radius must be BIT-IDENTICAL to a run with the fusion switched off (DBG_NO_FUSE_NEXT), whatever the pattern of calls;
     energies equal to summation order, and both equal to the oracle.  'equil': an equilibration schedule - the steps it acts on (and their neighbours) take
     the unfused path."""
     if kind == "gas":        # the dilute gas of case study 1 in small: cells of 20 atoms' worth of empty space
@@ -1125,7 +1126,7 @@ def test_radiative_thermostat_fused_into_the_pair_kernel(kind):
         case = inputs.lj_case((8, 8, 8), a=5.6, seed=44, rc=7.5, cell_list=7.9, T=250.0, tstat="radi", vel_T=200.0, radii=[(2.73, 4.731, 0.2)],
                               nEq=60 if kind == "equil" else 0, freqEq=7)
     a = engine(case, pair_variant=2)
-    b = engine(case, pair_variant=2, debug=131072)
+    b = engine(case, pair_variant=2, debug=DebugBit.DBG_NO_FUSE_NEXT)
     o = oracle.Oracle(case)
     o.forces(1)
     for n in (10, 1, 37, 2, 33, 64, 5):

@@ -7,6 +7,8 @@ import sys
 
 import pytest
 
+from aztotmd_amd.api import DebugBit
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -88,12 +90,12 @@ def test_slabs_survive_a_heating_step_between_two_calls():
 
 @pytest.mark.parametrize("name,nranks,nsteps,port", [("hot", 2, 70, 29626), ("hot", 3, 45, 29627), ("thermo", 2, 40, 29628)])
 def test_slab_ranks_repair_a_skin_violation_by_running_the_window_again(name, nranks, nsteps, port):
-    """A slab rank holds hw ghost layers, so it cannot fall back on a wider stencil when an atom leaves its cell's slack between two sorts.  Debug bit 8192
+    """A slab rank holds hw ghost layers, so it cannot fall back on a wider stencil when an atom leaves its cell's slack between two sorts.  DBG_FIXED_INTERVAL
     holds the interval at 32 steps on atoms far too fast for it: the look that finds the violation takes every rank back to the snapshot the last clean look
     left (per-atom arrays, DevStats, Counts, partial sums - device to device) and runs the steps since again with the cells rebuilt every step.  The result
     must equal the single-rank engine's (which repairs its own violations with the wider stencil): x / v / f 1e-9, energies, wall counters, and - 'thermo' -
     the radiative thermostat's per-atom state and random numbers."""
-    out = run_ranks(nranks, name, nsteps, extra={"sort_every": 32, "debug": 8192}, port=port)
+    out = run_ranks(nranks, name, nsteps, extra={"sort_every": 32, "debug": DebugBit.DBG_FIXED_INTERVAL}, port=port)
     assert out["every_atom_owned_once"] and out["owned_total"] == out["n_atoms"]
     assert out["max_rel_err_vs_single"] < 1e-9, out["errs"]
     assert all(v < 1e-10 for v in out["energy_rel"].values()), out["energy_rel"]
@@ -121,9 +123,9 @@ def test_slab_ranks_grow_their_lists_together():
 
 
 def test_slabs_with_deferred_half_kick():
-    """debug bit 256: the large-system path (second half-kick applied by the next step's k_integrate1_bin, which in slab mode also
+    """DBG_LARGE_KICK_PATH: the large-system path (second half-kick applied by the next step's k_integrate1_bin, which in slab mode also
     packs the migrants and the halo from the freshly kicked velocities)."""
-    out = run_ranks(2, "lj", 25, extra={"debug": 256}, port=29620)
+    out = run_ranks(2, "lj", 25, extra={"debug": DebugBit.DBG_LARGE_KICK_PATH}, port=29620)
     assert out["every_atom_owned_once"] and out["max_rel_err_vs_single"] < 1e-9, out["errs"]
     assert all(v < 1e-10 for v in out["energy_rel"].values()), out["energy_rel"]
 
@@ -175,14 +177,14 @@ def test_slabs_over_rccl(nranks, name, nsteps):
 
 
 def test_overlapped_coordinate_exchange_changes_nothing():
-    """opt-in (debug bit 16384): plain steps of a slab rank run the coordinate exchange on a second stream beside the interior cells' pair
+    """opt-in (DBG_OVERLAP_HALO): plain steps of a slab rank run the coordinate exchange on a second stream beside the interior cells' pair
     forces and launch the boundary cells afterwards (three launches instead of one).  One rank of 2 talking to itself (loopback transport: the
     only device-side transport a one-GPU box has) with and without the overlap: per-atom state bit for bit, energies to round-off."""
     from aztotmd_amd import api, inputs
     import numpy as np
     case = inputs.lj_case((42, 5, 5), a=5.735, seed=31, rc=8.5, vel_T=8.0)            # 28 cell layers along x: 14 owned layers per rank, 10 of them interior
     res = []
-    for dbg in (0, 16384):
+    for dbg in (0, DebugBit.DBG_OVERLAP_HALO):
         e = api.Engine(api.Model.from_case(case), slab={"rank": 1, "nranks": 2, "loopback": True}, debug=dbg)   # 14 layers = 21 lattice cells: the loopback seam matches the lattice
         for n in (6, 30, 30):
             e.step(n)
