@@ -6,13 +6,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "device_md.h"
+#include "device_resources.h"
+#include "list_store.h"
 #include "model.h"
 #include "msg_layout.h"
 
@@ -27,67 +28,62 @@ struct ArgError : std::runtime_error
     using std::runtime_error::runtime_error;
 };
 
-struct KernelTimer
-{
-    std::string name;
-    double ms = 0.0;
-    long long calls = 0;
-};
-
 }  // namespace aztot
 #include "exchange.h"
 namespace aztot {
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
-// The host state machine in one table.  "Forget" = the three assignments `sinceSort_ = 1 << 30; listsValid_ = false;
-// carryAgreed_ = false` that make the next step rebuild the cells.  API calls that touch state first complete a deferred call end (Engine::settle).
+// The host state machine in one table, grouped as the members are below.  API calls that touch state first complete a
+// deferred call end (Engine::settle).  Transitions with a name: forget_interval() (the next step rebuilds the cells), void_measurement() (looks start
+// over at 8 steps), set_interval(K), drop_graphs() (captured cycles are stale).  Memory, pinned blocks and the pair-list store say what they own in
+// device_resources.h / list_store.h.
 //
 //  member            meaning                                              set by                                      cleared / reset by                         invalidated by (API)
 //  ----------------  ---------------------------------------------------  ------------------------------------------  -----------------------------------------  ---------------------------------------
 //  unsettled_        the last aztot_step returned before its end           step_body (every call)                      settle (at once when settle_now(), else     every read / write entry point settles
 //                    (deferred kick, statistics, look) had happened                                                    by the next reader or the next due look)    first; mark_failed drops it
-//  failed_           first error of a step / settle: no more stepping      mark_failed                                 never (the handle is dead for stepping)    -
 //  hostStep_         steps launched so far (== DevStats::step when the     launch_step_kernels (+1), run_steps (graph  replay_from_snapshot (snapshot's),          aztot_set_clock; mark_failed re-reads it
 //                    stream has drained)                                   replay: + cycle)                            set_clock                                  from the device
-//  lazyK_            sort interval in force (1: every step)                adapt_sort_interval (from the longest step  -> 1: set_state with new v / f, a slab      aztot_set_state (v, f); aztot_forces keeps it
-//                                                                          seen), constructor (debug: fixed)           violation (replay), never above lazyCap_
-//  lazyMeasured_     lazyK_ comes from a measurement                       adapt_sort_interval                         set_state (v, f), slab violation            aztot_set_state (v, f)
-//  lazyWindow_       steps between two looks: 8, 16 ... 256 (64 on slabs)  step_body / settle (doubling)               -> 8: set_state (v, f), slab violation      aztot_set_state (v, f)
-//  sinceLook_        steps since the last look (runs on across calls)      step_body (+ n)                             every look (-> 0); set_state (v, f)         aztot_set_state (v, f)
-//  lazyMargin_       K steps of the longest step may use slack / margin    adapt_sort_interval (x 4/3 per violation)   never shrinks                               -
-//  sinceSort_        plain steps since the last rebuild (1 << 30: none)    sort_and_forces (0 at a rebuild, +1 plain)  Forget                                      aztot_forces, aztot_set_state, aztot_set_clock,
-//                                                                                                                                                                  replay, list re-allocation, run_steps without carryOn
-//  listsValid_       the lists on the device are those of the arrays as    launch_pair (build), prepare_next_call      Forget; sort_and_forces until launch_pair   as sinceSort_
-//                    they stand (a call may open with plain steps)                                                     has recorded the new ones; free_lists
-//  listsOn_          lists exist and plain steps walk them                 allocate_lists                              free_lists; adapt_sort_interval when most   -
-//                                                                                                                      unlisted cells can never be listed
-//  candLds_/iterLds_ LDS sizes of k_pair_list / k_build_lists              allocate_lists (= capacities)               adapt_sort_interval, prepare_next_call      - (baked into graphs: destroy_graphs)
-//                                                                                                                      (tightened to the largest cell recorded)
+// -- pair lists ---
+//  lists_            the store (list_store.h); lists_.on, the LDS sizes    ListStore::create / regrow / adapt,         ListStore::release, adapt (most unlisted    - (baked into graphs: drop_graphs)
+//                    and waves per cell are launch parameters              tighten                                     cells can never be listed)
+//  listsValid_       the lists on the device are those of the arrays as    launch_pair (build), prepare_next_call      forget_interval; sort_and_forces until      as sinceSort_
+//                    they stand (a call may open with plain steps)                                                     launch_pair has recorded the new ones
 //  unlistedState_    cells without a list in the lists in force: 0 ?,      launch_pair (slab: read back behind the     launch_pair at every build (-> 0), replay    -
 //                    1 none, 2 some                                        build), prepare_next_call
 //  unlistedAtLook_   the last look found cells recorded without a list     adapt_sort_interval                         the next look that saw a recording          -
-//  carryAgreed_      slab ranks: all agreed the next call may open with    prepare_next_call (all-reduce)              Forget                                      as sinceSort_
+// -- sort interval ---
+//  lazyK_            sort interval in force (1: every step)                set_interval: adapt_sort_interval (from the -> 1: set_state with new v / f, a slab      aztot_set_state (v, f); aztot_forces keeps it
+//                                                                          longest step seen); constructor (debug)     violation (replay), never above lazyCap_
+//  lazyMeasured_     lazyK_ comes from a measurement                       adapt_sort_interval                         void_measurement: set_state (v, f), slab    aztot_set_state (v, f)
+//                                                                                                                      violation
+//  lazyWindow_       steps between two looks: 8, 16 ... 256 (64 on slabs)  look (doubling)                             -> 8: void_measurement                      aztot_set_state (v, f)
+//  sinceLook_        steps since the last look (runs on across calls)      step_body (+ n)                             every look (-> 0); void_measurement         aztot_set_state (v, f)
+//  sinceSort_        plain steps since the last rebuild (kNoSort: none)    sort_and_forces (0 at a rebuild, +1 plain)  forget_interval                             aztot_forces, aztot_set_state, aztot_set_clock,
+//                                                                                                                                                                  replay, list re-allocation, run_steps without carryOn
+//  carryAgreed_      slab ranks: all agreed the next call may open with    prepare_next_call (all-reduce)              forget_interval                             as sinceSort_
 //                    plain steps
+//  haloInfoPending_  slab: the boundary ranges of the last sort are still  sort_and_forces                             take_halo_info, prepare_next_call, replay   -
+//                    on their way to pinned memory
+// -- graphs ---
+//  graphs_, graphCycle_  captured cycles, valid for one buffer state and   graph_for_state                             drop_graphs: any change of lazyK_,          aztot_set_clock, aztot_set_state (U / radius
+//                    one set of launch parameters                                                                       optimistic_, the list store's launch        first touched), replay
+//                                                                                                                      parameters, thermoTouched_
+// -- snapshot and optimism ---
 //  optimistic_       plain steps run without the clean-up launch           choose_optimism (start of a settled call,   choose_optimism; replay_from_snapshot       - (P_.optimistic is baked into graphs)
 //                    (P_.optimistic)                                       after every look)
 //  safeLooks_        looks still to spend with the clean-up launch         constructor (1), replay (4 << rollbacks_)   every look (- 1)                            -
 //  snap_.valid       a verified snapshot of the dynamic state exists       take_snapshot (start of a settled call,     choose_optimism (not optimistic any more),  aztot_forces, aztot_set_state, aztot_set_clock,
 //                                                                          every clean look; kept when younger than    settle (no roll-back mode)                  mark_failed
 //                                                                          kSnapshotKeepSteps)
-//  stepsSinceSnap_   steps launched since the snapshot                     step_body (+ n), replay (= n)               take_snapshot (-> 0)                        -
+// -- per-launch scratch ---
 //  kickOwed_         the last step's second half-kick has not been         step_body (= lazyKick_ at the end of a      finish_steps (k_integrate2); start of the   -
-//                    applied and settle must apply it                      call), replay                               next step_body (the device flag
+//                    applied and settle must apply it                      call), look at the end of a call (replay)   next step_body (the device flag
 //                                                                                                                      DevStats::pendingKick makes the next
 //                                                                                                                      integrate kernel pay it)
 //  preIntegrated_    the step being launched was opened by the previous    launch_pair (next-step fusion),             sort_and_forces (consumes it), run_steps,   -
 //                    step's pair kernel / boundary kernel                  launch_step_kernels (k_boundary_radi)       graph capture, replay
-//  fuseNext_/fuseNow_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   per-launch scratch: set and consumed inside launch_step_kernels / launch_pair
-//  graphs_, graphCycle_  captured cycles, valid for one buffer state and   graph_for_state                             destroy_graphs: any change of lazyK_,        aztot_set_clock, aztot_set_state (U / radius
-//                    one set of launch parameters                                                                       optimistic_, candLds_ / iterLds_,          first touched), replay
-//                                                                                                                      listWaves_, listsOn_, thermoTouched_
-//  haloInfoPending_  slab: the boundary ranges of the last sort are still  sort_and_forces                             take_halo_info, prepare_next_call, replay   -
-//                    on their way to pinned memory
-//  lastStepEquil_    the last step left its kinetic energy in DevStats     launch_step_kernels                         launch_step_kernels                         -
+//  fuseNext_/fuseNow_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   set and consumed inside launch_step_kernels / launch_pair
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 class Engine
 {
@@ -107,7 +103,7 @@ public:
     int cell_table(int32_t dims[3], int32_t* cellStart, int capCells, int32_t* atomId, int capAtoms);
     int kernel_times(std::vector<KernelTimer>& out);
     void reset_kernel_times();
-    void set_profile(bool on) { settle(); sync(); profile_ = on; }
+    void set_profile(bool on) { sync_all(); profile_ = on; }
     int n_atoms_global() const { return model_.nAt; }
     int comm_ranks() const { return xch_ ? xch_->comm_ranks() : 0; }
     void sync_all();                        // everything queued or deferred by earlier calls has happened when this returns (aztot_sync)
@@ -125,24 +121,20 @@ private:
     bool settle_now() const;
     void settle();
     void mark_failed(const char* what) noexcept;
-    void regrow_lists(int candCap, int iterCap);
     bool unsettled_ = false;                // the last aztot_step call returned with its end (deferred kick, statistics, look) still to come: Engine::settle
     std::string failed_;                    // first error of a step / settle: the handle no longer steps, reads still work
     void construct();
     void release();
-    void destroy_graphs();
     void check_launch(const char* where);
     void choose_cells();
     void allocate();
+    void alloc_atoms(AtomArrays& A, bool zero);
     void upload_initial();
     void upload_bonded();
     void upload_ewald();
     void launch_ewald();
     void sort_and_forces(int stepMode, bool withBonded = true);   // StepMode (kernels.hip.h): bin + sort + forces (aztot_forces), a step that re-sorts, a plain step of the lazy re-sort
     void launch_step_kernels();
-    bool adapt_sort_interval();
-    void look_sync();               // what a look reads (Counts, the list builder's report) copied into pinned memory behind the queued work, then ONE stream synchronisation
-    void* hLook_ = nullptr;         // pinned: Counts followed by 16 ints of PairLists::noList
     void run_steps(int nsteps);
     void launch_pair();
     int pair_variant() const;
@@ -151,12 +143,15 @@ private:
     void finish_steps();
     void check_overflow();
     void sync();
-    template <typename F> void timed(const char* name, F&& launch);
-    template <typename T> T* dev_alloc(size_t n, bool zero, std::vector<void*>* owner);
-    template <typename T> T* dev_alloc(size_t n, bool zero = false) { return dev_alloc<T>(n, zero, &allocs_); }
+    DevStats read_stats();          // DevStats / Counts as a caller may see them: the deferred end of the last call has happened and the stream has drained
+    Counts read_counts();
+    template <typename F> void timed(const char* name, F&& launch) { if (!profile_ || capturing_) launch(); else timers_.timed(name, stream_, launch); }
+    template <typename T> T* dev_alloc(size_t n, bool zero = false) { return mem_.alloc<T>(n, zero, stream_); }
     PairLaunch pair_launch(const StepParams& Q);    // what the pair launches of the step in flight share (Q: P_ as the launch sees it)
     AtomArrays& cur() { return buf_[cur_]; }
     AtomArrays& oth() { return buf_[cur_ ^ 1]; }
+    int left() const { return (rank_ + nranks_ - 1) % nranks_; }       // x-neighbours on the ring of slab ranks
+    int right() const { return (rank_ + 1) % nranks_; }
 
     Model model_;
     aztot_options opt_;
@@ -170,13 +165,13 @@ private:
     hipStream_t stream_ = nullptr;
     hipStream_t commStream_ = nullptr;      // slab ranks, plain steps: the coordinate exchange runs here while the interior cells' pair forces run on stream_
     hipEvent_t evIntegrated_ = nullptr, evHalo_ = nullptr;
-    bool overlapHalo_ = false;              // the pair launch in flight is split: interior cells now, boundary cells once evHalo_ has fired
+    DeviceArena mem_;               // every device buffer below except the pair lists' and the RDF sampler's
+    bool profile_ = false;
+    KernelTimers timers_;
     int capacity_ = 0;          // atoms that fit in the per-atom arrays (owned + ghosts + slack)
-    int nCellAlloc_ = 0;
     int maxBlocks_ = 0;
     AtomArrays buf_[2]{};
     int cur_ = 0;
-    std::vector<void*> allocs_;
     DevPot* dPots_ = nullptr;
     int32_t *dCellOf_ = nullptr, *dSlotOf_ = nullptr, *dCellCount_ = nullptr, *dCellStart_ = nullptr;
     int32_t* dChunkTot_ = nullptr;
@@ -189,12 +184,29 @@ private:
     double* dEkGlobal_ = nullptr;   // kinetic energy over all ranks (equilibration scaling only)
     char* dMsg_[4] = {nullptr, nullptr, nullptr, nullptr};   // sendLeft, sendRight, fromLeft, fromRight
     MsgLayout lay_{};
-    int pairBlocks_ = 0, pairBlocksUsed_ = 0, splitBlocks_ = 0;
-    int blocksEver_ = 0;            // partial-sum entries any launch has booked into so far (what k_collect has to read of the accumulating rows)
-    // lazy re-sort (one GPU): the cells are rebuilt only every lazyK_ steps; in between the atoms keep their slots, coordinates stay unwrapped and
-    // every step checks that no atom has moved farther than lazySlack_ from where it was sorted (RefPos) - see Engine::step
+    SplitArgs split_{};             // few cells, wide stencils: several waves per cell in the staging kernel (pair_tile.hip.h)
+    BondedTables bonded_{};         // all-null when the model has no bonds / angles
+    bool hasBonded_ = false;
+    EwaldTables ew_{};              // reciprocal-space Ewald sum ('elec pme')
+    bool hasEwald_ = false;
+    bool thermoTouched_ = false;    // the caller set U / radius on a run whose model does not use them: keep them attached to their atoms
+
+    // -- pair lists of the lazy re-sort ---
+    ListStore lists_;
+    // a sort interval may run on from one aztot_step call into the next (one GPU, pair lists): the lists recorded at the last rebuild are those of the
+    // arrays as they stand; set_state / aztot_forces end that
+    bool listsValid_ = false;
+    // slab ranks: how many cells the last list build left without a list, copied to pinned memory behind the build; once the copy has landed and says
+    // "none", the clean-up launches of the interval are skipped (a slab rank cannot widen its stencil, so the clean-up launch has nothing else to do there)
+    PinnedReadback hUnlisted_;
+    int unlistedState_ = 0;         // 0 unknown (copy in flight or never made), 1 known to be zero, 2 known to be non-zero
+    bool unlistedAtLook_ = false;   // the last look found cells recorded without a list
+
+    // -- sort interval: lazy re-sort (one GPU): the cells are rebuilt only every lazyK_ steps; in between the atoms keep their slots, coordinates stay
+    // unwrapped and every step checks that no atom has moved farther than lazySlack_ from where it was sorted (RefPos) - see Engine::run_steps ---
+    static constexpr int kNoSort = 1 << 30;     // sinceSort_: no rebuild to count from (the next step rebuilds the cells)
     bool lazyOn_ = false;
-    int lazyK_ = 1;                 // current sort interval (1: every step); adapted after every aztot_step call from the largest step seen
+    int lazyK_ = 1;                 // current sort interval (1: every step); adapted at every look from the largest step seen
     int lazyCap_ = 32;
     long long lazyViolations_ = 0;
     int lazyWindow_ = 8;               // steps between two looks at the speeds: 8, 16, ... 256
@@ -203,69 +215,42 @@ private:
                                        // without a violation at 1.05 too); widened by every violation (a system that heats up)
     bool lazyMeasured_ = false;     // the interval has been sized from a measurement at least once
     double lastLookLen_ = 0.0;      // the longest step of the window before the last look (0: none to compare with): growing speeds widen the margin
-    int sinceSort_ = 1 << 30;       // plain steps since the last sort
+    int sinceSort_ = kNoSort;       // plain steps since the last sort
     long long rebuilds_ = 0;        // steps that rebuilt the cell list so far
     double lazySlack_ = 0.0;
-    RefPos ref_{};
-    // lists of the lazy re-sort (pair_tile.hip.h / pair_list.hip.h), recorded by the step that rebuilds the cells and walked by the plain steps: per cell the
-    // candidates its tile held, and per atom of the cell its partners among them, dealt evenly to the lanes
-    uint32_t* dCandList_ = nullptr;
-    int32_t* dListMeta_ = nullptr;
-    uint16_t* dPairList_ = nullptr;
-    int candLds_ = 0, iterLds_ = 0; // what the LDS tiles of k_pair_list / k_build_lists are sized for (<= the capacities; from the largest cell recorded)
-    float4* dRel_ = nullptr;        // [capacity + 64] position relative to the own cell's centre (f32) + cell z index, written by the sort for the list builder
-    int candCap_ = 0, iterCap_ = 0; // capacities of the lists per cell (PairLists); grown when too many cells turn out not to fit
-    int listGrowths_ = 0;
-    int listWaves_ = 1;             // waves per cell in k_pair_list (PairLists::waves)
-    size_t listLdsMax_ = 0;         // dynamic LDS this device grants a workgroup
-    void allocate_lists(int candCap, int iterCap);
-    void free_lists();
-    PairLists pair_lists() const;
     double skinTarget_ = 0.0;       // the skin the cells were sized for (0: none)
-    int32_t* dNoList_ = nullptr;    // [2]: cells recorded without / with a list since the host last looked
-    bool listsOn_ = false;          // plain steps run k_pair_list (switched off when too many cells turn out to keep no list)
-    int candMode_ = 0;              // for the pair launch in flight: 0 none, 1 record, 2 plain step of the lazy re-sort
+    RefPos ref_{};
+    bool carryAgreed_ = false;      // slab ranks: every rank can carry the interval on (decided together at the end of the previous call)
+    void forget_interval() { sinceSort_ = kNoSort; listsValid_ = false; carryAgreed_ = false; }     // the next step rebuilds the cells
+    void void_measurement() { lazyMeasured_ = false; lazyWindow_ = 8; sinceLook_ = 0; }             // what the looks have learnt says nothing about the steps ahead
+    void set_interval(int K) { if (K != lazyK_) { lazyK_ = K; drop_graphs(); } }
+    void clear_violation_flag();
+    int window_cap() const { return nranks_ > 1 ? 64 : 256; }       // (a slab rank repairs a skin violation by running the window again: it looks more often)
+    void look_sync();               // what a look reads (Counts, the list builder's report) copied into pinned memory behind the queued work, then ONE stream synchronisation
+    PinnedReadback hLook_;          // Counts followed by the builder's report (ListReport)
+    bool adapt_sort_interval();
+    void look(bool callEnd);
+    void prepare_next_call();
     int halo_[5] = {0, 0, 0, 0, 0};  // slab ranks: ownedBegin, end of the left boundary layers, start of the right ones, ownedEnd, nTotal (after the last sort)
     // read back after every sort without stalling the stream: copied into pinned host memory behind the sort kernels, waited for only when the next plain
     // step needs the numbers (by then the list building and the pair kernel of the sort step are queued behind the copy)
-    int32_t* hHalo_ = nullptr;       // pinned: {cellStart of the two boundary layers, ownedBegin, ownedEnd, nTotal}
+    PinnedReadback hHalo_;           // the halo block (enum HaloInfo)
     int32_t* dHaloInfo_ = nullptr;   // the same on the device, written by k_rank_gather
-    hipEvent_t evHaloInfo_ = nullptr;
     bool haloInfoPending_ = false;
     void take_halo_info();
     void post_count_exchange();
     void adopt_halo_info(const int32_t* h);
-    int graphCycle_ = 0;            // steps held by the captured graphs
-    BondedTables bonded_{};         // all-null when the model has no bonds / angles
-    bool hasBonded_ = false;
-    bool thermoTouched_ = false;    // the caller set U / radius on a run whose model does not use them: keep them attached to their atoms
-    bool lazyKick_ = false;         // large plain-NVE runs: integrate2 is folded into the next step's integrate1 (flushed by finish_steps)
-    bool kickOwed_ = false;
+
     // Equilibration rescaling (control.txt: nequil / eqfreq) acts on a handful of steps only - step numbers the host can tell (hostStep_ mirrors DevStats::step) -,
     // so only those steps take the path that sums the kinetic energy on the device, decides a factor and scales; every other step of a thermostat run takes the
     // short path of a run without equilibration (case study 2: 6 launches per step -> 2)
     long long hostStep_ = 0;        // steps launched so far (== DevStats::step once the stream has drained)
-    bool lastStepEquil_ = false;    // the last step launched left its kinetic energy in DevStats::local (k_reduce_kin), not in the partial sums
     bool equil_phase() const { return P_.nEq > 0 && hostStep_ < P_.nEq; }
-    bool fuseEpilogue_ = false;     // small plain-NVE runs: the tile kernel's epilogue applies integrate2
-    bool fuseNow_ = false;          // the pair launch in flight also does integrate2's job (plain NVE steps, tile kernel)
-    bool ekinFromPair_ = false;     // where the last step left its kinetic-energy partials
-    EwaldTables ew_{};              // reciprocal-space Ewald sum ('elec pme')
-    bool hasEwald_ = false;
 
     // statistics window for the wall-momentum pressure (main.cpp:143-163)
     double lastMom_[6] = {0, 0, 0, 0, 0, 0};
     double pressure_ = 0.0;
     long long lastPresStep_ = 0;
-
-    // profiling
-    bool profile_ = false;
-    std::vector<KernelTimer> timers_;
-    std::map<std::string, int> timerIndex_;
-    struct PendingEvent { int idx; hipEvent_t a, b; };
-    std::vector<PendingEvent> pending_;
-    std::vector<hipEvent_t> eventPool_;
-    void drain_events();
 
     struct RdfState
     {
@@ -275,7 +260,7 @@ private:
         long long samples = 0;
         int copies = 0;                 // LDS sub-histograms per workgroup of k_rdf_pairs (0: straight into the totals)
         int blocks = 0;
-        std::vector<void*> allocs;
+        DeviceArena mem;
         int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
         double *x = nullptr, *y = nullptr, *z = nullptr;
         unsigned long long *histS = nullptr, *histN = nullptr;
@@ -283,26 +268,42 @@ private:
         DevStats* scanStats = nullptr;
         RdfGrid grid{};
     } rdf_;
-    void rdf_free();
 
-    // hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was captured in
-    // (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue swaps
-    // coordinate arrays); it also remembers the state it leaves behind
+    // -- graphs: hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was
+    // captured in (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue
+    // swaps coordinate arrays); it also remembers the state it leaves behind ---
     struct BufState { int cur; double* xyz[2][3]; double* alt[2][3]; };
     // ... and what the host notes down while it launches a step for whoever reduces the statistics afterwards (finish_steps): a replayed cycle does not pass
     // through that host code, so the slot carries the notes of its last step (found by the call-pattern fuzz of round 4: aztot_forces - whose staging launch
     // books into more partial-sum slots than the list kernel - followed by a call served entirely by replays summed stale slots into the energies)
-    struct LaunchNotes { int pairBlocksUsed = 0, blocksEver = 0; bool ekinFromPair = false, lastStepEquil = false; };
+    struct LaunchNotes
+    {
+        int pairBlocksUsed = 0;
+        int blocksEver = 0;             // partial-sum entries any launch has booked into so far (what k_collect has to read of the accumulating rows)
+        bool ekinFromPair = false;      // where the last step left its kinetic-energy partials
+        bool lastStepEquil = false;     // the last step launched left its kinetic energy in DevStats::local (k_reduce_kin), not in the partial sums
+    } notes_;                           // of the last step EXECUTED (launched one by one, or the last of a replayed cycle)
     struct GraphSlot { BufState before, after; LaunchNotes notes; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
-    LaunchNotes launch_notes() const { LaunchNotes n; n.pairBlocksUsed = pairBlocksUsed_; n.blocksEver = blocksEver_; n.ekinFromPair = ekinFromPair_; n.lastStepEquil = lastStepEquil_; return n; }
-    void adopt_launch_notes(const LaunchNotes& n) { pairBlocksUsed_ = n.pairBlocksUsed; blocksEver_ = std::max(blocksEver_, n.blocksEver); ekinFromPair_ = n.ekinFromPair; lastStepEquil_ = n.lastStepEquil; }
+    void adopt_launch_notes(const LaunchNotes& n) { const int ever = std::max(notes_.blocksEver, n.blocksEver); notes_ = n; notes_.blocksEver = ever; }
     std::vector<GraphSlot> graphs_;
+    int graphCycle_ = 0;            // steps held by the captured graphs
+    bool capturing_ = false;
+    // The captured graphs are stale (a launch parameter or a baked-in pointer changed).  graphCycle_ goes back to 0 with them: graph_for_state compares
+    // it with the cycle it is asked for and, finding no graph either way, captures anew - so callers that used to leave it alone lose nothing
+    void drop_graphs();
     BufState buf_state() const;
     GraphSlot* graph_for_state(int cycle);
     int graph_cycle() const;
     bool can_graph() const;
     void set_buf_state(const BufState& b);
-    bool capturing_ = false;
+
+    // -- per-launch scratch, and who applies the second half-kick (decided once, in the constructor) ---
+    bool lazyKick_ = false;         // large plain-NVE runs: integrate2 is folded into the next step's integrate1 (flushed by finish_steps)
+    bool kickOwed_ = false;
+    bool fuseEpilogue_ = false;     // small plain-NVE runs: the tile kernel's epilogue applies integrate2
+    bool fuseNow_ = false;          // the pair launch in flight also does integrate2's job (plain NVE steps, tile kernel)
+    bool overlapHalo_ = false;      // the pair launch in flight is split: interior cells now, boundary cells once evHalo_ has fired
+    int candMode_ = 0;              // for the pair launch in flight: 0 none, 1 record, 2 plain step of the lazy re-sort
     // next-step fusion (pair_tile.hip.h NextStep): on plain NVE steps of a lazy run on one GPU the pair kernel's epilogue also does the next step's
     // k_integrate1_bin<2>; the new positions go to a second set of coordinate arrays, swapped in after the launch
     double* altXyz_[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
@@ -312,44 +313,36 @@ private:
     bool pairClosedStep_ = false;   // the pair launch of the step in flight has closed the step (second half-kick + thermostat): no k_integrate2_post / k_boundary_radi
     bool preIntegrated_ = false;    // the step being launched was opened by the previous step's pair kernel: no k_integrate1_bin
     int stepsLeftInRun_ = 0;        // steps that follow the one being launched before the host looks / the cycle ends
-    // a sort interval may run on from one aztot_step call into the next (one GPU, pair lists): the lists recorded at the last rebuild are those of the
-    // arrays as they stand; set_state / aztot_forces end that
-    SplitArgs split_{};             // few cells, wide stencils: several waves per cell in the staging kernel (pair_tile.hip.h)
-    bool listsValid_ = false;
-    // slab ranks: how many cells the last list build left without a list, copied to pinned memory behind the build; once the copy has landed and says
-    // "none", the clean-up launches of the interval are skipped (a slab rank cannot widen its stencil, so the clean-up launch has nothing else to do there)
-    int32_t* hUnlisted_ = nullptr;
-    hipEvent_t evUnlisted_ = nullptr;
-    int unlistedState_ = 0;         // 0 unknown (copy in flight or never made), 1 known to be zero, 2 known to be non-zero
-    bool carryAgreed_ = false;      // slab ranks: every rank can carry the interval on (decided together at the end of the previous call)
-    // Slab ranks cannot repair a skin violation on the spot (they hold hw ghost layers: no wider stencil to fall back on), and the host learns of one only
-    // at its next look.  So every look that finds none leaves a snapshot of the dynamic state (per-atom arrays, DevStats, Counts, partial sums - what an
-    // exact restart needs, device to device), and a look that finds one goes back to it and runs the steps since again with the cells rebuilt every
-    // step, which is exact whatever the speeds (all ranks together: the verdict is all-reduced).  A violation costs time, never exactness.
-    struct Snapshot
+
+    // -- snapshot: Slab ranks cannot repair a skin violation on the spot (they hold hw ghost layers: no wider stencil to fall back on), and the host learns
+    // of one only at its next look.  So every look that finds none leaves a snapshot of the dynamic state (per-atom arrays, DevStats, Counts, partial sums -
+    // what an exact restart needs, device to device), and a look that finds one goes back to it and runs the steps since again with the cells rebuilt every
+    // step, which is exact whatever the speeds (all ranks together: the verdict is all-reduced).  A violation costs time, never exactness. ---
+    struct DynState                 // what k_copy_state copies
     {
         AtomArrays A{};
         void *stats = nullptr, *counts = nullptr;
         double* partials = nullptr;
+    };
+    struct Snapshot : DynState
+    {
         BufState buf{};
         long long hostStep = 0;
         bool valid = false;
     } snap_;
     long long stepsSinceSnap_ = 0;
+    DynState live() { return DynState{cur(), dStats_, dCounts_, dPartials_}; }
+    void copy_state(DynState from, DynState to);
     // One GPU, small systems (a step is a handful of microsecond kernels: the clean-up launch behind every k_pair_list is a quarter of a 40 000-atom step and
     // nearly always has nothing to do): the same snapshots let the plain steps run WITHOUT it.  A look that finds a violation or a cell that kept no list
     // goes back and runs the window again with the launch in place (exact as before), and the run stays on the safe side for a few looks.
     bool optimistic_ = false;
     int safeLooks_ = 1;             // looks still to be spent with the clean-up launch in place (an engine's first; 8, 16, 32 ... after a window had to be run again)
     int rollbacks_ = 0;
-    bool unlistedAtLook_ = false;   // the last look found cells recorded without a list
     void choose_optimism();
     bool rollback_on() const { return lazyOn_ && (nranks_ > 1 || optimistic_); }
     void take_snapshot();
     void replay_from_snapshot();
-    void prepare_next_call();
 };
-
-void check_hip(hipError_t e, const char* what);
 
 }  // namespace aztot

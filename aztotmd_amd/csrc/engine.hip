@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <array>
 #include <cstring>
 #include <cstddef>
 #include <cstdio>
@@ -39,63 +40,36 @@ constexpr int kListIterMax = 248;
 constexpr long long kSnapshotKeepSteps = 32;     // a verified snapshot younger than this is kept at the end of a call (Engine::settle)
 }  // namespace
 
-// device memory for n elements (never less than 16 bytes), zero-filled on stream_ if asked.  `owner` is the list that frees it: the engine's (release), the
-// RDF sampler's (rdf_free), or none - the caller frees it itself (free_lists)
-template <typename T> T* Engine::dev_alloc(size_t n, bool zero, std::vector<void*>* owner)
-{
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, std::max<size_t>(sizeof(T) * n, 16)));
-    if (owner) owner->push_back(p);
-    if (zero) HIP_CHECK(hipMemsetAsync(p, 0, sizeof(T) * n, stream_));
-    return (T*)p;
-}
-
-template <typename F>
-void Engine::timed(const char* name, F&& launch)
-{
-    if (!profile_ || capturing_) { launch(); return; }
-    int idx;
-    auto it = timerIndex_.find(name);
-    if (it == timerIndex_.end())
-    {
-        idx = (int)timers_.size();
-        timers_.push_back(KernelTimer{name, 0.0, 0});
-        timerIndex_[name] = idx;
-    }
-    else idx = it->second;
-    auto get = [&]() {
-        if (!eventPool_.empty()) { hipEvent_t e = eventPool_.back(); eventPool_.pop_back(); return e; }
-        hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); return e;
-    };
-    hipEvent_t a = get(), b = get();
-    HIP_CHECK(hipEventRecord(a, stream_));
-    launch();
-    HIP_CHECK(hipEventRecord(b, stream_));
-    pending_.push_back({idx, a, b});
-    if (pending_.size() > 8192) { HIP_CHECK(hipStreamSynchronize(stream_)); drain_events(); }
-}
-
-void Engine::drain_events()
-{
-    for (auto& p : pending_)
-    {
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
-        timers_[p.idx].ms += ms;
-        timers_[p.idx].calls += 1;
-        eventPool_.push_back(p.a); eventPool_.push_back(p.b);
-    }
-    pending_.clear();
-}
-
 void Engine::sync()
 {
     HIP_CHECK(hipStreamSynchronize(stream_));
-    if (profile_) drain_events();
+    if (profile_) timers_.drain();
 }
 
-int Engine::kernel_times(std::vector<KernelTimer>& out) { settle(); sync(); out = timers_; return (int)out.size(); }
-void Engine::reset_kernel_times() { settle(); sync(); for (auto& t : timers_) { t.ms = 0; t.calls = 0; } }
+void Engine::sync_all()
+{
+    settle();
+    sync();
+}
+
+DevStats Engine::read_stats()
+{
+    sync_all();
+    DevStats s;
+    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
+    return s;
+}
+
+Counts Engine::read_counts()
+{
+    sync_all();
+    Counts c;
+    HIP_CHECK(hipMemcpy(&c, dCounts_, sizeof(Counts), hipMemcpyDeviceToHost));
+    return c;
+}
+
+int Engine::kernel_times(std::vector<KernelTimer>& out) { sync_all(); out = timers_.totals(); return (int)out.size(); }
+void Engine::reset_kernel_times() { sync_all(); timers_.reset(); }
 
 // ---------------------------------------------------------------------------------------------------
 // cell grid: split_cells (cuCellList.cu:9-34, div_type 1: edge >= requested size).  No pair tables are
@@ -320,8 +294,8 @@ void Engine::construct()
         // gather: case study 2's surk potential), not with bonded terms or the Ewald sum (their forces arrive after the pair kernel).
         const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP) && !P_.use_radii && P_.potSet != POTSET_ONE_SURK && (P_.single_lj || P_.potSet == POTSET_ONE_FAMILY) &&
                               nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
-        fuseNextTstat_ = radiFuse && listsOn_ && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
-        if (((plainNve && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && listsOn_ && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
+        fuseNextTstat_ = radiFuse && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
+        if (((plainNve && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
         {
             fuseNextOk_ = true;
             for (int b = 0; b < 2; b++)
@@ -342,7 +316,7 @@ void Engine::construct()
 
 Engine::~Engine() { release(); }
 
-void Engine::destroy_graphs()
+void Engine::drop_graphs()
 {
     for (GraphSlot& g : graphs_)
     {
@@ -350,6 +324,7 @@ void Engine::destroy_graphs()
         if (g.graph) (void)hipGraphDestroy(g.graph);
     }
     graphs_.clear();
+    graphCycle_ = 0;
 }
 
 Engine::BufState Engine::buf_state() const
@@ -374,31 +349,15 @@ void Engine::set_buf_state(const BufState& b)
     }
 }
 
+// What the order of destruction cannot express: the streams drain before anything they use goes (the members free their memory, pinned blocks and
+// events afterwards, in their destructors - also when the constructor throws)
 void Engine::release()
 {
     if (stream_) (void)hipStreamSynchronize(stream_);
-    destroy_graphs();
-    for (auto& p : pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    pending_.clear();
-    for (auto e : eventPool_) (void)hipEventDestroy(e);
-    eventPool_.clear();
-    for (void* p : allocs_) (void)hipFree(p);
-    allocs_.clear();
-    free_lists();
-    rdf_free();
+    drop_graphs();
     if (evIntegrated_) (void)hipEventDestroy(evIntegrated_);
     if (evHalo_) (void)hipEventDestroy(evHalo_);
     evIntegrated_ = evHalo_ = nullptr;
-    if (evUnlisted_) (void)hipEventDestroy(evUnlisted_);
-    evUnlisted_ = nullptr;
-    if (hUnlisted_) (void)hipHostFree(hUnlisted_);
-    hUnlisted_ = nullptr;
-    if (evHaloInfo_) (void)hipEventDestroy(evHaloInfo_);
-    evHaloInfo_ = nullptr;
-    if (hHalo_) (void)hipHostFree(hHalo_);
-    hHalo_ = nullptr;
-    if (hLook_) (void)hipHostFree(hLook_);
-    hLook_ = nullptr;
     if (commStream_) { (void)hipStreamSynchronize(commStream_); (void)hipStreamDestroy(commStream_); }
     commStream_ = nullptr;
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -410,6 +369,15 @@ void Engine::check_launch(const char* where)
 {
     if (capturing_) return;
     check_hip(hipGetLastError(), where);
+}
+
+// the eleven double arrays of an AtomArrays in StateCopy's order (its two int32_t arrays are type, id)
+static std::array<double**, 11> double_arrays(AtomArrays& A) { return {&A.x, &A.y, &A.z, &A.vx, &A.vy, &A.vz, &A.fx, &A.fy, &A.fz, &A.U, &A.rad}; }
+
+void Engine::alloc_atoms(AtomArrays& A, bool zero)
+{
+    for (double** pp : double_arrays(A)) *pp = dev_alloc<double>((size_t)capacity_, zero);
+    A.type = dev_alloc<int32_t>((size_t)capacity_, zero); A.id = dev_alloc<int32_t>((size_t)capacity_, zero);
 }
 
 void Engine::allocate()
@@ -447,7 +415,6 @@ void Engine::allocate()
         lay_.migCap = (int)std::min<double>((double)N, std::ceil(maxLayer * 0.03) + 1024);
     }
     else capacity_ = N;
-    nCellAlloc_ = P_.nCellLocal;
     // + 24: a split launch rounds each of its three runs up to 8 workgroups; the clean-up launches behind k_pair_list book into their own slots
     {   // few cells (less than half a residency of waves) and a stencil with columns to share out: several waves per cell in the staging kernel
         const int cells = pair_tile_cells(P_);
@@ -465,16 +432,10 @@ void Engine::allocate()
         split_.n = n;
         split_.capacity = capacity_;
     }
-    pairBlocks_ = std::max(div_up(capacity_, kBlock), pair_tile_grid(P_) * std::max(split_.n, kListMaxWaves) + 24 + 3 * pair_cleanup_grid(pair_tile_cells(P_)));
-    maxBlocks_ = std::max(div_up(capacity_, kBlock), pairBlocks_) + 1;
-    const size_t nAtoms = (size_t)capacity_, nCells = (size_t)(nCellAlloc_ + 1);
-    for (int b = 0; b < 2; b++)
-    {
-        AtomArrays& A = buf_[b];
-        double** d[] = {&A.x, &A.y, &A.z, &A.vx, &A.vy, &A.vz, &A.fx, &A.fy, &A.fz, &A.U, &A.rad};
-        for (auto pp : d) *pp = dev_alloc<double>(nAtoms, true);
-        A.type = dev_alloc<int32_t>(nAtoms, true); A.id = dev_alloc<int32_t>(nAtoms, true);
-    }
+    const int pairBlocks = std::max(div_up(capacity_, kBlock), pair_tile_grid(P_) * std::max(split_.n, kListMaxWaves) + 24 + 3 * pair_cleanup_grid(pair_tile_cells(P_)));
+    maxBlocks_ = std::max(div_up(capacity_, kBlock), pairBlocks) + 1;
+    const size_t nAtoms = (size_t)capacity_, nCells = (size_t)(P_.nCellLocal + 1);
+    for (AtomArrays& A : buf_) alloc_atoms(A, true);
     dCellOf_ = dev_alloc<int32_t>(nAtoms); dSlotOf_ = dev_alloc<int32_t>(nAtoms);
     dTmpId_ = dev_alloc<int32_t>(nAtoms); dTmpSrc_ = dev_alloc<int32_t>(nAtoms); dTmpCell_ = dev_alloc<int32_t>(nAtoms); dCellOfSorted_ = dev_alloc<int32_t>(nAtoms);
     dCellCount_ = dev_alloc<int32_t>(nCells, true); dCellStart_ = dev_alloc<int32_t>(nCells, true);
@@ -492,12 +453,12 @@ void Engine::allocate()
         split_.fx = dev_alloc<double>(nb); split_.fy = dev_alloc<double>(nb); split_.fz = dev_alloc<double>(nb);
         split_.arrived = dev_alloc<int32_t>((size_t)P_.nCellLocal, true);
     }
-    dCounts_ = dev_alloc<Counts>(1); dChunkTot_ = dev_alloc<int32_t>((size_t)(div_up(nCellAlloc_, kScanChunk) + 1));
+    dCounts_ = dev_alloc<Counts>(1); dChunkTot_ = dev_alloc<int32_t>((size_t)(div_up(P_.nCellLocal, kScanChunk) + 1));
     dEkGlobal_ = dev_alloc<double>(2); dStage_ = dev_alloc<double>((size_t)PS_COUNT * kCollectParts, true);
     if (nranks_ > 1)
     {
         for (int k = 0; k < 4; k++) dMsg_[k] = dev_alloc<char>(lay_.bytes(), true);
-        dHaloInfo_ = dev_alloc<int32_t>(16, true);
+        dHaloInfo_ = dev_alloc<int32_t>(HI_COUNT, true);
     }
     const int ns = model_.nSpec();
     std::vector<DevPot> pots((size_t)ns * ns);
@@ -540,49 +501,7 @@ void Engine::allocate()
         {
             ref_.x = dev_alloc<double>(nAtoms); ref_.y = dev_alloc<double>(nAtoms); ref_.z = dev_alloc<double>(nAtoms);
             if (capacity_ < (1 << 26) && !(debug_ & DBG_NO_LISTS))          // atom index + 6 bits of image code in 32 bits
-            {
-                if (P_.ncxLocal > 1023 || P_.nc[1] > 1023 || P_.nc[2] > 1023) throw std::runtime_error("more than 1023 cells along an axis");
-                int devLds = 0;
-                HIP_CHECK(hipDeviceGetAttribute(&devLds, hipDeviceAttributeMaxSharedMemoryPerBlock, opt_.device));
-                listLdsMax_ = (size_t)std::max(devLds, 64 * 1024);
-                // capacities from the density: candidates = atoms within the list radius of a cell's box, iterations = pairs of a cell / 64 lanes, each
-                // with room for a liquid's fluctuations (+ 30 % / + 50 %); cells that need more keep no list, and the engine grows the lists when
-                // that happens to more than a few (adapt_sort_interval)
-                const double a = P_.csz[0], b = P_.csz[1], c = P_.csz[2], r = rp;
-                const double vol = swept_volume(a, b, c, r);
-                const double density = (double)m.nAt / (m.L[0] * m.L[1] * m.L[2]);
-                const double perCell = density * a * b * c, partners = density * 4.18879020478639 * r * r * r;
-                // (a cell's iterations are its atoms' partners divided by the slices each atom gets, NS = 64 / atoms: sized for a cell 60 % fuller than the mean)
-                const int nBig = std::min(kWave, (int)(1.6 * perCell) + 6);
-                int cand = (int)(density * vol * 1.5) + 64;
-                int iters = (int)(partners * 1.25 / list_slices(nBig)) + 4;
-                // waves per cell in k_pair_list (they share the cell's tile and split its atoms): one where cells are many and their tiles small; more where the
-                // tile of a cell is large (LDS per wave bounds the occupancy: dense systems, wide stencils) - measured: M4 (28 atoms and 720 candidates per
-                // cell) 788 -> 514 us with two; on the 1 M-atom liquid (14 atoms, 320 candidates) two waves cost 102 -> 158 us: every wave pays the
-                // fixed part of a cell again
-                {
-                    const int cells = pair_tile_cells(P_);
-                    const double tileBytes = density * vol * (P_.single_lj ? 24.0 : (pair_list_tab_mode(P_) ? 25.0 : 32.0));
-                    int w = 1;
-                    (void)cells;             // (few cells alone do not pay for more waves: C2 13.9 -> 15.2 us, an emulated rank of 8 26.8 -> 29.2 us with two)
-                    if (tileBytes > 13.0 * 1024) w = 2;
-                    if (tileBytes > 26.0 * 1024) w = 4;
-                    if (opt_.waves_per_cell == 1 || opt_.waves_per_cell == 2 || opt_.waves_per_cell == 4) w = opt_.waves_per_cell;
-                    listWaves_ = w;
-                    // (a wave of a W-wave cell serves ceil(n / W) atoms: sized for a cell 60 % fuller than the mean, as above)
-                    iters = (int)(partners * 1.25 / list_slices(list_atoms_per_wave(std::min(kWave * w, (int)(1.6 * perCell) + 6), w))) + 4;
-                }
-                cand = std::max(kListMinCand * listWaves_, (cand + 63) & ~63);
-                iters = std::max(2 * kListMinIter, (iters + 7) & ~7);
-                if (const char* e = std::getenv("AZTOT_CAND_CAP")) cand = std::atoi(e);        // (experiments / tests: start from other capacities)
-                if (const char* e = std::getenv("AZTOT_ITER_CAP")) iters = std::atoi(e);
-                try { allocate_lists(cand, iters); }
-                catch (const std::exception&)
-                {   // (no room for the lists - hundreds of millions of cells: the run goes on without them, the steps between two rebuilds stage every cell)
-                    (void)hipGetLastError();
-                    free_lists();
-                }
-            }
+                lists_.create(P_, m, opt_, capacity_, rp, stream_, rank_);
         }
     }
     dPots_ = dev_alloc<DevPot>(pots.size());
@@ -590,84 +509,224 @@ void Engine::allocate()
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
-// Lists of the lazy re-sort (pair_list.hip.h): [nCell][candCap] candidates, [nCell][iterCap x 64] pair entries, headers.  Capacities are clipped to
-// what the LDS of k_pair_list / k_build_lists and the entry format allow.
-void Engine::allocate_lists(int candCap, int iterCap)
+// ---------------------------------------------------------------------------------------------------
+// ListStore (list_store.h)
+// ---------------------------------------------------------------------------------------------------
+// bytes of k_pair_list's LDS tile per candidate are 24, 25 or 32 with the pair mode; tiles beyond 13 / 26 KiB, or lists beyond 96 / 192 iterations, want
+// 2 / 4 waves per cell (they share the cell's tile and split its atoms): one where cells are many and their tiles small; more where the tile of a cell is
+// large (LDS per wave bounds the occupancy: dense systems, wide stencils) - measured: M4 (28 atoms and 720 candidates per cell) 788 -> 514 us with two; on
+// the 1 M-atom liquid (14 atoms, 320 candidates) two waves cost 102 -> 158 us: every wave pays the fixed part of a cell again.  (Few cells alone do not
+// pay for more waves: C2 13.9 -> 15.2 us, an emulated rank of 8 26.8 -> 29.2 us with two.)
+int ListStore::waves_wanted(double tileRecords, int iters) const
 {
-    free_lists();
-    // (k_pair_list asks for five groups of candidate entries per wave and two chunks of 8 iterations before it knows the cell: the arrays are never smaller)
-    candCap = std::max(kListMinCand * listWaves_, std::min((candCap + 63) & ~63, kListCandMax));
-    iterCap = std::max(kListMinIter, std::min((iterCap + 7) & ~7, kListIterMax));
-    PairLists probe;
-    probe.candCap = probe.candLds = candCap; probe.iterCap = probe.iterLds = iterCap; probe.recBytes = pair_list_rec_bytes(P_); probe.waves = listWaves_;
-    while (candCap > kListMinCand && (pair_list_lds_bytes(P_, probe) > listLdsMax_ || build_lists_lds_bytes(probe) > listLdsMax_))
-    {
-        candCap -= 64;
-        probe.candCap = probe.candLds = candCap;
+    const double tileBytes = tileRecords * (P_->single_lj ? 24.0 : (pair_list_tab_mode(*P_) ? 25.0 : 32.0));
+    if (tileBytes > 26.0 * 1024 || iters > 192) return 4;
+    return (tileBytes > 13.0 * 1024 || iters > 96) ? 2 : 1;
+}
+
+void ListStore::create(const StepParams& P, const Model& m, const aztot_options& opt, int capacity, double listRadius, hipStream_t stream, int rank)
+{
+    P_ = &P; stream_ = stream; capacity_ = capacity; rank_ = rank;
+    forcedWaves_ = (opt.waves_per_cell == 1 || opt.waves_per_cell == 2 || opt.waves_per_cell == 4) ? opt.waves_per_cell : 0;      // measurements: forced
+    if (P.ncxLocal > 1023 || P.nc[1] > 1023 || P.nc[2] > 1023) throw std::runtime_error("more than 1023 cells along an axis");
+    int devLds = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&devLds, hipDeviceAttributeMaxSharedMemoryPerBlock, opt.device));
+    ldsMax_ = (size_t)std::max(devLds, 64 * 1024);
+    // capacities from the density: candidates = atoms within the list radius of a cell's box, iterations = pairs of a cell / 64 lanes, each
+    // with room for a liquid's fluctuations (+ 30 % / + 50 %); cells that need more keep no list, and the store grows the lists when
+    // that happens to more than a few (adapt)
+    const double a = P.csz[0], b = P.csz[1], c = P.csz[2], r = listRadius;
+    const double vol = swept_volume(a, b, c, r);
+    const double density = (double)m.nAt / (m.L[0] * m.L[1] * m.L[2]);
+    const double perCell = density * a * b * c, partners = density * 4.18879020478639 * r * r * r;
+    waves = forcedWaves_ ? forcedWaves_ : waves_wanted(density * vol, 0);
+    int cand = (int)(density * vol * 1.5) + 64;
+    // (a cell's iterations are its atoms' partners divided by the slices each atom gets, NS = 64 / atoms; a wave of a W-wave cell serves ceil(n / W)
+    //  atoms: sized for a cell 60 % fuller than the mean)
+    int iters = (int)(partners * 1.25 / list_slices(list_atoms_per_wave(std::min(kWave * waves, (int)(1.6 * perCell) + 6), waves))) + 4;
+    cand = std::max(kListMinCand * waves, (cand + 63) & ~63);
+    iters = std::max(2 * kListMinIter, (iters + 7) & ~7);
+    if (const char* e = std::getenv("AZTOT_CAND_CAP")) cand = std::atoi(e);        // (experiments / tests: start from other capacities)
+    if (const char* e = std::getenv("AZTOT_ITER_CAP")) iters = std::atoi(e);
+    try { allocate(cand, iters); }
+    catch (const std::exception&)
+    {   // (no room for the lists - hundreds of millions of cells: the run goes on without them, the steps between two rebuilds stage every cell)
+        (void)hipGetLastError();
+        release();
     }
-    while (iterCap > 2 * kListMinIter && build_lists_lds_bytes(probe) > listLdsMax_) { iterCap -= 8; probe.iterCap = probe.iterLds = iterCap; }
-    const size_t nc = (size_t)P_.nCellLocal;
-    dCandList_ = dev_alloc<uint32_t>(nc * candCap, true, nullptr);             // (free_lists owns these five) every entry is an atom index at all times
-    dListMeta_ = dev_alloc<int32_t>(4 * nc, false, nullptr);
-    dPairList_ = dev_alloc<uint16_t>(nc * (size_t)listWaves_ * (size_t)iterCap * kWave, true, nullptr);   // every entry is a tile offset at all times (k_pair_list reads ahead)
-    dNoList_ = dev_alloc<int32_t>(16, true, nullptr); dRel_ = dev_alloc<float4>((size_t)capacity_ + kWave, true, nullptr);
-    candCap_ = candCap; iterCap_ = iterCap;
-    candLds_ = candCap; iterLds_ = iterCap;          // (tightened once the builder has reported what the cells really hold: adapt_sort_interval)
+}
+
+// [nCell][candCap] candidates, [nCell][iterCap x 64] pair entries, headers.  Capacities are clipped to what the LDS of k_pair_list / k_build_lists and
+// the entry format allow.
+void ListStore::allocate(int candCapNew, int iterCapNew)
+{
+    release();
+    const StepParams& P = *P_;
+    // (k_pair_list asks for five groups of candidate entries per wave and two chunks of 8 iterations before it knows the cell: the arrays are never smaller)
+    candCapNew = std::max(kListMinCand * waves, std::min((candCapNew + 63) & ~63, kListCandMax));
+    iterCapNew = std::max(kListMinIter, std::min((iterCapNew + 7) & ~7, kListIterMax));
+    PairLists probe;
+    probe.candCap = probe.candLds = candCapNew; probe.iterCap = probe.iterLds = iterCapNew; probe.recBytes = pair_list_rec_bytes(P); probe.waves = waves;
+    while (candCapNew > kListMinCand && (pair_list_lds_bytes(P, probe) > ldsMax_ || build_lists_lds_bytes(probe) > ldsMax_))
+    {
+        candCapNew -= 64;
+        probe.candCap = probe.candLds = candCapNew;
+    }
+    while (iterCapNew > 2 * kListMinIter && build_lists_lds_bytes(probe) > ldsMax_) { iterCapNew -= 8; probe.iterCap = probe.iterLds = iterCapNew; }
+    const size_t nc = (size_t)P.nCellLocal;
+    cand = mem_.alloc<uint32_t>(nc * candCapNew, true, stream_);            // every entry is an atom index at all times
+    meta = mem_.alloc<int32_t>(4 * nc, false, stream_);
+    pairs = mem_.alloc<uint16_t>(nc * (size_t)waves * (size_t)iterCapNew * kWave, true, stream_);   // every entry is a tile offset at all times (k_pair_list reads ahead)
+    report = mem_.alloc<int32_t>(LR_COUNT, true, stream_); rel = mem_.alloc<float4>((size_t)capacity_ + kWave, true, stream_);
+    candCap = candCapNew; iterCap = iterCapNew;
+    candLds = candCapNew; iterLds = iterCapNew;          // (tightened once the builder has reported what the cells really hold: tighten / adapt)
     {   // header: -1 = no list ; second word: the cell's coordinates in the local grid (the kernels decode them with shifts)
         std::vector<int32_t> mx(4 * nc, 0);
-        const int ncy = P_.nc[1], ncz = P_.nc[2];
+        const int ncy = P.nc[1], ncz = P.nc[2];
         for (size_t c = 0; c < nc; c++)
         {
             const int cz = (int)(c % ncz), cy = (int)((c / ncz) % ncy), lx = (int)(c / ((size_t)ncy * ncz));
             mx[4 * c] = -1; mx[4 * c + 1] = lx | (cy << 10) | (cz << 20);
         }
-        HIP_CHECK(hipMemcpyAsync(dListMeta_, mx.data(), sizeof(int32_t) * 4 * nc, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(meta, mx.data(), sizeof(int32_t) * 4 * nc, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    listsOn_ = true;
-    listsValid_ = false;
+    on = true;
     if (std::getenv("AZTOT_VERBOSE"))
         std::fprintf(stderr, "aztot: pair lists for %zu cells: %d candidates, %d iterations per cell (%.1f MB), LDS %zu B (list kernel) / %zu B (builder)\n", nc, candCap, iterCap,
-                     (double)(nc * ((size_t)candCap * 4 + (size_t)iterCap * 128)) / 1e6, pair_list_lds_bytes(P_, pair_lists()), build_lists_lds_bytes(pair_lists()));
+                     (double)(nc * ((size_t)candCap * 4 + (size_t)iterCap * 128)) / 1e6, pair_list_lds_bytes(P, pair_lists()), build_lists_lds_bytes(pair_lists()));
 }
 
-// Larger lists in the middle of a run (adapt_sort_interval).  allocate_lists frees the old ones first; if the new ones do not fit the run goes on
-// without lists - the steps between two rebuilds stage every cell, as after a failed allocation at construction - instead of failing the call half-way
-// through a look (on slab ranks the other ranks would be left waiting in the look's all-reduce: ADVICE round 3).
-void Engine::regrow_lists(int candCap, int iterCap)
+void ListStore::regrow(int candCapNew, int iterCapNew)
 {
-    try { allocate_lists(candCap, iterCap); }
+    try { allocate(candCapNew, iterCapNew); }
     catch (const std::exception& e)
-    {
+    {   // (on slab ranks the other ranks would be left waiting in the look's all-reduce: ADVICE round 3)
         (void)hipGetLastError();
-        free_lists();
+        release();
         if (std::getenv("AZTOT_VERBOSE")) std::fprintf(stderr, "aztot: rank %d: no room for larger pair lists (%s): the run goes on without lists\n", rank_, e.what());
     }
 }
 
-void Engine::free_lists()
+void ListStore::release() noexcept
 {
     if (stream_) (void)hipStreamSynchronize(stream_);
-    if (dCandList_) (void)hipFree(dCandList_);
-    if (dListMeta_) (void)hipFree(dListMeta_);
-    if (dPairList_) (void)hipFree(dPairList_);
-    if (dNoList_) (void)hipFree(dNoList_);
-    if (dRel_) (void)hipFree(dRel_);
-    dRel_ = nullptr;
-    dCandList_ = nullptr; dListMeta_ = nullptr; dPairList_ = nullptr; dNoList_ = nullptr;
-    listsOn_ = false; listsValid_ = false;
+    mem_.release();
+    cand = nullptr; meta = nullptr; pairs = nullptr; report = nullptr; rel = nullptr;
+    on = false;
 }
 
-PairLists Engine::pair_lists() const
+PairLists ListStore::pair_lists() const
 {
     PairLists pl;
-    if (listsOn_)
+    if (on)
     {
-        pl.cand = dCandList_; pl.meta = dListMeta_; pl.pairs = dPairList_; pl.noList = dNoList_;
-        pl.candCap = candCap_; pl.iterCap = iterCap_; pl.candLds = candLds_; pl.iterLds = iterLds_; pl.recBytes = pair_list_rec_bytes(P_); pl.entryScale = pair_list_entry_scale(P_); pl.waves = listWaves_;
-        pl.rel = dRel_;
+        pl.cand = cand; pl.meta = meta; pl.pairs = pairs; pl.noList = report;
+        pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.entryScale = pair_list_entry_scale(*P_); pl.waves = waves;
+        pl.rel = rel;
     }
     return pl;
+}
+
+// Records of k_pair_list's LDS tile for cells of at most maxT candidates.  LDS per wave bounds the kernel's occupancy and the hardware hands LDS out in
+// blocks of 1 280 B (gfx950: 160 KiB in 128 blocks), so the tile is the largest one that costs no more blocks than the smallest one that would do
+// (largest cell + 1 % + 1): C4's largest tile of 305 candidates gives 319 records in six blocks - 21 waves per CU by LDS - where "largest + 4 % + 6" took seven.
+int ListStore::tile_records_for(int maxT) const
+{
+    constexpr size_t kLdsBlock = 1280;
+    PairLists L = pair_lists();
+    // (roomy: systems that run without the clean-up launch - a cell that outgrows the tile there costs a window of steps run again, and LDS per wave is not
+    //  what bounds a step of a few thousand cells: + 6 %)
+    const bool roomy = P_->nranks == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
+    const int need = std::max(4 * kWave, std::min(candCap, roomy ? maxT + maxT / 16 + 4 : maxT + maxT / 100 + 1));
+    L.candLds = need;
+    const size_t blocks = (pair_list_lds_bytes(*P_, L) + kLdsBlock - 1) / kLdsBlock;
+    int best = need;
+    for (int c = need + 1; c <= candCap; c++)
+    {
+        L.candLds = c;
+        if ((pair_list_lds_bytes(*P_, L) + kLdsBlock - 1) / kLdsBlock > blocks) break;
+        best = c;
+    }
+    return best;
+}
+
+// LDS per wave is what bounds the occupancy of k_pair_list: the tiles are sized from the largest cell ever recorded (+ 6 %), not from the capacity of
+// the arrays; the builder's list buffer from the longest list (+ 1/8)
+void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& iterLdsNew) const
+{
+    candLdsNew = tile_records_for(rep[LR_MAX_TILE]);
+    iterLdsNew = std::max(2 * kListMinIter, std::min(iterCap, (rep[LR_MAX_ITERS] + rep[LR_MAX_ITERS] / 8 + 2 + 7) & ~7));
+}
+
+bool ListStore::tighten(const int32_t* rep)
+{
+    if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_MAX_TILE] <= 0) return false;
+    int c, i;
+    lds_for(rep, c, i);
+    if (c >= candLds && i >= iterLds) return false;
+    candLds = std::min(candLds, c); iterLds = std::min(iterLds, i);
+    return true;
+}
+
+// Cells that keep no list are staged by the small clean-up launch: fine for a few, slow for many (stencils wider than one tile, cells of more than
+// 64 atoms) - then the plain steps go back to staging every cell.  
+ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
+{
+    Verdict v;
+    const bool frozen = debug & DBG_SHORT_LISTS;
+    if (debug & DBG_LIST_STATS)
+    {   // measurement aid: mean list length / tile size / atoms per cell over the cells recorded since the last look
+        std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates, %.2f atoms\n", (double)rep[LR_SUM_ITERS] / rep[LR_RECORDED], (double)rep[LR_SUM_CANDS] / rep[LR_RECORDED], (double)rep[LR_SUM_ATOMS] / rep[LR_RECORDED]);
+        HIP_CHECK(hipMemset(&report[LR_SUM_ITERS], 0, sizeof(int32_t) * 3));
+    }
+    // (LR_UNLISTED_NOW stays: it describes the lists in force; the maxima are all-time)
+    HIP_CHECK(hipMemsetAsync(&report[LR_UNLISTED], 0, sizeof(int32_t) * 2, stream_));
+    HIP_CHECK(hipMemsetAsync(&report[LR_TILE_FULL], 0, sizeof(int32_t) * 2, stream_));
+    const int tileFull = rep[LR_TILE_FULL], listFull = rep[LR_LIST_FULL], recorded = rep[LR_RECORDED], unlisted = rep[LR_UNLISTED];
+    if (std::getenv("AZTOT_VERBOSE"))
+        std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: tile full, %d: list full); largest tile %d of %d (LDS %d), longest list %d of %d (LDS %d)\n",
+                     recorded, unlisted, tileFull, listFull, rep[LR_MAX_TILE], candCap, candLds, rep[LR_MAX_ITERS], iterCap, iterLds);
+    // A cell that does not fit next time keeps no list for one interval (exact: the clean-up launch serves it) and is counted; then the tiles grow again.
+    int candLdsNew, iterLdsNew;
+    lds_for(rep, candLdsNew, iterLdsNew);
+    if (tileFull > 0) candLdsNew = std::min(candCap, std::max(candLdsNew, candLds + 32));
+    if (listFull > 0) iterLdsNew = std::min(iterCap, std::max(iterLdsNew, iterLds + 8));
+    if (frozen) { candLdsNew = candLds; iterLdsNew = iterLds; }
+    // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
+    // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
+    const int wWant = std::max(waves, waves_wanted((double)rep[LR_MAX_TILE], rep[LR_MAX_ITERS]));
+    if (wWant > waves && !forcedWaves_ && !frozen)
+    {   // (what was recorded describes lists that no longer exist: nothing more to decide now)
+        const int itersNew = std::max(2 * kListMinIter, ((int)(rep[LR_MAX_ITERS] * (double)waves / wWant * 1.3) + 8 + 7) & ~7);
+        const int candNew = std::max(candCap, kListMinCand * wWant);
+        waves = wWant;
+        regrow(candNew, itersNew);
+        v.rebuild = v.launchChanged = true;
+        return v;
+    }
+    const bool capFull = (tileFull > 0 && candLds == candCap) || (listFull > 0 && iterLds == iterCap);
+    // (one GPU: ANY cell that does not fit costs an engine that runs without the clean-up launch a window of steps run again, so the arrays grow at once
+    //  while they still can; slab ranks and the last growth wait until it is more than a handful)
+    if (capFull && !frozen && (double)(tileFull + listFull) > ((P_->nranks == 1 && growths < 3) ? 0.0 : 0.0005 * (double)recorded))
+    {   // the arrays themselves are too small: larger ones if the limits allow (twice), and the next step rebuilds; else - cells of more than 64 atoms
+        // never fit - the plain steps go back to staging once that is more than 2 % of the cells
+        const int candNew = tileFull > 0 ? std::min(kListCandMax, (candCap * 3 / 2 + 63) & ~63) : candCap;
+        const int itersNew = listFull > 0 ? std::min(kListIterMax, (iterCap * 2 + 7) & ~7) : iterCap;
+        v.launchChanged = true;
+        if (growths < 3 && (candNew > candCap || itersNew > iterCap)) { growths++; regrow(candNew, itersNew); v.rebuild = true; }
+    }
+    else if (candLdsNew != candLds || iterLdsNew != iterLds)
+    {
+        candLds = candLdsNew; iterLds = iterLdsNew;
+        v.launchChanged = true;               // (launch parameters are baked into the graphs)
+    }
+    if (on && (double)unlisted > 0.02 * (double)recorded && !frozen && tileFull + listFull < unlisted / 2)
+    {   // mostly cells of more than 64 atoms: no list will ever hold them
+        on = false;
+        v.launchChanged = true;
+    }
+    return v;
 }
 
 // Static per-atom tables of the bonded terms, keyed by atom id and replicated on every rank (like the reference's
@@ -850,11 +909,9 @@ void Engine::upload_initial()
             HIP_CHECK(hipMemcpy(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
         };
         alloc_up(dPhotons_, ph); alloc_up(dUvx_, ux); alloc_up(dUvy_, uy); alloc_up(dUvz_, uz);
-        for (int k = 0; k < n; k++) tmp[k] = initial_radius(opt_.seed, (uint64_t)ids[k]);
-        HIP_CHECK(hipMemcpy(A.rad, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     }
-    else if (P_.use_radii)
-    {   // a radius-dependent potential without the radiative thermostat: the radii it would have drawn (cuTemp.cu:41), never unset memory
+    if (m.tstat_type == AZTOT_TSTAT_RADI || P_.use_radii)
+    {   // (a radius-dependent potential without the radiative thermostat: the radii it would have drawn, cuTemp.cu:41, never unset memory)
         for (int k = 0; k < n; k++) tmp[k] = initial_radius(opt_.seed, (uint64_t)ids[k]);
         HIP_CHECK(hipMemcpy(A.rad, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     }
@@ -884,6 +941,7 @@ PairLaunch Engine::pair_launch(const StepParams& Q) { return PairLaunch{Q, S_, d
 void Engine::launch_pair()
 {
     const int variant = pair_variant();
+    int splitBlocks = 0;            // partial-sum slots a split or list launch has booked into (0: the plain tile grid)
     if (variant == 2)
     {
         StepParams Q = P_;
@@ -892,7 +950,7 @@ void Engine::launch_pair()
         // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
         // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
         const bool wantEnergies = stepsLeftInRun_ == 0 || (debug_ & DBG_ENERGIES_EVERY_STEP);
-        const PairLists pl = pair_lists();
+        const PairLists pl = lists_.pair_lists();
         if (overlapHalo_)
         {   // interior x-layers [2 hw, ncx - 2 hw) first; then, once the neighbours' coordinates have landed, the two runs of boundary layers
             const int plane = P_.nc[1] * P_.nc[2], hw = P_.hw[0];
@@ -921,12 +979,11 @@ void Engine::launch_pair()
                 run(lo);
                 run(hi);
             });
-            splitBlocks_ = nb;
+            splitBlocks = nb;
             overlapHalo_ = false;
         }
         else
         {
-            splitBlocks_ = 0;
             if (candMode_ != 0 && pl.cand)
             {   // lazy re-sort.  The step that rebuilds the cells first makes the lists (candidates of every tile, partners of every atom); then, like every
                 // plain step until the next rebuild, it walks them; the clean-up launch stages the cells that keep no list
@@ -937,17 +994,12 @@ void Engine::launch_pair()
                     unlistedState_ = 0;
                     if (nranks_ > 1 && !capturing_)
                     {
-                        if (!hUnlisted_)
-                        {
-                            HIP_CHECK(hipHostMalloc((void**)&hUnlisted_, sizeof(int32_t) * 4, hipHostMallocDefault));
-                            HIP_CHECK(hipEventCreateWithFlags(&evUnlisted_, hipEventDisableTiming));
-                        }
-                        HIP_CHECK(hipMemcpyAsync(hUnlisted_, dNoList_ + 2, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-                        HIP_CHECK(hipEventRecord(evUnlisted_, stream_));
+                        hUnlisted_.post(&pl.noList[LR_UNLISTED_NOW], sizeof(int32_t), stream_);
+                        hUnlisted_.mark(stream_);
                     }
                 }
-                else if (nranks_ > 1 && unlistedState_ == 0 && hUnlisted_ && !capturing_ && hipEventQuery(evUnlisted_) == hipSuccess)
-                    unlistedState_ = (hUnlisted_[0] == 0) ? 1 : 2;
+                else if (nranks_ > 1 && unlistedState_ == 0 && !capturing_ && hUnlisted_.landed())
+                    unlistedState_ = (*hUnlisted_.as<int32_t>() == 0) ? 1 : 2;
                 const bool skipCleanup = (nranks_ > 1 && unlistedState_ == 1 && candMode_ == 2 && !capturing_) || optimistic_;
                 NextStep nx;
                 nx.st = dStats_; nx.cnt = dCounts_; nx.R0 = ref_;
@@ -955,9 +1007,9 @@ void Engine::launch_pair()
                 if (fuseNext_ && fuseNextTstat_) { nx.photons = dPhotons_; nx.uvx = dUvx_; nx.uvy = dUvy_; nx.uvz = dUvz_; pairClosedStep_ = true; }
                 else nx.pendingAfter = lazyKick_ ? 1 : -1;         // this step's second half-kick is owed to the next k_integrate1_bin (a call may open
                                                                     // with a plain step, where no scan re-arms the flag)
-                timed("pair_list", [&] { splitBlocks_ = launch_pair_list(C, PairRange(), pl, nx, wantEnergies); });
+                timed("pair_list", [&] { splitBlocks = launch_pair_list(C, PairRange(), pl, nx, wantEnergies); });
                 if (!skipCleanup)
-                    timed("pair_cleanup", [&] { splitBlocks_ += launch_pair_cleanup(C, PairRange(), pl, nx); });
+                    timed("pair_cleanup", [&] { splitBlocks += launch_pair_cleanup(C, PairRange(), pl, nx); });
                 if (fuseNext_)
                 {   // the next step's positions are in the other set of coordinate arrays now
                     AtomArrays& A = cur();
@@ -975,26 +1027,26 @@ void Engine::launch_pair()
                                dCellOfSorted_, dPartials_, maxBlocks_);
         });
     if (variant < 2) fuseNow_ = false;           // only the tile kernels have the fused epilogue (cannot happen: see the constructor)
-    pairBlocksUsed_ = (variant == 2) ? (splitBlocks_ ? splitBlocks_ : pair_tile_grid(P_) * split_.n) : div_up(capacity_, kBlock);
-    blocksEver_ = std::max(blocksEver_, std::max(pairBlocksUsed_, div_up(capacity_, kBlock)) + 1);
+    notes_.pairBlocksUsed = (variant == 2) ? (splitBlocks ? splitBlocks : pair_tile_grid(P_) * split_.n) : div_up(capacity_, kBlock);
+    notes_.blocksEver = std::max(notes_.blocksEver, std::max(notes_.pairBlocksUsed, div_up(capacity_, kBlock)) + 1);
 }
 
 // slab ranks: where the boundary layers sit in the sorted arrays, as read back behind the last sort
 void Engine::take_halo_info()
 {
     if (!haloInfoPending_) return;
-    HIP_CHECK(hipEventSynchronize(evHaloInfo_));
+    hHalo_.wait();
     haloInfoPending_ = false;
-    adopt_halo_info(hHalo_);
+    adopt_halo_info(hHalo_.as<int32_t>());
 }
 
 // Behind every sort that opens an interval of plain steps the ranks tell each other how many boundary atoms they will send per plain step (k_rank_gather
-// left {send count, ghost count} per side in dHaloInfo_[5..6] and [10..11]); the right neighbour's pair lands in [12..13], the left one's in [14..15].
+// left {send count, ghost count} per side in the halo block, HaloInfo); the neighbours' pairs land behind them.
 // Fixed-size messages: this exchange cannot itself be mismatched.
 void Engine::post_count_exchange()
 {
-    const int left = (rank_ + nranks_ - 1) % nranks_, right = (rank_ + 1) % nranks_;
-    xch_->exchange_counts(left, right, dHaloInfo_ + 5, dHaloInfo_ + 10, dHaloInfo_ + 14, dHaloInfo_ + 12, 2, stream_);
+    int32_t* h = dHaloInfo_;
+    xch_->exchange_counts(left(), right(), &h[HI_SEND_LEFT], &h[HI_SEND_RIGHT], &h[HI_LEFT_SENDS], &h[HI_RIGHT_SENDS], 2, stream_);
 }
 
 // ... and before the first plain step posts a send or a receive, every rank checks that its ghost ranges are exactly as long as what the neighbours
@@ -1002,21 +1054,20 @@ void Engine::post_count_exchange()
 // shifting coordinates onto the wrong atoms
 void Engine::adopt_halo_info(const int32_t* h)
 {
-    halo_[0] = h[2]; halo_[1] = h[0]; halo_[2] = h[1]; halo_[3] = h[3]; halo_[4] = h[4];
-    const int ghostsLeft = h[2], ghostsRight = h[4] - h[3], sendLeft = h[5], sendRight = h[10];
+    halo_[0] = h[HI_OWNED_BEGIN]; halo_[1] = h[HI_LEFT_END]; halo_[2] = h[HI_RIGHT_BEGIN]; halo_[3] = h[HI_OWNED_END]; halo_[4] = h[HI_NTOTAL];
+    const int ghostsLeft = h[HI_OWNED_BEGIN], ghostsRight = h[HI_NTOTAL] - h[HI_OWNED_END], sendLeft = h[HI_SEND_LEFT], sendRight = h[HI_SEND_RIGHT];
     // (both ranks of a boundary evaluate the same two equalities, so they fail together)
-    if (h[12] != ghostsRight || h[13] != sendRight || h[14] != ghostsLeft || h[15] != sendLeft)
+    if (h[HI_RIGHT_SENDS] != ghostsRight || h[HI_RIGHT_HOLDS] != sendRight || h[HI_LEFT_SENDS] != ghostsLeft || h[HI_LEFT_HOLDS] != sendLeft)
         throw std::runtime_error("slab decomposition: the neighbours disagree about their boundary atoms (left boundary: this rank sends " + std::to_string(sendLeft) +
-                                 " and holds " + std::to_string(ghostsLeft) + " ghosts, the neighbour holds " + std::to_string(h[15]) + " and sends " + std::to_string(h[14]) +
+                                 " and holds " + std::to_string(ghostsLeft) + " ghosts, the neighbour holds " + std::to_string(h[HI_LEFT_HOLDS]) + " and sends " + std::to_string(h[HI_LEFT_SENDS]) +
                                  "; right boundary: sends " + std::to_string(sendRight) + ", holds " + std::to_string(ghostsRight) + ", the neighbour holds " +
-                                 std::to_string(h[13]) + " and sends " + std::to_string(h[12]) + "): no coordinate exchange was posted");
+                                 std::to_string(h[HI_RIGHT_HOLDS]) + " and sends " + std::to_string(h[HI_RIGHT_SENDS]) + "): no coordinate exchange was posted");
 }
 
 // one message to each x-neighbour: migrants + halo (packed by k_integrate1_bin; protocol in slab.hip.h)
 void Engine::exchange_halo()
 {
-    const int left = (rank_ + nranks_ - 1) % nranks_, right = (rank_ + 1) % nranks_;
-    timed("exchange", [&] { xch_->exchange(left, right, dMsg_[0], dMsg_[1], dMsg_[2], dMsg_[3], lay_.bytes(), stream_); });
+    timed("exchange", [&] { xch_->exchange(left(), right(), dMsg_[0], dMsg_[1], dMsg_[2], dMsg_[3], lay_.bytes(), stream_); });
     const int recvCap = 2 * (lay_.migCap + lay_.haloCap);
     timed("unpack_halo", [&] {
         hipLaunchKernelGGL(k_unpack, dim3(div_up(recvCap, kBlock)), dim3(kBlock), 0, stream_, P_, cur(), dCounts_, capacity_, lay_, dMsg_[2], dMsg_[3],
@@ -1048,7 +1099,6 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
         });
         if (nranks_ > 1)
         {   // the neighbours hold this rank's boundary atoms in the order of the last sort: only their coordinates (and radii) travel
-            const int left = (rank_ + nranks_ - 1) % nranks_, right = (rank_ + 1) % nranks_;
             take_halo_info();
             AtomArrays& A = cur();
             double* arr[4] = {A.x, A.y, A.z, A.rad};
@@ -1066,7 +1116,7 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
             }
             hipStream_t xs = overlapHalo_ ? commStream_ : stream_;
             timed("exchange_coords", [&] {
-                xch_->exchange_ranges(left, right, arr, P_.use_radii ? 4 : 3, halo_[0], halo_[1] - halo_[0], halo_[2], halo_[3] - halo_[2], 0, halo_[0], halo_[3],
+                xch_->exchange_ranges(left(), right(), arr, P_.use_radii ? 4 : 3, halo_[0], halo_[1] - halo_[0], halo_[2], halo_[3] - halo_[2], 0, halo_[0], halo_[3],
                                       halo_[4] - halo_[3], xs);
             });
             if (overlapHalo_) HIP_CHECK(hipEventRecord(evHalo_, commStream_));
@@ -1084,7 +1134,7 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
         });
     else
     {
-        HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(nCellAlloc_ + 1), stream_));
+        HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(P_.nCellLocal + 1), stream_));
         timed("bin", [&] {
             hipLaunchKernelGGL(k_integrate1_bin<STEP_BIN_ONLY>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
@@ -1109,7 +1159,7 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     timed("rank_gather", [&] {
         hipLaunchKernelGGL(k_rank_gather, dim3(gridAtoms), dim3(kBlock), 0, stream_, dCounts_, dCellStart_, dTmpId_, dTmpSrc_, dTmpCell_, cur(), oth(),
                            dCellOfSorted_, (P_.tstat == AZTOT_TSTAT_RADI || P_.use_radii || thermoTouched_) ? 2 : 0, P_, dCounts_, bonded_.idxOfId, ref_,
-                           dHaloInfo_, (listsOn_ && stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? dNoList_ + 2 : nullptr, listsOn_ ? dRel_ : nullptr);
+                           dHaloInfo_, (lists_.on && stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? &lists_.report[LR_UNLISTED_NOW] : nullptr, lists_.on ? lists_.rel : nullptr);
     });
     cur_ ^= 1;
     sinceSort_ = 0;
@@ -1118,14 +1168,9 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     if (nranks_ > 1 && lazyOn_ && lazyK_ > 1)
     {   // where the boundary layers sit in the sorted arrays: [ownedBegin, end of layer 2hw-1) goes left, [start of layer ncx-2hw, ownedEnd) goes right;
         // ghosts are [0, ownedBegin) and [ownedEnd, nTotal).  One small read-back per sort.
-        if (!hHalo_)
-        {
-            HIP_CHECK(hipHostMalloc((void**)&hHalo_, sizeof(int32_t) * 16, hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&evHaloInfo_, hipEventDisableTiming));
-        }
         post_count_exchange();
-        HIP_CHECK(hipMemcpyAsync(hHalo_, dHaloInfo_, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, stream_));
-        HIP_CHECK(hipEventRecord(evHaloInfo_, stream_));
+        hHalo_.post(dHaloInfo_, sizeof(int32_t) * HI_COUNT, stream_);
+        hHalo_.mark(stream_);
         haloInfoPending_ = true;      // (no stall here: take_halo_info waits when the numbers are needed)
     }
     }
@@ -1144,8 +1189,8 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
 void Engine::collect_and_finalize(unsigned slotMask)
 {
     timed("collect", [&] {
-        hipLaunchKernelGGL(k_collect, dim3(PS_COUNT * kCollectParts), dim3(256), 0, stream_, dPartials_, maxBlocks_, div_up(capacity_, kBlock), pairBlocksUsed_,
-                           dStage_, slotMask, ekinFromPair_ ? 1 : 0, blocksEver_);
+        hipLaunchKernelGGL(k_collect, dim3(PS_COUNT * kCollectParts), dim3(256), 0, stream_, dPartials_, maxBlocks_, div_up(capacity_, kBlock), notes_.pairBlocksUsed,
+                           dStage_, slotMask, notes_.ekinFromPair ? 1 : 0, notes_.blocksEver);
     });
     timed("finalize", [&] { hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, stream_, P_, dStats_, dStage_, slotMask); });
 }
@@ -1155,14 +1200,14 @@ void Engine::forces(bool withBonded)
     if (!failed_.empty()) throw std::runtime_error("this handle failed in an earlier call: " + failed_);
     settle();
     snap_.valid = false;
-    sinceSort_ = 1 << 30;           // a sort interval does not run on through a force call (it re-bins wrapped coordinates)
+    sinceSort_ = kNoSort;           // a sort interval does not run on through a force call (it re-bins wrapped coordinates)
     sort_and_forces(STEP_BIN_ONLY, withBonded);
-    sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false;
+    forget_interval();
     // energies of this configuration; kinetic energy and wall counters are left untouched
     unsigned mask = (1u << PS_EVDW) | (1u << PS_ECOUL) | (1u << PS_DROPPED);
     if (hasBonded_ && withBonded) mask |= (1u << PS_EBOND) | (1u << PS_EANGLE);
     collect_and_finalize(mask);
-    HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(nCellAlloc_ + 1), stream_));
+    HIP_CHECK(hipMemsetAsync(dCellCount_, 0, sizeof(int32_t) * (size_t)(P_.nCellLocal + 1), stream_));
     sync();
     check_overflow();
 }
@@ -1188,18 +1233,18 @@ void Engine::launch_step_kernels()
     const int sinceAfter = (stepMode == STEP_PLAIN) ? sinceSort_ + 1 : 0;
     const bool nextPlain = lazyOn_ && sinceAfter < lazyK_ - 1 && stepsLeftInRun_ > 0;
     {   // does this step's pair kernel also open the next step?  Only if this step walks the lists (k_pair_list and its clean-up launch carry the epilogue)
-        const bool lists = listsOn_ && lazyOn_ && lazyK_ > 1 && pair_variant() == 2;
+        const bool lists = lists_.on && lazyOn_ && lazyK_ > 1 && pair_variant() == 2;
         fuseNext_ = fuseNextOk_ && lists && nextPlain;
         // thermostat runs: only where no clean-up launch follows (it has no thermostat epilogue), on steps without equilibration scaling, never with energies on every step
         // (and one wave per cell: in the multi-wave kernels of dense systems the thermostat's registers cost the loop more than the launch saves -
         //  measured with a second radius array for case study 2's surk kernel: S40 0.076 -> 0.093 ms/step, case study 2 unchanged; not kept)
-        if (fuseNextTstat_) fuseNext_ = fuseNext_ && optimistic_ && !equil && listWaves_ == 1 && !(debug_ & DBG_ENERGIES_EVERY_STEP);
+        if (fuseNextTstat_) fuseNext_ = fuseNext_ && optimistic_ && !equil && lists_.waves == 1 && !(debug_ & DBG_ENERGIES_EVERY_STEP);
     }
     pairClosedStep_ = false;
     sort_and_forces(stepMode);
     const bool fused = fuseNow_;                 // launch_pair drops the request if the tile kernel is not the one running
     fuseNow_ = false;
-    ekinFromPair_ = fused;
+    notes_.ekinFromPair = fused;
     // radiative thermostat without equilibration scaling: nothing global happens between the second half-kick and the thermostat - one launch
     // (DBG_KICK_POST_SPLIT: two, as everywhere else)
     const bool closed = pairClosedStep_;           // (thermostat run, fused: the pair kernel has closed this step and opened the next)
@@ -1250,7 +1295,7 @@ void Engine::launch_step_kernels()
         static const double one = 1.0;
         HIP_CHECK(hipMemcpyAsync(&dStats_->vscale, &one, sizeof(double), hipMemcpyHostToDevice, stream_));
     }
-    lastStepEquil_ = equil;
+    notes_.lastStepEquil = equil;
     if (!capturing_) hostStep_++;
 }
 
@@ -1267,7 +1312,7 @@ void Engine::finish_steps()
         kickOwed_ = false;
     }
     unsigned mask = (1u << PS_COUNT) - 1u;
-    if (lastStepEquil_) mask &= ~(1u << PS_EKIN);   // k_reduce_kin / k_scale_decision own engKin then
+    if (notes_.lastStepEquil) mask &= ~(1u << PS_EKIN);   // k_reduce_kin / k_scale_decision own engKin then
     if (!(P_.nEq > 0 || P_.tstat == AZTOT_TSTAT_RADI)) mask &= ~(1u << PS_ETEMP);
     if (!hasBonded_) mask &= ~((1u << PS_EBOND) | (1u << PS_EANGLE));
     collect_and_finalize(mask);
@@ -1279,15 +1324,27 @@ void Engine::choose_optimism()
 {
     // (any size since round 4: on 1 M atoms the launch cost 6.9 us of a 123 us step - the drain and refill of the chip around a kernel that finds nothing
     //  to do -, a snapshot is 100 MB = 33 us per look, and looks are up to 256 steps apart)
-    const bool want = nranks_ == 1 && lazyOn_ && listsOn_ && lazyMeasured_ && lazyK_ > 1 && pair_variant() == 2 &&
+    const bool want = nranks_ == 1 && lazyOn_ && lists_.on && lazyMeasured_ && lazyK_ > 1 && pair_variant() == 2 &&
                       safeLooks_ == 0 && !unlistedAtLook_ && unlistedState_ != 2 && !(debug_ & DBG_ALWAYS_CLEANUP);
     if (want != optimistic_)
     {
         optimistic_ = want;
         P_.optimistic = want ? 1 : 0;
-        destroy_graphs(); graphCycle_ = 0;
+        drop_graphs();
         if (!want) snap_.valid = false;
     }
+}
+
+void Engine::copy_state(DynState from, DynState to)
+{
+    StateCopy C;
+    const auto src = double_arrays(from.A), dst = double_arrays(to.A);
+    for (int k = 0; k < 11; k++) { C.srcD[k] = *src[k]; C.dstD[k] = *dst[k]; }
+    C.srcI[0] = from.A.type; C.dstI[0] = to.A.type; C.srcI[1] = from.A.id; C.dstI[1] = to.A.id;
+    C.srcP = from.partials; C.dstP = to.partials; C.nP = (long long)PS_COUNT * maxBlocks_;
+    C.srcS[0] = (const int32_t*)from.stats; C.dstS[0] = (int32_t*)to.stats; C.nS[0] = (int)(sizeof(DevStats) / 4);
+    C.srcS[1] = (const int32_t*)from.counts; C.dstS[1] = (int32_t*)to.counts; C.nS[1] = (int)(sizeof(Counts) / 4);
+    hipLaunchKernelGGL(k_copy_state, dim3(div_up(capacity_, kBlock)), dim3(kBlock), 0, stream_, C, capacity_);
 }
 
 // Slab ranks: the dynamic state as it stands (the host has just looked and found no skin violation), device to device.  The arrays are those an exact
@@ -1296,22 +1353,10 @@ void Engine::take_snapshot()
 {
     if (!snap_.A.x)
     {
-        const size_t nAtoms = (size_t)capacity_;
-        double** d[] = {&snap_.A.x, &snap_.A.y, &snap_.A.z, &snap_.A.vx, &snap_.A.vy, &snap_.A.vz, &snap_.A.fx, &snap_.A.fy, &snap_.A.fz, &snap_.A.U, &snap_.A.rad};
-        for (auto pp : d) *pp = dev_alloc<double>(nAtoms);
-        snap_.A.type = dev_alloc<int32_t>(nAtoms); snap_.A.id = dev_alloc<int32_t>(nAtoms);
+        alloc_atoms(snap_.A, false);
         snap_.stats = dev_alloc<DevStats>(1); snap_.counts = dev_alloc<Counts>(1); snap_.partials = dev_alloc<double>((size_t)PS_COUNT * maxBlocks_);
     }
-    const AtomArrays& A = cur();
-    StateCopy C;
-    const double* src[] = {A.x, A.y, A.z, A.vx, A.vy, A.vz, A.fx, A.fy, A.fz, A.U, A.rad};
-    double* dst[] = {snap_.A.x, snap_.A.y, snap_.A.z, snap_.A.vx, snap_.A.vy, snap_.A.vz, snap_.A.fx, snap_.A.fy, snap_.A.fz, snap_.A.U, snap_.A.rad};
-    for (int k = 0; k < 11; k++) { C.srcD[k] = src[k]; C.dstD[k] = dst[k]; }
-    C.srcI[0] = A.type; C.dstI[0] = snap_.A.type; C.srcI[1] = A.id; C.dstI[1] = snap_.A.id;
-    C.srcP = dPartials_; C.dstP = snap_.partials; C.nP = (long long)PS_COUNT * maxBlocks_;
-    C.srcS[0] = (const int32_t*)dStats_; C.dstS[0] = (int32_t*)snap_.stats; C.nS[0] = (int)(sizeof(DevStats) / 4);
-    C.srcS[1] = (const int32_t*)dCounts_; C.dstS[1] = (int32_t*)snap_.counts; C.nS[1] = (int)(sizeof(Counts) / 4);
-    hipLaunchKernelGGL(k_copy_state, dim3(div_up(capacity_, kBlock)), dim3(kBlock), 0, stream_, C, capacity_);
+    copy_state(live(), snap_);
     snap_.buf = buf_state();
     snap_.hostStep = hostStep_;
     snap_.valid = true;
@@ -1323,22 +1368,13 @@ void Engine::replay_from_snapshot()
 {
     if (!snap_.valid) throw std::runtime_error("lazy re-sort on slab ranks: an atom left its cell's slack and there is no snapshot to go back to");
     sync();
-    destroy_graphs(); graphCycle_ = 0;
+    drop_graphs();
     set_buf_state(snap_.buf);
-    const AtomArrays& A = cur();
-    StateCopy C;
-    double* dst[] = {A.x, A.y, A.z, A.vx, A.vy, A.vz, A.fx, A.fy, A.fz, A.U, A.rad};
-    const double* src[] = {snap_.A.x, snap_.A.y, snap_.A.z, snap_.A.vx, snap_.A.vy, snap_.A.vz, snap_.A.fx, snap_.A.fy, snap_.A.fz, snap_.A.U, snap_.A.rad};
-    for (int k = 0; k < 11; k++) { C.srcD[k] = src[k]; C.dstD[k] = dst[k]; }
-    C.srcI[0] = snap_.A.type; C.dstI[0] = A.type; C.srcI[1] = snap_.A.id; C.dstI[1] = A.id;
-    C.srcP = snap_.partials; C.dstP = dPartials_; C.nP = (long long)PS_COUNT * maxBlocks_;
-    C.srcS[0] = (const int32_t*)snap_.stats; C.dstS[0] = (int32_t*)dStats_; C.nS[0] = (int)(sizeof(DevStats) / 4);
-    C.srcS[1] = (const int32_t*)snap_.counts; C.dstS[1] = (int32_t*)dCounts_; C.nS[1] = (int)(sizeof(Counts) / 4);
-    hipLaunchKernelGGL(k_copy_state, dim3(div_up(capacity_, kBlock)), dim3(kBlock), 0, stream_, C, capacity_);
-    sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false; preIntegrated_ = false; haloInfoPending_ = false; unlistedState_ = 0;
+    copy_state(snap_, live());
+    forget_interval(); preIntegrated_ = false; haloInfoPending_ = false; unlistedState_ = 0;
     kickOwed_ = false;
     hostStep_ = snap_.hostStep;
-    if (nranks_ > 1) { if (lazyK_ != 1) lazyK_ = 1; }
+    if (nranks_ > 1) lazyK_ = 1;
     else
     {   // one GPU: the same steps with the clean-up launch behind every k_pair_list (it stages the cells without a list and, from the step of a violation
         // on, every cell with the wider stencil)
@@ -1391,31 +1427,42 @@ bool Engine::settle_now() const
 // The end of a call, possibly deferred (settle_now): the deferred second half-kick and the statistics of the last step, the look at the sort interval
 // (a window of steps run again where it finds a skin violation that nothing had repaired on the spot), overflow checks on the state the caller will see,
 // what the next call needs.
+// A look: what the window just run has left on the device (look_sync), the sort interval and the lists from it (adapt_sort_interval), and where the window
+// turns out not to have been exact (slab ranks, all together: an atom left its slack; one GPU without the clean-up launch: that, or a cell without a
+// list) those steps again from the snapshot, exactly, then a look that cannot fail.  The two callers differ on purpose.  At the end of a call the
+// statistics of the call's last step have been reduced already, so the steps run again owe their second half-kick (kickOwed_) and their statistics once
+// more; inside a call the steps that follow pay the kick on the device (DevStats::pendingKick) and nobody has asked for statistics.  A look inside a call
+// was due, so the window doubles; the end of a call stands in for a due look only if at least half a window has gone by.
+void Engine::look(bool callEnd)
+{
+    look_sync();
+    if (!lazyOn_) return;
+    if (!adapt_sort_interval())
+    {
+        replay_from_snapshot();
+        if (callEnd)
+        {
+            kickOwed_ = lazyKick_;
+            finish_steps();
+            check_launch("step kernels (run again)");
+        }
+        look_sync();
+        if (!adapt_sort_interval()) throw std::runtime_error("lazy re-sort: a skin violation in a run that rebuilds its cells every step");
+    }
+    if (!callEnd || 2 * sinceLook_ >= lazyWindow_) lazyWindow_ = std::min(window_cap(), 2 * lazyWindow_);
+    sinceLook_ = 0;
+    if (safeLooks_ > 0) safeLooks_--;
+}
+
 void Engine::settle()
 {
     if (!unsettled_ || !failed_.empty()) return;
     unsettled_ = false;
     try
     {
-        const int windowCap = nranks_ > 1 ? 64 : 256;
         finish_steps();
         check_launch("end-of-call kernels");
-        look_sync();
-        if (lazyOn_)
-        {
-            if (!adapt_sort_interval())
-            {
-                replay_from_snapshot();
-                kickOwed_ = lazyKick_;
-                finish_steps();
-                check_launch("step kernels (run again)");
-                look_sync();
-                if (!adapt_sort_interval()) throw std::runtime_error("lazy re-sort: a skin violation in a run that rebuilds its cells every step");
-            }
-            if (2 * sinceLook_ >= lazyWindow_) lazyWindow_ = std::min(windowCap, 2 * lazyWindow_);      // (this look stands in for the one that was due)
-            sinceLook_ = 0;
-            if (safeLooks_ > 0) safeLooks_--;
-        }
+        look(true);
         // (on the state the caller will see: an optimistic window that had to be run again is inexact until it has been - ADVICE round 3)
         check_overflow();
         prepare_next_call();
@@ -1431,19 +1478,12 @@ void Engine::settle()
     catch (const std::exception& e) { mark_failed(e.what()); throw; }
 }
 
-void Engine::sync_all()
-{
-    settle();
-    sync();
-}
-
 void Engine::step_body(int nsteps)
 {
     // The sort interval is re-evaluated ("a look": a stream synchronisation and a few small read-backs, ~0.1 ms with the pipeline refill) at the end of every
     // call and, inside long calls, whenever lazyWindow_ steps have gone by since the last look - 8, 16, 32, ... then every 256 (a run that starts from rest speeds
     // up for a while: the looks are close together where that happens).  The count runs on across calls (sinceLook_), and a look is skipped when the call
     // ends within half a window anyway: a short call right behind a look - the driver's 20 steps after 5 of warm-up - pays for no look of its own.
-    const int windowCap = nranks_ > 1 ? 64 : 256;     // (a slab rank repairs a skin violation by running the window again: it looks more often)
     // (a call whose end was deferred - settle_now - and that nobody has looked at since: its second half-kick is still owed on the device, DevStats::pendingKick,
     //  and this call's first integrate kernel pays it exactly as it does between two steps of one call; its statistics were never asked for)
     kickOwed_ = false;
@@ -1452,7 +1492,6 @@ void Engine::step_body(int nsteps)
         choose_optimism();
         if (rollback_on() && !snap_.valid) take_snapshot();         // (the state as the caller left it: set_state / aztot_forces / the first call)
     }
-    bool roll = rollback_on();
     int left = nsteps;
     while (left > 0)
     {
@@ -1465,19 +1504,9 @@ void Engine::step_body(int nsteps)
         {
             if (2 * left > lazyWindow_)
             {
-                look_sync();
-                if (!adapt_sort_interval())
-                {   // (slab ranks, all together) an atom left its slack somewhere since the snapshot: those steps again, exactly, then a look that cannot fail
-                    replay_from_snapshot();
-                    look_sync();
-                    if (!adapt_sort_interval()) throw std::runtime_error("lazy re-sort: a skin violation in a run that rebuilds its cells every step");
-                }
-                if (safeLooks_ > 0) safeLooks_--;
+                look(false);
                 choose_optimism();
-                roll = rollback_on();
-                if (roll) take_snapshot();
-                sinceLook_ = 0;
-                lazyWindow_ = std::min(windowCap, 2 * lazyWindow_);
+                if (rollback_on()) take_snapshot();
             }
             else { run_steps(left); sinceLook_ += left; stepsSinceSnap_ += left; left = 0; }      // the end of the call, at most half a window away, is the look
         }
@@ -1510,19 +1539,19 @@ bool Engine::can_graph() const
 // state because kernel arguments are baked in at capture time; a graph starts with a step that sorts
 Engine::GraphSlot* Engine::graph_for_state(int cycle)
 {
-    if (graphCycle_ != cycle) { destroy_graphs(); graphCycle_ = cycle; }
+    if (graphCycle_ != cycle) { drop_graphs(); graphCycle_ = cycle; }
     const BufState now = buf_state();
     for (GraphSlot& g : graphs_)
         if (g.before.cur == now.cur && g.before.xyz[0][0] == now.xyz[0][0] && g.before.xyz[1][0] == now.xyz[1][0]) return &g;
     GraphSlot g;
     g.before = now;
     const int sinceBefore = sinceSort_;
-    const LaunchNotes notesBefore = launch_notes();      // (the capture executes nothing: what the host knows about the last EXECUTED step must survive it)
+    const LaunchNotes notesBefore = notes_;      // (the capture executes nothing: what the host knows about the last EXECUTED step must survive it)
     HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
     capturing_ = true;
     try
     {
-        sinceSort_ = 1 << 30;
+        sinceSort_ = kNoSort;
         preIntegrated_ = false;
         for (int k = 0; k < cycle; k++) { stepsLeftInRun_ = cycle - 1 - k; launch_step_kernels(); }
     }
@@ -1542,7 +1571,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     HIP_CHECK(hipStreamEndCapture(stream_, &g.graph));
     HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
     g.after = buf_state();
-    g.notes = launch_notes();         // ... of the cycle's last step
+    g.notes = notes_;         // ... of the cycle's last step
     set_buf_state(now);               // the capture itself executed nothing
     adopt_launch_notes(notesBefore);
     sinceSort_ = sinceBefore;
@@ -1563,14 +1592,14 @@ void Engine::run_steps(int nsteps)
     // With pair lists a sort interval runs on from the previous call when nothing has touched the state since (the lists are those of the arrays as they
     // stand; slab ranks: when all ranks agreed at the end of the previous call that they can - a rebuild step carries the full exchange, so they must
     // take it together); the plain steps that finish it are launched one by one, whole cycles are replayed as graphs after that.
-    const bool carryOn = lazyOn_ && (nranks_ == 1 || carryAgreed_) && listsOn_ && listsValid_ && lazyK_ > 1 && sinceSort_ < (1 << 29) && pair_variant() == 2;
-    if (!carryOn) sinceSort_ = 1 << 30;
+    const bool carryOn = lazyOn_ && (nranks_ == 1 || carryAgreed_) && lists_.on && listsValid_ && lazyK_ > 1 && sinceSort_ < kNoSort / 2 && pair_variant() == 2;
+    if (!carryOn) sinceSort_ = kNoSort;
     preIntegrated_ = false;
     while (carryOn && done < nsteps && sinceSort_ < lazyK_ - 1) { stepsLeftInRun_ = nsteps - 1 - done; launch_step_kernels(); done++; }
     const int cycle = graph_cycle();
     if (can_graph() && nsteps - done >= cycle)
     {
-        sinceSort_ = 1 << 30;
+        sinceSort_ = kNoSort;
         while (nsteps - done >= cycle)
         {
             GraphSlot* slot = graph_for_state(cycle);
@@ -1580,7 +1609,7 @@ void Engine::run_steps(int nsteps)
             rebuilds_ += (lazyOn_ && lazyK_ > 1) ? 1 : cycle;       // (a captured cycle: one sort interval, or two every-step steps)
             set_buf_state(slot->after);           // one sort per cycle (K > 1) and the coordinate-array swaps of the fused steps
             adopt_launch_notes(slot->notes);      // where the cycle's last step left its partial sums
-            sinceSort_ = 1 << 30;                 // the next cycle (or the eager remainder) starts with a sort
+            sinceSort_ = kNoSort;                 // the next cycle (or the eager remainder) starts with a sort
         }
     }
     preIntegrated_ = false;
@@ -1592,55 +1621,25 @@ void Engine::run_steps(int nsteps)
 // state the engine is in (capturing executes nothing).  (2) If the cells were rebuilt by the last step but no lists were recorded (the interval was 1
 // until now: the engine had not measured the atoms' speed yet), the lists of the arrays as they stand - so that the next call opens with plain steps
 // instead of rebuilding the same cells again.
-// Records of k_pair_list's LDS tile for cells of at most maxT candidates.  LDS per wave bounds the kernel's occupancy and the hardware hands LDS out in
-// blocks of 1 280 B (gfx950: 160 KiB in 128 blocks), so the tile is the largest one that costs no more blocks than the smallest one that would do
-// (largest cell + 1 % + 1): C4's largest tile of 305 candidates gives 319 records in six blocks - 21 waves per CU by LDS - where "largest + 4 % + 6" took seven.
-static int tile_records_for(const StepParams& P, const PairLists& base, int maxT, int candCap, bool roomy)
-{
-    constexpr size_t kLdsBlock = 1280;
-    PairLists L = base;
-    // (roomy: systems that run without the clean-up launch - a cell that outgrows the tile there costs a window of steps run again, and LDS per wave is not
-    //  what bounds a step of a few thousand cells: + 6 %)
-    const int need = std::max(4 * kWave, std::min(candCap, roomy ? maxT + maxT / 16 + 4 : maxT + maxT / 100 + 1));
-    L.candLds = need;
-    const size_t blocks = (pair_list_lds_bytes(P, L) + kLdsBlock - 1) / kLdsBlock;
-    int best = need;
-    for (int c = need + 1; c <= candCap; c++)
-    {
-        L.candLds = c;
-        if ((pair_list_lds_bytes(P, L) + kLdsBlock - 1) / kLdsBlock > blocks) break;
-        best = c;
-    }
-    return best;
-}
-
 void Engine::prepare_next_call()
 {
     if (!lazyOn_ || !lazyMeasured_) return;
-    if (listsOn_ && lazyK_ > 1 && !listsValid_ && sinceSort_ == 0 && pair_variant() == 2)
+    if (lists_.on && lazyK_ > 1 && !listsValid_ && sinceSort_ == 0 && pair_variant() == 2)
     {
-        const PairLists pl = pair_lists();
         P_.cycleStep = 0;
-        HIP_CHECK(hipMemsetAsync(dNoList_ + 2, 0, sizeof(int32_t), stream_));
-        launch_build_lists(pair_launch(P_), PairRange(), pl);
+        HIP_CHECK(hipMemsetAsync(&lists_.report[LR_UNLISTED_NOW], 0, sizeof(int32_t), stream_));
+        launch_build_lists(pair_launch(P_), PairRange(), lists_.pair_lists());
         check_launch("list building");
         sync();
-        {
-            int32_t nl[8];
-            HIP_CHECK(hipMemcpy(nl, dNoList_, sizeof(nl), hipMemcpyDeviceToHost));
-            unlistedState_ = (nl[2] == 0) ? 1 : 2;
-            // the first lists of an engine's life: size the LDS tiles from what the cells really hold right away (adapt_sort_interval does the same at
-            // every look) - the next call then walks them at full occupancy
-            if (nl[5] == 0 && nl[6] == 0 && nl[3] > 0 && !(debug_ & DBG_SHORT_LISTS))
-            {
-                const int candLds = tile_records_for(P_, pl, nl[3], candCap_, nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms);
-                const int iterLds = std::max(2 * kListMinIter, std::min(iterCap_, (nl[4] + nl[4] / 8 + 2 + 7) & ~7));
-                if (candLds < candLds_ || iterLds < iterLds_) { candLds_ = std::min(candLds_, candLds); iterLds_ = std::min(iterLds_, iterLds); destroy_graphs(); graphCycle_ = 0; }
-            }
-        }
+        int32_t rep[LR_COUNT];
+        HIP_CHECK(hipMemcpy(rep, lists_.report, sizeof(rep), hipMemcpyDeviceToHost));
+        unlistedState_ = (rep[LR_UNLISTED_NOW] == 0) ? 1 : 2;
+        // the first lists of an engine's life: size the LDS tiles from what the cells really hold right away (adapt_sort_interval does the same at
+        // every look) - the next call then walks them at full occupancy
+        if (!(debug_ & DBG_SHORT_LISTS) && lists_.tighten(rep)) drop_graphs();
         if (nranks_ > 1)
         {   // the plain steps' coordinate exchange needs to know where the boundary layers sit; with interval 1 nobody had asked (k_rank_gather left it ready)
-            int32_t h[16];
+            int32_t h[HI_COUNT];
             post_count_exchange();
             HIP_CHECK(hipStreamSynchronize(stream_));
             HIP_CHECK(hipMemcpy(h, dHaloInfo_, sizeof(h), hipMemcpyDeviceToHost));
@@ -1651,7 +1650,7 @@ void Engine::prepare_next_call()
     }
     if (nranks_ > 1)
     {   // can every rank open the next call with plain steps?
-        double cannot = (listsOn_ && listsValid_ && lazyK_ > 1 && pair_variant() == 2) ? 0.0 : 1.0;
+        double cannot = (lists_.on && listsValid_ && lazyK_ > 1 && pair_variant() == 2) ? 0.0 : 1.0;
         xch_->allreduce_sum(&cannot, 1, stream_);
         carryAgreed_ = cannot == 0.0;
     }
@@ -1669,9 +1668,9 @@ void Engine::look_sync()
 {
     if (lazyOn_)
     {
-        if (!hLook_) HIP_CHECK(hipHostMalloc(&hLook_, sizeof(Counts) + sizeof(int32_t) * 16, hipHostMallocDefault));
-        HIP_CHECK(hipMemcpyAsync(hLook_, dCounts_, sizeof(Counts), hipMemcpyDeviceToHost, stream_));
-        if (listsOn_ && dNoList_) HIP_CHECK(hipMemcpyAsync((char*)hLook_ + sizeof(Counts), dNoList_, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, stream_));
+        static_assert(sizeof(Counts) + sizeof(int32_t) * LR_COUNT <= PinnedReadback::kBytes, "the look's block holds Counts and the builder's report");
+        hLook_.post(dCounts_, sizeof(Counts), stream_);
+        if (lists_.on) hLook_.post(lists_.report, sizeof(int32_t) * LR_COUNT, stream_, sizeof(Counts));
     }
     sync();
 }
@@ -1679,78 +1678,16 @@ void Engine::look_sync()
 // (called right behind look_sync: reads what it left in pinned memory)
 bool Engine::adapt_sort_interval()
 {
-    Counts c;
-    std::memcpy(&c, hLook_, sizeof(Counts));
+    Counts c = *hLook_.as<Counts>();
     bool rebuildNeeded = false;                    // this rank's lists were re-allocated: the next step must rebuild (on every rank: rebuild steps carry the full exchange)
-    if (listsOn_)
-    {   // cells that keep no list are staged by the small clean-up launch: fine for a few, slow for many (stencils wider than one tile, cells of more than
-        // 64 atoms) - then the plain steps go back to staging every cell
-        int32_t nl[16];
-        std::memcpy(nl, (const char*)hLook_ + sizeof(Counts), sizeof(nl));
-        if ((debug_ & DBG_LIST_STATS) && nl[1] > 0)
-        {   // measurement aid: mean list length / tile size / atoms per cell over the cells recorded since the last look
-            std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates, %.2f atoms\n", (double)nl[8] / nl[1], (double)nl[9] / nl[1], (double)nl[10] / nl[1]);
-            HIP_CHECK(hipMemset(dNoList_ + 8, 0, sizeof(int32_t) * 3));
-        }
-        if (nl[1] > 0) unlistedAtLook_ = nl[0] > 0;      // (nothing recorded since the last look: what that look found still stands)
-        if (nl[1] > 0)
-        {
-            HIP_CHECK(hipMemsetAsync(dNoList_, 0, sizeof(int32_t) * 2, stream_));          // ([2] stays: it describes the lists in force; [3], [4] are all-time maxima)
-            HIP_CHECK(hipMemsetAsync(dNoList_ + 5, 0, sizeof(int32_t) * 2, stream_));
-            if (std::getenv("AZTOT_VERBOSE"))
-                std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: tile full, %d: list full); largest tile %d of %d (LDS %d), longest list %d of %d (LDS %d)\n",
-                             nl[1], nl[0], nl[5], nl[6], nl[3], candCap_, candLds_, nl[4], iterCap_, iterLds_);
-            // LDS per wave is what bounds the occupancy of k_pair_list: the tiles are sized from the largest cell ever recorded (+ 6 %), not from the
-            // capacity of the arrays.  A cell that does not fit next time keeps no list for one interval (exact: the clean-up launch serves it) and is
-            // counted; then the tiles grow again.
-            int candLds = tile_records_for(P_, pair_lists(), nl[3], candCap_, nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms);
-            int iterLds = std::max(2 * kListMinIter, std::min(iterCap_, (nl[4] + nl[4] / 8 + 2 + 7) & ~7));
-            if (nl[5] > 0) candLds = std::min(candCap_, std::max(candLds, candLds_ + 32));
-            if (nl[6] > 0) iterLds = std::min(iterCap_, std::max(iterLds, iterLds_ + 8));
-            if (debug_ & DBG_SHORT_LISTS) { candLds = candLds_; iterLds = iterLds_; }
-            // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
-            // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
-            {
-                const double tileNow = (double)nl[3] * (P_.single_lj ? 24.0 : (pair_list_tab_mode(P_) ? 25.0 : 32.0));
-                int wWant = listWaves_;
-                if (tileNow > 13.0 * 1024 || nl[4] > 96) wWant = std::max(wWant, 2);
-                if (tileNow > 26.0 * 1024 || nl[4] > 192) wWant = 4;
-                const bool forced = opt_.waves_per_cell == 1 || opt_.waves_per_cell == 2 || opt_.waves_per_cell == 4;
-                if (wWant > listWaves_ && !forced && !(debug_ & DBG_SHORT_LISTS))
-                {
-                    const int itersNew = std::max(2 * kListMinIter, ((int)(nl[4] * (double)listWaves_ / wWant * 1.3) + 8 + 7) & ~7);
-                    const int candNew = std::max(candCap_, kListMinCand * wWant);
-                    listWaves_ = wWant;
-                    destroy_graphs(); graphCycle_ = 0;
-                    regrow_lists(candNew, itersNew);
-                    rebuildNeeded = true;
-                    nl[1] = 0;                                  // (what was recorded describes lists that no longer exist: nothing more to decide now)
-                }
-            }
-            if (nl[1] > 0)
-            {
-            const bool capFull = (nl[5] > 0 && candLds_ == candCap_) || (nl[6] > 0 && iterLds_ == iterCap_);
-            // (one GPU: ANY cell that does not fit costs an engine that runs without the clean-up launch a window of steps run again, so the arrays grow at once
-            //  while they still can; slab ranks and the last growth wait until it is more than a handful)
-            if (capFull && !(debug_ & DBG_SHORT_LISTS) && (double)(nl[5] + nl[6]) > ((nranks_ == 1 && listGrowths_ < 3) ? 0.0 : 0.0005 * (double)nl[1]))
-            {   // the arrays themselves are too small: larger ones if the limits allow (twice), and the next step rebuilds; else - cells of more than 64 atoms
-                // never fit - the plain steps go back to staging once that is more than 2 % of the cells
-                const int cand = nl[5] > 0 ? std::min(kListCandMax, (candCap_ * 3 / 2 + 63) & ~63) : candCap_;
-                const int iters = nl[6] > 0 ? std::min(kListIterMax, (iterCap_ * 2 + 7) & ~7) : iterCap_;
-                destroy_graphs(); graphCycle_ = 0;
-                if (listGrowths_ < 3 && (cand > candCap_ || iters > iterCap_)) { listGrowths_++; regrow_lists(cand, iters); rebuildNeeded = true; }
-            }
-            else if (candLds != candLds_ || iterLds != iterLds_)
-            {
-                candLds_ = candLds; iterLds_ = iterLds;
-                destroy_graphs(); graphCycle_ = 0;        // (launch parameters are baked into the graphs)
-            }
-            if (listsOn_ && (double)nl[0] > 0.02 * (double)nl[1] && !(debug_ & DBG_SHORT_LISTS) && nl[5] + nl[6] < nl[0] / 2)
-            {   // mostly cells of more than 64 atoms: no list will ever hold them
-                listsOn_ = false; listsValid_ = false; destroy_graphs(); graphCycle_ = 0;
-            }
-            }
-        }
+    const int32_t* rep = hLook_.as<int32_t>(sizeof(Counts));
+    if (lists_.on && rep[LR_RECORDED] > 0)
+    {   // (nothing recorded since the last look: what that look found still stands)
+        unlistedAtLook_ = rep[LR_UNLISTED] > 0;
+        const ListStore::Verdict v = lists_.adapt(rep, debug_);
+        if (v.launchChanged) drop_graphs();
+        if (!lists_.on) listsValid_ = false;
+        rebuildNeeded = v.rebuild;
     }
     if (nranks_ > 1)
     {   // every rank must arrive at the same interval (sort steps carry the full exchange) and at the same verdict: one slot per rank + the flags
@@ -1769,29 +1706,23 @@ bool Engine::adapt_sort_interval()
         c.lazyViolatedEver = v[8] > 0.0 ? 1 : 0;
         if (c.lazyViolatedEver)
         {
-            const int32_t z = 0;
-            HIP_CHECK(hipMemcpy(&dCounts_->lazyViolatedEver, &z, sizeof(z), hipMemcpyHostToDevice));
-            if (lazyK_ != 1) { lazyK_ = 1; destroy_graphs(); graphCycle_ = 0; }
-            lazyMeasured_ = false; lazyWindow_ = 8; sinceLook_ = 0; lazyViolations_++;
+            clear_violation_flag();
+            set_interval(1);
+            void_measurement();
             lazyMargin_ = std::min(4.0, lazyMargin_ * (4.0 / 3.0));
-            if (rebuildNeeded) { sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false; }
+            if (rebuildNeeded) forget_interval();
             return false;             // every rank goes back to its snapshot (Engine::step)
         }
     }
     HIP_CHECK(hipMemsetAsync(&dCounts_->maxStep2, 0, sizeof(unsigned long long), stream_));      // (in stream order: no second round trip for the look)
-    if (rebuildNeeded) { sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false; }
+    if (rebuildNeeded) forget_interval();
     lazyMeasured_ = true;
     int K = lazyK_;
     // one GPU without the clean-up launch: a violation, or a cell that kept no list, means the steps since the last look were not exact
     const bool goBack = optimistic_ && (c.lazyViolatedEver != 0 || unlistedAtLook_);
     if (debug_ & DBG_FIXED_INTERVAL)
     {   // debug: fixed interval whatever the speeds (exercises the wider-stencil fallback); violations are only counted
-        if (c.lazyViolatedEver)
-        {
-            const int32_t z = 0;
-            HIP_CHECK(hipMemcpy(&dCounts_->lazyViolatedEver, &z, sizeof(z), hipMemcpyHostToDevice));
-            lazyViolations_++;
-        }
+        if (c.lazyViolatedEver) clear_violation_flag();
         K = lazyCap_;
     }
     else
@@ -1799,9 +1730,7 @@ bool Engine::adapt_sort_interval()
         const bool violated = c.lazyViolatedEver != 0;
         if (violated)
         {
-            const int32_t z = 0;
-            HIP_CHECK(hipMemcpy(&dCounts_->lazyViolatedEver, &z, sizeof(z), hipMemcpyHostToDevice));
-            lazyViolations_++;
+            clear_violation_flag();
             lazyMargin_ = std::min(4.0, lazyMargin_ * (4.0 / 3.0));      // the speeds are growing: more room from now on (1.15 -> 1.5 -> 2.0 -> 2.7 -> 3.6 -> 4)
         }
         int fromSpeed = -1;
@@ -1835,8 +1764,16 @@ bool Engine::adapt_sort_interval()
         if (violated) K = std::max(1, fromSpeed > 0 ? std::min(K / 2, fromSpeed) : K / 2);
         else if (fromSpeed > 0) K = fromSpeed;
     }
-    if (K != lazyK_) { lazyK_ = K; destroy_graphs(); graphCycle_ = 0; }
+    set_interval(K);
     return !goBack;
+}
+
+// a violation the host has seen and counted: Counts::lazyViolatedEver is sticky on the device until cleared here (a blocking copy: looks are rare)
+void Engine::clear_violation_flag()
+{
+    const int32_t z = 0;
+    HIP_CHECK(hipMemcpy(&dCounts_->lazyViolatedEver, &z, sizeof(z), hipMemcpyHostToDevice));
+    lazyViolations_++;
 }
 
 void Engine::check_overflow()
@@ -1852,10 +1789,7 @@ void Engine::check_overflow()
 
 void Engine::get_stats(aztot_stats& out)
 {
-    settle();
-    sync();
-    DevStats s;
-    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
+    const DevStats s = read_stats();
     // (the host decides from its own count of the steps which of them the equilibration schedule acts on: the two counts must never part)
     if (failed_.empty() && s.step != hostStep_) throw std::runtime_error("the host's step count (" + std::to_string(hostStep_) + ") and the device's (" + std::to_string(s.step) + ") differ");
     double v[24];
@@ -1880,14 +1814,14 @@ void Engine::get_stats(aztot_stats& out)
     out.n_cells = (int64_t)P_.nc[0] * P_.nc[1] * P_.nc[2];
     out.nose_chit = s.chit; out.nose_conint = s.conint;
     out.sort_interval = lazyOn_ ? lazyK_ : 1; out.sort_violations = lazyViolations_;
-    out.pair_lists = (listsOn_ && lazyOn_ && lazyK_ > 1) ? 1 : 0;
+    out.pair_lists = (lists_.on && lazyOn_ && lazyK_ > 1) ? 1 : 0;
     out.rebuilds = rebuilds_;
     out.skin = 2.0 * lazySlack_;
     out.cells_without_list = 0;
-    if (listsOn_)
+    if (lists_.on)
     {
         int32_t nl = 0;
-        HIP_CHECK(hipMemcpy(&nl, dNoList_ + 2, sizeof(nl), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&nl, &lists_.report[LR_UNLISTED_NOW], sizeof(nl), hipMemcpyDeviceToHost));
         out.cells_without_list = nl;
     }
     // pressure from the wall momentum over the window since the previous evaluation (main.cpp:143-163)
@@ -1908,10 +1842,7 @@ void Engine::species_crossings(int64_t* out, int cap)
 {
     const int n = 6 * model_.nSpec();
     if (cap < n) throw std::runtime_error("species_crossings: output array too small");
-    settle();
-    sync();
-    DevStats s;
-    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
+    const DevStats s = read_stats();
     double v[kSpecCap * 6];
     for (int k = 0; k < n; k++) v[k] = (double)s.specCross[k];
     if (nranks_ > 1) xch_->allreduce_sum(v, n, stream_);
@@ -1922,10 +1853,7 @@ void Engine::species_crossings(int64_t* out, int cap)
 // we put every atom back at its original index.  On several ranks each rank fills only the atoms it owns.
 void Engine::md_to_host(aztot_state& out)
 {
-    settle();
-    sync();
-    Counts c;
-    HIP_CHECK(hipMemcpy(&c, dCounts_, sizeof(Counts), hipMemcpyDeviceToHost));
+    const Counts c = read_counts();
     const int n = c.ownedEnd - c.ownedBegin;
     if (out.n_atoms < model_.nAt) throw std::runtime_error("md_to_host: output arrays too small");
     std::vector<int32_t> ids(std::max(n, 1));
@@ -1964,34 +1892,27 @@ void Engine::md_to_host(aztot_state& out)
 // restart support: step number + thermostat scalars (see aztot_clock)
 void Engine::get_clock(aztot_clock& out)
 {
-    settle();
-    sync();
-    DevStats s;
-    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
+    const DevStats s = read_stats();
     out.step = s.step; out.nose_chit = s.chit; out.nose_conint = s.conint; out.eng_kin = s.ekSim;
 }
 
 void Engine::set_clock(const aztot_clock& in)
 {
-    settle();
-    sync();
+    DevStats s = read_stats();
     snap_.valid = false;
-    DevStats s;
-    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
     s.step = in.step; s.stepAtSort = in.step; s.chit = in.nose_chit; s.conint = in.nose_conint; s.ekSim = in.eng_kin; s.engKin = in.eng_kin;
     s.pendingKick = 0;
     HIP_CHECK(hipMemcpy(dStats_, &s, sizeof(DevStats), hipMemcpyHostToDevice));
     lastPresStep_ = in.step;
     hostStep_ = in.step;
-    sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false;       // the next call rebuilds the cells
-    destroy_graphs();
+    forget_interval();
+    drop_graphs();
 }
 
 // read-back of the sorted cell list (cudaMD::firstAtomInCell + the id of the atom in every slot)
 int Engine::cell_table(int32_t dims[3], int32_t* cellStart, int capCells, int32_t* atomId, int capAtoms)
 {
-    settle();
-    sync();
+    sync_all();
     dims[0] = P_.ncxLocal; dims[1] = P_.nc[1]; dims[2] = P_.nc[2];
     const int nCell = P_.nCellLocal;
     if (cellStart)
@@ -2013,17 +1934,15 @@ int Engine::cell_table(int32_t dims[3], int32_t* cellStart, int capCells, int32_
 void Engine::set_state(const aztot_state& in)
 {
     if (!failed_.empty()) throw std::runtime_error("this handle failed in an earlier call: " + failed_);
-    settle();
-    sync();
+    const Counts c = read_counts();
     snap_.valid = false;
-    sinceSort_ = 1 << 30; listsValid_ = false; carryAgreed_ = false;       // the next call rebuilds the cells
+    forget_interval();
     if (in.vx || in.vy || in.vz || in.fx || in.fy || in.fz)
     {   // new velocities / forces: the interval measured on the old ones says nothing about them - every step rebuilds until the first look
-        if (lazyK_ != 1 && !(debug_ & DBG_FIXED_INTERVAL)) { lazyK_ = 1; destroy_graphs(); graphCycle_ = 0; }
-        lazyMeasured_ = false; lazyWindow_ = 8; sinceLook_ = 0; lastLookLen_ = 0.0;
+        if (!(debug_ & DBG_FIXED_INTERVAL)) set_interval(1);
+        void_measurement();
+        lastLookLen_ = 0.0;
     }
-    Counts c;
-    HIP_CHECK(hipMemcpy(&c, dCounts_, sizeof(Counts), hipMemcpyDeviceToHost));
     const int n = c.ownedEnd - c.ownedBegin;
     std::vector<int32_t> ids(std::max(n, 1));
     HIP_CHECK(hipMemcpy(ids.data(), cur().id + c.ownedBegin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
@@ -2039,7 +1958,7 @@ void Engine::set_state(const aztot_state& in)
     if ((in.U || in.radius) && !thermoTouched_)
     {   // from now on the sort carries the per-atom thermostat state along; a captured graph has the old carry mode baked in
         thermoTouched_ = true;
-        destroy_graphs();
+        drop_graphs();
     }
 }
 
@@ -2047,13 +1966,6 @@ void Engine::set_state(const aztot_state& in)
 // Radial distribution functions (rdf.hip.h).  Launched on the engine's stream between two aztot_step calls, never inside a captured step; they read
 // the current per-atom arrays and write only their own buffers.
 // ---------------------------------------------------------------------------------------------------
-void Engine::rdf_free()
-{
-    if (!rdf_.allocs.empty() && stream_) (void)hipStreamSynchronize(stream_);
-    for (void* p : rdf_.allocs) (void)hipFree(p);
-    rdf_ = RdfState();
-}
-
 int Engine::rdf_setup(double rmax, double dr, bool nuclei)
 {
     if (nranks_ > 1) throw std::runtime_error("out of scope: radial distribution functions of a slab-decomposed (multi-GPU) run are not supported");
@@ -2065,9 +1977,8 @@ int Engine::rdf_setup(double rmax, double dr, bool nuclei)
     const int nSpec = model_.nSpec(), nNucl = (int)nu.names.size();
     const long long nPairS = (long long)nSpec * (nSpec + 1) / 2, nPairN = nuclei ? (long long)nNucl * (nNucl + 1) / 2 : 0;
     if (nb * (double)(nPairS + nPairN) > (double)(1 << 28)) throw ArgError("rdf: too many bins (min(rmax, box x edge) / dr x pairs > 2^28)");
-    settle();
-    sync();
-    rdf_free();
+    sync_all();
+    rdf_ = RdfState();              // (frees the buffers of an earlier set-up: the stream has just drained)
     RdfState& R = rdf_;
     R.rmax = rmax; R.dr = dr; R.nuclei = nuclei; R.nBins = (int)nb;
     RdfGrid& G = R.grid;
@@ -2098,12 +2009,12 @@ int Engine::rdf_setup(double rmax, double dr, bool nuclei)
     R.copies = (4 * nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget) ? 4 : (nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget ? 1 : 0);
     R.blocks = std::max(1, std::min(kRdfMaxBlocks, div_up(N, kBlock)));
     const size_t n = (size_t)std::max(N, 1);
-    R.cellOf = dev_alloc<int32_t>(n, false, &R.allocs); R.rankOf = dev_alloc<int32_t>(n, false, &R.allocs); R.kind = dev_alloc<int32_t>(n, false, &R.allocs);
-    R.x = dev_alloc<double>(n, false, &R.allocs); R.y = dev_alloc<double>(n, false, &R.allocs); R.z = dev_alloc<double>(n, false, &R.allocs);
-    R.cellCount = dev_alloc<int32_t>((size_t)G.nCell, true, &R.allocs); R.cellStart = dev_alloc<int32_t>((size_t)(G.nCell + 1), false, &R.allocs);
-    R.chunkTot = dev_alloc<int32_t>((size_t)div_up(G.nCell, kScanChunk), false, &R.allocs);
-    R.histS = dev_alloc<unsigned long long>((size_t)R.nBins * nPairS, false, &R.allocs); R.histN = dev_alloc<unsigned long long>((size_t)R.nBins * std::max(nPairN, 1LL), false, &R.allocs);
-    R.scanCounts = dev_alloc<Counts>(1, true, &R.allocs); R.scanStats = dev_alloc<DevStats>(1, true, &R.allocs);
+    R.cellOf = R.mem.alloc<int32_t>(n, false, stream_); R.rankOf = R.mem.alloc<int32_t>(n, false, stream_); R.kind = R.mem.alloc<int32_t>(n, false, stream_);
+    R.x = R.mem.alloc<double>(n, false, stream_); R.y = R.mem.alloc<double>(n, false, stream_); R.z = R.mem.alloc<double>(n, false, stream_);
+    R.cellCount = R.mem.alloc<int32_t>((size_t)G.nCell, true, stream_); R.cellStart = R.mem.alloc<int32_t>((size_t)(G.nCell + 1), false, stream_);
+    R.chunkTot = R.mem.alloc<int32_t>((size_t)div_up(G.nCell, kScanChunk), false, stream_);
+    R.histS = R.mem.alloc<unsigned long long>((size_t)R.nBins * nPairS, false, stream_); R.histN = R.mem.alloc<unsigned long long>((size_t)R.nBins * std::max(nPairN, 1LL), false, stream_);
+    R.scanCounts = R.mem.alloc<Counts>(1, true, stream_); R.scanStats = R.mem.alloc<DevStats>(1, true, stream_);
     rdf_reset();
     return R.nBins;
 }

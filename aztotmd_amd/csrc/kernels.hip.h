@@ -775,6 +775,20 @@ __global__ __launch_bounds__(kBlock) void k_place(const Counts* __restrict__ cnt
     tmpCell[p] = c;
 }
 
+// The halo block of a slab rank (k_rank_gather's haloInfo): written here behind every sort, completed by the ranks' count exchange
+// (Engine::post_count_exchange: each {sends, holds} pair travels to that side's neighbour) and read by the host before the first plain step
+// (Engine::adopt_halo_info).  Positions are indices into the sorted arrays.
+enum HaloInfo : int
+{
+    HI_LEFT_END = 0,        // end of the left boundary layers: [HI_OWNED_BEGIN, HI_LEFT_END) goes to the left neighbour
+    HI_RIGHT_BEGIN = 1,     // start of the right boundary layers: [HI_RIGHT_BEGIN, HI_OWNED_END) goes to the right neighbour
+    HI_OWNED_BEGIN = 2, HI_OWNED_END = 3, HI_NTOTAL = 4,      // ghosts are [0, HI_OWNED_BEGIN) and [HI_OWNED_END, HI_NTOTAL)
+    HI_SEND_LEFT = 5, HI_GHOSTS_LEFT = 6,                     // message to the left neighbour: {what I send leftward, my left ghosts}
+    HI_SEND_RIGHT = 10, HI_GHOSTS_RIGHT = 11,                 // message to the right neighbour: {what I send rightward, my right ghosts}
+    HI_RIGHT_SENDS = 12, HI_RIGHT_HOLDS = 13,                 // the right neighbour's message: {what it sends leftward, its left ghosts}
+    HI_LEFT_SENDS = 14, HI_LEFT_HOLDS = 15,                   // the left neighbour's message: {what it sends rightward, its right ghosts}
+    HI_COUNT = 16
+};
 __global__ __launch_bounds__(kBlock) void k_rank_gather(const Counts* __restrict__ cnt, const int32_t* __restrict__ cellStart,
                                                         const int32_t* __restrict__ tmpId, const int32_t* __restrict__ tmpSrc,
                                                         const int32_t* __restrict__ tmpCell, AtomArrays src, AtomArrays dst,
@@ -793,13 +807,13 @@ __global__ __launch_bounds__(kBlock) void k_rank_gather(const Counts* __restrict
             cntOut->ownedEnd = oe;
             if (haloInfo)
             {   // what the host needs to address the boundary layers in the plain steps' coordinate exchange: one small copy instead of three
-                haloInfo[0] = cellStart[2 * P.hw[0] * plane]; haloInfo[1] = cellStart[(P.ncxLocal - 2 * P.hw[0]) * plane];
-                haloInfo[2] = ob; haloInfo[3] = oe; haloInfo[4] = cnt->nTotal;
+                haloInfo[HI_LEFT_END] = cellStart[2 * P.hw[0] * plane]; haloInfo[HI_RIGHT_BEGIN] = cellStart[(P.ncxLocal - 2 * P.hw[0]) * plane];
+                haloInfo[HI_OWNED_BEGIN] = ob; haloInfo[HI_OWNED_END] = oe; haloInfo[HI_NTOTAL] = cnt->nTotal;
                 // what this rank will send on every plain step until the next sort: to the left neighbour its first 2 hw owned layers, to the right one its
                 // last 2 hw - each neighbour must hold exactly that many ghosts on that side (checked before the first plain step: Engine::take_halo_info)
                 // (each message also carries the ghost count of that side, so that both ranks of a boundary see both numbers and arrive at the same verdict)
-                haloInfo[5] = haloInfo[0] - ob; haloInfo[6] = ob;                          // to the left neighbour: {what I send leftward, my left ghosts}
-                haloInfo[10] = oe - haloInfo[1]; haloInfo[11] = cnt->nTotal - oe;          // to the right neighbour: {what I send rightward, my right ghosts}
+                haloInfo[HI_SEND_LEFT] = haloInfo[HI_LEFT_END] - ob; haloInfo[HI_GHOSTS_LEFT] = ob;
+                haloInfo[HI_SEND_RIGHT] = oe - haloInfo[HI_RIGHT_BEGIN]; haloInfo[HI_GHOSTS_RIGHT] = cnt->nTotal - oe;
             }
         }
         else { cntOut->ownedBegin = 0; cntOut->ownedEnd = cnt->nTotal; }

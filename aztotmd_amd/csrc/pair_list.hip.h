@@ -382,7 +382,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     const int lane = threadIdx.x;
     const int per = (nCellsRun + 7) >> 3;
     const int cr = (blockIdx.x & 7) * per + (blockIdx.x >> 3);       // the mapping of k_pair_list: a cell is built and walked on the same XCD
-    if (blockIdx.x == 0 && lane == 0) atomicAdd(&L.noList[1], nCellsRun);      // cells recorded (one atomic per launch)
+    if (blockIdx.x == 0 && lane == 0) atomicAdd(&L.noList[LR_RECORDED], nCellsRun);      // cells recorded (one atomic per launch)
     if (cr >= nCellsRun) return;
     const int cell = firstCell + cr;
     const int ncy = P.nc[1], ncz = P.nc[2];
@@ -391,8 +391,8 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     const int ib = cellStart[cell], ie = cellStart[cell + 1];
     const int nthis = ie - ib;
     if (nthis == 0) { if (lane == 0) L.meta[4 * cell] = 0; return; }            // an empty cell: a list with nothing in it
-    auto no_list = [&](int why) { if (lane == 0) { L.meta[4 * cell] = -1; atomicAdd(&L.noList[0], 1); atomicAdd(&L.noList[2], 1); if (why) atomicAdd(&L.noList[why], 1); } };
-    if (nthis > kWave * W) { no_list(0); return; }                 // (W waves of k_pair_list share the cell: up to 64 atoms each)
+    auto no_list = [&](int why) { if (lane == 0) { L.meta[4 * cell] = -1; atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); if (why != LR_NONE) atomicAdd(&L.noList[why], 1); } };
+    if (nthis > kWave * W) { no_list(LR_NONE); return; }                 // (W waves of k_pair_list share the cell: up to 64 atoms each)
     const int RECB = L.entryScale;                                  // record number -> list entry (k_pair_list's mode decides: byte offset or number)
     const int candLds = L.candLds;
     const float cs0 = (float)P.csz[0], cs1 = (float)P.csz[1], cs2 = (float)P.csz[2];
@@ -516,7 +516,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
             __builtin_amdgcn_wave_barrier();
         }
     }
-    if (overflow) { no_list(5); return; }
+    if (overflow) { no_list(LR_TILE_FULL); return; }
     if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 1) return;                                 // (phase timing: staging only)
 
     // ---- candidates: written out in whole groups of 64 (k_pair_list gathers whole groups: the last one is filled with a valid atom, the cell's first)
@@ -659,10 +659,10 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         L.meta[4 * cell] = usable ? (T | (nIter << 12) | (NS << 20)) : -1;
         L.meta[4 * cell + 2] = ib;
         L.meta[4 * cell + 3] = nthis | (rcpNS << 12);
-        if (T > L.noList[3]) atomicMax(&L.noList[3], T);           // (a read first: after the first few cells nobody has a new record to report)
-        if (usable && nIter > L.noList[4]) atomicMax(&L.noList[4], nIter);
-        if (P.debugMask & DBG_LIST_STATS) { atomicAdd(&L.noList[8], nIter); atomicAdd(&L.noList[9], T); atomicAdd(&L.noList[10], nthis); }      // measurement aid (slow)
-        if (!usable) { atomicAdd(&L.noList[0], 1); atomicAdd(&L.noList[2], 1); atomicAdd(&L.noList[6], 1); }
+        if (T > L.noList[LR_MAX_TILE]) atomicMax(&L.noList[LR_MAX_TILE], T);           // (a read first: after the first few cells nobody has a new record to report)
+        if (usable && nIter > L.noList[LR_MAX_ITERS]) atomicMax(&L.noList[LR_MAX_ITERS], nIter);
+        if (P.debugMask & DBG_LIST_STATS) { atomicAdd(&L.noList[LR_SUM_ITERS], nIter); atomicAdd(&L.noList[LR_SUM_CANDS], T); atomicAdd(&L.noList[LR_SUM_ATOMS], nthis); }      // measurement aid (slow)
+        if (!usable) { atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); atomicAdd(&L.noList[LR_LIST_FULL], 1); }
     }
 }
 

@@ -411,8 +411,23 @@ __device__ __forceinline__ void tile_passes(const StepParams& P, const SpecTable
 }
 
 // Lists of the lazy re-sort, written by k_build_lists and read by k_pair_list (both in pair_list.hip.h); the clean-up launch of k_pair_tile looks at the
-// headers to find the cells that keep no list.  Sizes are per engine (Engine::allocate sizes them from density, cut-off and skin; they grow when too
+// headers to find the cells that keep no list.  Sizes are per engine (ListStore::create sizes them from density, cut-off and skin; they grow when too
 // many cells turn out not to fit).
+// The builder's report (PairLists::noList): k_build_lists counts into it, k_rank_gather clears LR_UNLISTED_NOW before a recording, the clean-up launch
+// reads that one, and the host reads all of it at every look (ListStore::adapt) and clears what is "since the last look".
+enum ListReport : int
+{
+    LR_UNLISTED = 0,        // cells recorded without a list since the host last looked
+    LR_RECORDED = 1,        // cells recorded since the host last looked
+    LR_UNLISTED_NOW = 2,    // cells without a list in the lists in force (zeroed before every recording launch)
+    LR_MAX_TILE = 3,        // largest T (candidates of a cell) ever recorded
+    LR_MAX_ITERS = 4,       // largest iteration count ever recorded
+    LR_TILE_FULL = 5,       // cells that did not fit the tile since the host last looked
+    LR_LIST_FULL = 6,       // ... that did not fit the list
+    LR_SUM_ITERS = 8, LR_SUM_CANDS = 9, LR_SUM_ATOMS = 10,     // DBG_LIST_STATS: totals over the cells recorded (three in a row: cleared together)
+    LR_COUNT = 16,
+    LR_NONE = -1            // (k_build_lists: a cell without a list that no counter of its own explains - more than 64 atoms per wave)
+};
 struct PairLists
 {
     uint32_t* cand = nullptr;      // [nCell][candCap]: atom index | image code << 26 of every candidate, in tile order; padded with valid entries to a multiple of 64
@@ -422,9 +437,7 @@ struct PairLists
                                    //          iterations than iterCap) - such cells are staged in full on every step by the clean-up launch
     uint16_t* pairs = nullptr;     // [nCell][iterCap * 64]: chunks of 8 iterations x 64 lanes; an entry is the byte offset of the candidate's record in the LDS tile
                                    //          of k_pair_list: candidate k sits in record k + 1, record 0 is the far-away dummy (entry 0 = "no candidate")
-    int32_t* noList = nullptr;     // [0], [1]: cells recorded without a list / cells recorded since the host last looked ; [2]: cells without a list in the lists in force
-                                   //      (zeroed before every recording launch) ; [3], [4]: largest T / largest iteration count ever recorded ; [5], [6]: cells that did not
-                                   //      fit the tile / the list since the host last looked ; [8..10] statistics (debug)
+    int32_t* noList = nullptr;     // [LR_COUNT]: the builder's report to the host (enum ListReport)
     int32_t candCap = 0;           // candidates per cell in `cand` (multiple of 64)
     int32_t iterCap = 0;           // list iterations per cell in `pairs` (multiple of 8)
     int32_t candLds = 0;           // candidates the LDS tiles of k_pair_list / k_build_lists hold (>= 256, <= candCap): sized by the engine from the largest T
@@ -584,7 +597,7 @@ __global__ __launch_bounds__(kWave, pair_mode_has_table(MODE) ? 3 : 1) void k_pa
     // which of this workgroup's cells need work: lane k of batch b looks at row (blockIdx >> 3) + (64 b + k) * rowStep of this XCD's share.  A full launch
     // has exactly one cell; the clean-up launch (a few workgroups that stride over all cells) takes those without a list - or, after a slack violation, all
     bool cleanupIdle = false;
-    if (onlyUnlisted && !widened) cleanupIdle = L.noList[2] == 0;       // the last recording left no cell without a list: nothing to clean up
+    if (onlyUnlisted && !widened) cleanupIdle = L.noList[LR_UNLISTED_NOW] == 0;       // the last recording left no cell without a list: nothing to clean up
     const int nSplit = CLEANUP ? 1 : Z.n;
     const int sub = (int)(blockIdx.x >> 3) & (nSplit - 1);           // which share of the stencil's columns this wave takes (all shares of a cell on one XCD)
     for (int rowBase = (int)(blockIdx.x >> 3) / nSplit; rowBase < per && !cleanupIdle; rowBase += CLEANUP ? kWave * rowStep : per)
