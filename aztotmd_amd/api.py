@@ -80,6 +80,10 @@ class _Stats(C.Structure):
                 ("pair_lists", C.c_int64), ("cells_without_list", C.c_int64), ("rebuilds", C.c_int64), ("skin", C.c_double)]
 
 
+class _CnColumn(C.Structure):
+    _fields_ = [("central", C.c_int32), ("ligand", C.c_int32), ("radius", C.c_double)]
+
+
 class _Clock(C.Structure):
     _fields_ = [("step", C.c_int64), ("nose_chit", C.c_double), ("nose_conint", C.c_double), ("eng_kin", C.c_double)]
 
@@ -95,9 +99,11 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_init_device", "aztot_free_device", "aztot_step", "aztot_sync", "aztot_forces", "aztot_get_stats", "aztot_species_crossings", "aztot_md_to_host",
            "aztot_set_state", "aztot_get_clock", "aztot_set_clock", "aztot_cell_table", "aztot_kernel_times", "aztot_reset_kernel_times", "aztot_set_profile", "aztot_comm_id_bytes", "aztot_comm_make_id", "aztot_comm_selftest", "aztot_comm_ranks",
            "aztot_init_device_slab", "aztot_rdf_setup", "aztot_rdf_sample", "aztot_rdf_reset", "aztot_rdf_shape", "aztot_rdf_counts", "aztot_rdf_values",
+           "aztot_cn_setup", "aztot_cn_sample", "aztot_cn_shape", "aztot_cn_per_atom", "aztot_cn_table",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
+CN_KINDS = {"species": 0, "nuclei": 1}        # AZTOT_CN_SPECIES (outCN rules) / AZTOT_CN_NUCLEI (ncn rules)
 
 
 class DebugBit(enum.IntFlag):
@@ -204,6 +210,11 @@ def lib():
         L.aztot_rdf_shape.argtypes = [C.c_void_p, C.c_int, _ip, _ip]
         L.aztot_rdf_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int]
         L.aztot_rdf_values.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int]
+        L.aztot_cn_setup.argtypes = [C.c_void_p, C.c_int, C.POINTER(_CnColumn), C.c_int]
+        L.aztot_cn_sample.argtypes = [C.c_void_p, C.c_int]
+        L.aztot_cn_shape.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip]
+        L.aztot_cn_per_atom.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
+        L.aztot_cn_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
         _LIB = L
     return _LIB
 
@@ -530,6 +541,39 @@ class Engine:
             names = [self.model.nucleus_name(i) for i in range(int(self.model.query("n_nuclei")[0]))]
         pairs = ["%s-%s" % (names[a], names[b]) for a in range(len(names)) for b in range(a, len(names))]
         return r[:nb], g[:nb * npair].reshape(nb, npair), pairs
+
+    # ---- coordination numbers (aztot_cn_*; the rules of the two kinds are stated in include/aztot.h) ----
+    def cn_setup(self, kind, columns):
+        """columns: [(central group, ligand group, radius)], groups being species ("species", outCN rules) or nuclei ("nuclei", ncn rules)"""
+        cols = (_CnColumn * max(len(columns), 1))()
+        for i, (a, b, r) in enumerate(columns):
+            cols[i].central, cols[i].ligand, cols[i].radius = int(a), int(b), float(r)
+        _check(lib().aztot_cn_setup(self.h, CN_KINDS[kind], cols, len(columns)))
+
+    def cn_sample(self, kind="species"):
+        """a snapshot of the current configuration: replaces the previous sample of `kind`"""
+        _check(lib().aztot_cn_sample(self.h, CN_KINDS[kind]))
+
+    def cn_shape(self, kind="species"):
+        """(n_cols, cn_min, cn_max): the columns and the first and last row of the file"""
+        nc, mn, mx = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().aztot_cn_shape(self.h, CN_KINDS[kind], C.byref(nc), C.byref(mn), C.byref(mx)))
+        return nc.value, mn.value, mx.value
+
+    def cn_per_atom(self, kind="species"):
+        """int32 [n_atoms, n_cols] in ORIGINAL atom order; -1 where the atom is not of the column's central group"""
+        n = _check(lib().aztot_cn_per_atom(self.h, CN_KINDS[kind], None, 0))
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().aztot_cn_per_atom(self.h, CN_KINDS[kind], out.ctypes.data_as(_ip), n))
+        return out[:n].reshape(self.N, -1) if n else out[:0].reshape(self.N, 0)
+
+    def cn_table(self, kind="species"):
+        """(cn_min, table[cn - cn_min, column]): central atoms of each column with each coordination number"""
+        nc, mn, mx = self.cn_shape(kind)
+        n = _check(lib().aztot_cn_table(self.h, CN_KINDS[kind], None, 0))
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        _check(lib().aztot_cn_table(self.h, CN_KINDS[kind], out.ctypes.data_as(C.POINTER(C.c_int64)), n))
+        return mn, out[:n].reshape(-1, nc)
 
     def close(self):
         if getattr(self, "h", None):

@@ -119,6 +119,8 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  bonds (at1, at2, type id per bond, after the turn of read_bondlist)  angles (central, lig1, lig2, type id)
 //  rdf (present, rmax, dr, every, out_every, nucl: the 'rdf' line of control.txt; present = 0 without one)
 //  nuclei (nucleus index of each species)  n_nuclei
+//  outcn (present, R, nCentral, nLigand, central species ids..., ligand species ids...: the 'outCN' line of control.txt; 0, 0, 0, 0 without one)
+//  ncn (n, then per line: central nucleus, ligand nucleus, R: the 'ncn' block of control.txt; n = 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -180,6 +182,17 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
         else if (k == "angles")
             for (size_t i = 0; i < m.angC.size(); i++) { v.push_back(m.angC[i]); v.push_back(m.angL1[i]); v.push_back(m.angL2[i]); v.push_back(m.angT[i]); }
         else if (k == "rdf") v = {(double)m.rdf_present, m.rdf_rmax, m.rdf_dr, (double)m.rdf_every, (double)m.rdf_out_every, (double)m.rdf_nucl};
+        else if (k == "outcn")
+        {
+            v = {(double)m.outcn_present, m.outcn_radius, (double)m.outcn_central.size(), (double)m.outcn_ligand.size()};
+            for (int j : m.outcn_central) v.push_back(j);
+            for (int j : m.outcn_ligand) v.push_back(j);
+        }
+        else if (k == "ncn")
+        {
+            v = {(double)m.ncn_central.size()};
+            for (size_t i = 0; i < m.ncn_central.size(); i++) { v.push_back(m.ncn_central[i]); v.push_back(m.ncn_ligand[i]); v.push_back(m.ncn_radius[i]); }
+        }
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -456,6 +469,58 @@ int aztot_rdf_values(aztot_md* md, int kind, double* r, double* g, int cap)
         md->eng->rdf_values(kind, rv, gv);
         if (r) std::memcpy(r, rv.data(), sizeof(double) * rv.size());
         if (g) std::memcpy(g, gv.data(), sizeof(double) * gv.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_cn_setup(aztot_md* md, int kind, const aztot_cn_column* cols, int n_cols)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->cn_setup(kind, cols, n_cols); });
+}
+
+int aztot_cn_sample(aztot_md* md, int kind)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->cn_sample(kind); });
+}
+
+int aztot_cn_shape(aztot_md* md, int kind, int* n_cols, int* cn_min, int* cn_max)
+{
+    if (!md || !md->eng || !n_cols || !cn_min || !cn_max) return fail(AZTOT_ERR_ARG, "null argument");
+    return guarded([&] { md->eng->cn_shape(kind, *n_cols, *cn_min, *cn_max); });
+}
+
+int aztot_cn_per_atom(aztot_md* md, int kind, int32_t* counts, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nc = 0, mn = 0, mx = 0;
+        md->eng->cn_shape(kind, nc, mn, mx);
+        const long long want = (long long)md->eng->n_atoms_global() * nc;
+        if (want > 0x7fffffffLL) throw ArgError("cn: atoms x columns does not fit the int this call returns");
+        need = (int)want;
+        if (!counts || cap < need) return;
+        std::vector<int32_t> v;
+        md->eng->cn_per_atom(kind, v);
+        std::memcpy(counts, v.data(), sizeof(int32_t) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_cn_table(aztot_md* md, int kind, int64_t* table, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nc = 0, mn = 0, mx = 0;
+        md->eng->cn_shape(kind, nc, mn, mx);
+        need = std::max(0, mx - mn + 1) * nc;
+        if (!table || cap < need) return;
+        std::vector<long long> v;
+        md->eng->cn_table(kind, v);
+        for (int k = 0; k < need; k++) table[k] = v[k];
     });
     return rc < 0 ? rc : need;
 }

@@ -215,4 +215,16 @@ struct RdfGrid
     int nucl[kSpecCap];         // nucleus of each species
 };
 
+// coordination numbers (cn.hip.h): how k_cn_pairs reads an atom's group and tests a pair.  The column tables ([central group][ligand group], kSpecCap x kSpecCap)
+// live in device memory and are copied into LDS by every workgroup
+constexpr int kCnLive = 15;     // columns one atom can be the central atom of (one per ligand group: MX_SPEC, defines.h:14)
+struct CnParams
+{
+    int shift;                  // group of an atom = (sKind >> shift) & 255: 0 species (outCN), 8 nucleus (ncn)
+    int inclusive;              // 1: R * R >= r2 (out_cn, out_md.cpp:434); 0: r2 < R * R (out_ncn, out_md.cpp:313,318)
+    int countSelf;              // 1: j == i is a candidate like any other (out_cn's loop over j does not skip it, out_md.cpp:429)
+    int maxLive;                // columns per atom in the per-atom counts: the largest number of columns any one group is central of
+    int nCols;
+};
+
 }  // namespace aztot

@@ -116,6 +116,13 @@ public:
     void rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts);
     void rdf_values(int kind, std::vector<double>& r, std::vector<double>& g);     // bin centres and normalised g(r), same layout
 
+    // coordination numbers (cn.hip.h; aztot_cn_* in include/aztot.h, which states the rules of the two kinds)
+    void cn_setup(int kind, const aztot_cn_column* cols, int nCols);   // (re)allocates; replaces the columns and forgets the last sample of `kind`
+    void cn_sample(int kind);                                          // a snapshot of the configuration as aztot_md_to_host would return it
+    void cn_shape(int kind, int& nCols, int& cnMin, int& cnMax);
+    void cn_per_atom(int kind, std::vector<int32_t>& out);             // [atom id][column], -1 where the atom is not the column's central
+    void cn_table(int kind, std::vector<long long>& out);              // [cn - cnMin][column]
+
 private:
     void step_body(int nsteps);
     bool settle_now() const;
@@ -165,7 +172,7 @@ private:
     hipStream_t stream_ = nullptr;
     hipStream_t commStream_ = nullptr;      // slab ranks, plain steps: the coordinate exchange runs here while the interior cells' pair forces run on stream_
     hipEvent_t evIntegrated_ = nullptr, evHalo_ = nullptr;
-    DeviceArena mem_;               // every device buffer below except the pair lists' and the RDF sampler's
+    DeviceArena mem_;               // every device buffer below except the pair lists', the RDF sampler's and the coordination numbers'
     bool profile_ = false;
     KernelTimers timers_;
     int capacity_ = 0;          // atoms that fit in the per-atom arrays (owned + ghosts + slack)
@@ -252,7 +259,20 @@ private:
     double pressure_ = 0.0;
     long long lastPresStep_ = 0;
 
-    struct RdfState
+    // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
+    // each coordination-number set-up has one (different cell edges)
+    struct GridSort
+    {
+        DeviceArena mem;
+        int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
+        double *x = nullptr, *y = nullptr, *z = nullptr;
+        Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
+        DevStats* scanStats = nullptr;
+        RdfGrid grid{};
+    };
+    void grid_setup(GridSort& S, double edge);                      // cells with an edge >= `edge`, at most about N of them; allocates the sort's buffers
+    void grid_fill(GridSort& S, const char* const timerNames[3]);   // bin, scan, place the current positions (timer names of the three stages)
+    struct RdfState : GridSort
     {
         double rmax = 0, dr = 0;
         int nBins = 0;                  // 0: not set up
@@ -260,14 +280,24 @@ private:
         long long samples = 0;
         int copies = 0;                 // LDS sub-histograms per workgroup of k_rdf_pairs (0: straight into the totals)
         int blocks = 0;
-        DeviceArena mem;
-        int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
-        double *x = nullptr, *y = nullptr, *z = nullptr;
         unsigned long long *histS = nullptr, *histN = nullptr;
-        Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
-        DevStats* scanStats = nullptr;
-        RdfGrid grid{};
     } rdf_;
+    // coordination numbers (cn.hip.h): one state per kind (AZTOT_CN_SPECIES, AZTOT_CN_NUCLEI), each a snapshot of the last sample
+    struct CnState : GridSort
+    {
+        std::vector<aztot_cn_column> cols;          // empty: not set up
+        CnParams par{};
+        int sliceShift = 0;                         // lanes per atom in k_cn_pairs = 1 << sliceShift
+        int nLive[kSpecCap] = {};                   // per central group: its columns ...
+        int colOf[kSpecCap * kCnLive] = {};         // ... and which column each of its counters is
+        bool sampled = false;
+        int cnMin = 0, cnMax = 0, rowsCap = 0;
+        int32_t *slotId = nullptr, *counts = nullptr, *range = nullptr, *dSlotOf = nullptr, *dNLive = nullptr, *dColOf = nullptr;
+        double *dR2Of = nullptr, *dRowMax = nullptr;
+        DeviceArena tableMem;                       // the table alone: it grows when a sample has more rows than any before
+        unsigned long long* table = nullptr;
+    } cn_[2];
+    CnState& cn_state(int kind, bool needSetup, bool needSample);
 
     // -- graphs: hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was
     // captured in (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue

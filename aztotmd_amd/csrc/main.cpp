@@ -8,6 +8,8 @@
 //   rdf.dat         radial distribution functions, when control.txt has 'rdf rmax dr every out_every [nucl]' (rdf_iter / copy_rdf, cuStat.cu:514-600)
 //   rdf_n.dat       the same per nucleus pair, with 'nucl' (nrdf_iter / copy_nrdf, cuStat.cu:703-790)
 //   rdf<k>.dat      running RDFs at the samples with (c - 1) % out_every == 0, k = c - 1 (and rdf_n<k>.dat)
+//   CN.dat          coordination numbers of species at the end of the run, with 'outCN R nCentral names.. nLigand names..' (out_cn, out_md.cpp:389-504; main.cu:446)
+//   nCN.dat         the same per nucleus pair, with 'ncn n' + n lines 'nucleus1 nucleus2 R'          (out_ncn, out_md.cpp:196-387; main.cu:448)
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
 // stat row (c % stat == 0, and the last step) or an RDF sample (which only reads the state: its place against the stat row of the same step does not matter).
@@ -50,6 +52,36 @@ static void write_rdf(aztot_md* md, int kind, const std::vector<std::string>& na
         std::fprintf(f, "\n");
     }
     std::fclose(f);
+}
+
+// out_cn / out_ncn layout: header "CN\t<central>-<ligand>...", rows "%d" CN then "\t%d" per column; false (and a warning) when the columns cannot be used
+static bool write_cn(aztot_md* md, int kind, const std::vector<aztot_cn_column>& cols, const std::vector<std::string>& names, const std::string& path)
+{
+    if (aztot_cn_setup(md, kind, cols.data(), (int)cols.size()) != AZTOT_OK)
+    {
+        std::fprintf(stderr, "WARNING: %s directive not usable (%s): no %s\n", kind == AZTOT_CN_SPECIES ? "outCN" : "ncn", aztot_last_error(), path.c_str());
+        return false;
+    }
+    if (aztot_cn_sample(md, kind) != AZTOT_OK) die("cn sample");
+    int nc = 0, mn = 0, mx = 0;
+    if (aztot_cn_shape(md, kind, &nc, &mn, &mx) != AZTOT_OK) die("cn shape");
+    const int need = aztot_cn_table(md, kind, nullptr, 0);
+    if (need < 0) die("cn table");
+    std::vector<int64_t> t(std::max(need, 1));
+    if (aztot_cn_table(md, kind, t.data(), need) < 0) die("cn table");
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) { std::perror(path.c_str()); std::exit(1); }
+    std::fprintf(f, "CN");
+    for (const auto& c : cols) std::fprintf(f, "\t%s-%s", names[c.central].c_str(), names[c.ligand].c_str());
+    std::fprintf(f, "\n");
+    for (int r = mn; r <= mx; r++)
+    {
+        std::fprintf(f, "%d", r);
+        for (int c = 0; c < nc; c++) std::fprintf(f, "\t%lld", (long long)t[(size_t)(r - mn) * nc + c]);
+        std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+    return true;
 }
 
 static double q1(const aztot_model* m, const char* key)
@@ -171,6 +203,34 @@ int main(int argc, char** argv)
     {
         write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf.dat");
         if (nucl) write_rdf(md, AZTOT_RDF_NUCLEI, nnames, out + "/rdf_n.dat");
+    }
+    // coordination numbers: one snapshot of the final configuration (main.cu:446-448)
+    auto query_all = [&](const char* key) {
+        const int n = aztot_model_query(model, key, nullptr, 0);
+        if (n < 0) die(key);
+        std::vector<double> v(std::max(n, 1));
+        if (aztot_model_query(model, key, v.data(), n) < 0) die(key);
+        v.resize(n);
+        return v;
+    };
+    const std::vector<double> ocn = query_all("outcn");
+    if (ocn[0] != 0.0)
+    {
+        const int nC = (int)ocn[2], nL = (int)ocn[3];
+        std::vector<aztot_cn_column> cols;
+        for (int a = 0; a < nC; a++)
+            for (int b = 0; b < nL; b++) cols.push_back({(int32_t)ocn[4 + a], (int32_t)ocn[4 + nC + b], ocn[1]});
+        write_cn(md, AZTOT_CN_SPECIES, cols, names, out + "/CN.dat");
+    }
+    const std::vector<double> ncn = query_all("ncn");
+    if (ncn[0] != 0.0)
+    {
+        std::vector<aztot_cn_column> cols;
+        for (int i = 0; i < (int)ncn[0]; i++) cols.push_back({(int32_t)ncn[1 + 3 * i], (int32_t)ncn[2 + 3 * i], ncn[3 + 3 * i]});
+        std::vector<std::string> nn;
+        const int nNucl = (int)q1(model, "n_nuclei");
+        for (int i = 0; i < nNucl; i++) { char b[16]; aztot_model_nucleus_name(model, i, b, 16); nn.push_back(b); }
+        write_cn(md, AZTOT_CN_NUCLEI, cols, nn, out + "/nCN.dat");
     }
 
     std::vector<double> x(N), y(N), z(N), vx(N), vy(N), vz(N), U(N), rad(N);

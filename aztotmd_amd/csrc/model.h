@@ -107,6 +107,13 @@ struct Model
     int rdf_present = 0;
     double rdf_rmax = 0, rdf_dr = 0;
     int rdf_every = 0, rdf_out_every = 0, rdf_nucl = 0;
+    // 'outCN R nCentral names.. nLigand names..' (read_sim, sys_init.cpp:889-932): species indices in the order the names appear
+    int outcn_present = 0;
+    double outcn_radius = 0;
+    std::vector<int32_t> outcn_central, outcn_ligand;
+    // 'ncn n' + n lines 'nucleus1 nucleus2 R' (out_ncn, out_md.cpp:219-271): nucleus indices, one directed column per line
+    std::vector<int32_t> ncn_central, ncn_ligand;
+    std::vector<double> ncn_radius;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

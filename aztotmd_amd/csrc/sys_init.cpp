@@ -380,6 +380,56 @@ void read_sim(const std::string& dir, Model& m)
         char w[64] = {0};
         if (std::fscanf(f, " %63s", w) == 1 && std::strcmp(w, "nucl") == 0) m.rdf_nucl = 1;
     }
+    // coordination numbers of species: 'outCN <radius> <nCentral> <names..> <nLigand> <names..>' (sys_init.cpp:889-932).  The reference numbers the
+    // species of each list as they appear (idCentral / idCounter), so a name given twice would leave a hole in its tables: refused here
+    m.outcn_present = 0; m.outcn_radius = 0.0; m.outcn_central.clear(); m.outcn_ligand.clear();
+    if (seek_value(f, " outCN %lf ", &m.outcn_radius))
+    {
+        m.outcn_present = 1;
+        auto read_list = [&](std::vector<int32_t>& ids, const char* code) {
+            int n = 0;
+            if (std::fscanf(f, "%d", &n) != 1 || n <= 0) fail(std::string(code) + " malformed outCN directive: a species count is missing");
+            for (int i = 0; i < n; i++)
+            {
+                char w[64] = {0};
+                const int j = std::fscanf(f, " %63s", w) == 1 ? species_by_name(m, w) : -1;
+                if (j < 0) fail(std::string(code) + " Unknown species in outCN directive!");
+                for (int k : ids) if (k == j) fail(std::string(code) + " species " + w + " is named twice in one list of the outCN directive");
+                ids.push_back(j);
+            }
+        };
+        read_list(m.outcn_central, "ERROR[201]");
+        read_list(m.outcn_ligand, "ERROR[202]");
+    }
+    // coordination numbers of nuclei: 'ncn <n>' and n lines '<nucleus1> <nucleus2> <radius>' (out_ncn, out_md.cpp:216-271, which reads them at the end of
+    // the run and goes on with an unknown name after printing the error; the same pair twice overwrites its own table entry): both refused here
+    m.ncn_central.clear(); m.ncn_ligand.clear(); m.ncn_radius.clear();
+    int nNcn = 0;
+    if (seek_value(f, " ncn %d ", &nNcn) && nNcn > 0)
+    {
+        const Nuclei nu = nuclei_of(m);
+        auto nucleus = [&](const char* w) { for (size_t j = 0; j < nu.names.size(); j++) if (nu.names[j] == w) return (int)j; return -1; };
+        for (int i = 0; i < nNcn; i++)
+        {
+            char a[64] = {0}, b[64] = {0}, line[256];
+            double r = 0.0;
+            if (std::fscanf(f, " %63s %63s %lf", a, b, &r) != 3) fail("ERROR[b010] malformed line " + std::to_string(i + 1) + " in ncn section of control file");
+            const int ia = nucleus(a), ib = nucleus(b);
+            if (ia < 0 || ib < 0)
+            {
+                std::snprintf(line, sizeof(line), "ERROR[%s] Unknown nuclei name(%s) in ncn section of control file! Line %d: %s %s %f", ia < 0 ? "b010" : "b011",
+                              ia < 0 ? a : b, i + 1, a, b, r);
+                fail(line);
+            }
+            for (size_t k = 0; k < m.ncn_central.size(); k++)
+                if (m.ncn_central[k] == ia && m.ncn_ligand[k] == ib)
+                {
+                    std::snprintf(line, sizeof(line), "ERROR[b010] nuclei pair %s %s is given twice in ncn section of control file! Line %d", a, b, i + 1);
+                    fail(line);
+                }
+            m.ncn_central.push_back(ia); m.ncn_ligand.push_back(ib); m.ncn_radius.push_back(r);
+        }
+    }
     if (!seek_value(f, " max_neigh %d ", &m.max_neigh)) m.max_neigh = 50;
 }
 

@@ -219,6 +219,12 @@ def write_input_files(case, directory, stat=200):
         else:
             f.write("elec\t%s\t%r\t%r\n" % (et, case["rReal"], case["alpha"]))
         f.write("rdf\t8.0\t0.02\t1000000\t1000000\tnucl\n")
+        if case.get("outCN"):           # (radius, [central species names], [ligand species names]): sys_init.cpp:889-932
+            R, cen, lig = case["outCN"]
+            f.write("outCN\t%r\t%d\t%s\t%d\t%s\n" % (float(R), len(cen), "\t".join(cen), len(lig), "\t".join(lig)))
+        if case.get("ncn"):             # [(nucleus1, nucleus2, radius)]: out_ncn, out_md.cpp:216-271
+            f.write("ncn %d\n" % len(case["ncn"]))
+            f.writelines("%s %s %r\n" % (a, b, float(r)) for a, b, r in case["ncn"])
         f.write("stat\t%d\n" % stat)
     if case.get("bonds") is not None and len(case["bonds"]):
         with open(os.path.join(directory, "bonds.txt"), "w") as f:       # read_bondlist, bonds.cpp:25-110

@@ -279,6 +279,53 @@ int aztot_rdf_counts(aztot_md *md, int kind, int64_t *samples, uint64_t *counts,
 /* bin centres r[n_bins] and g[bin][pair] (if cap >= n_bins * n_pairs); returns n_bins * n_pairs */
 int aztot_rdf_values(aztot_md *md, int kind, double *r, double *g, int cap);
 
+/* ---- coordination numbers: out_cn (out_md.cpp:389-504, CN.dat) and out_ncn (out_md.cpp:196-387, nCN.dat) --------------------------------------------
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.  Two kinds, which can be set up side by side and
+   differ in every detail:
+
+                      AZTOT_CN_SPECIES ('outCN R nCentral names.. nLigand names..')      AZTOT_CN_NUCLEI ('ncn n' + n lines 'nucleus1 nucleus2 R')
+     groups           species indices; all columns share one radius (sys_init.cpp:890-930)   nucleus indices (aztot_model_query "nuclei"); a radius per column
+     columns          nCentral x nLigand, central-major, in the order the names appear      the n lines in file order, each ONE directed column
+                      (out_md.cpp:465-472,481-483)                                           (central = nucleus1, ligand = nucleus2; pairInds, out_md.cpp:258)
+     test             R * R >= r2, inclusive (out_md.cpp:434)                                r2 < R * R, strict (out_md.cpp:313,318)
+     the atom itself  COUNTED when its species is central and ligand: the loop over j         never: pairs i < j only (out_md.cpp:301-304)
+                      does not skip j == i, r2 = 0 (out_md.cpp:429)
+     rows of the file CN = 0 ... largest count (mx starts at 0, out_md.cpp:392,486)          CN = min(10, smallest) ... max(0, largest) ('mn = 10; mx = 0',
+                                                                                             out_md.cpp:300); no row at all when nothing lies in between
+                                                                                             (no central atom and hence largest = 0 < 10)
+     file             header 'CN' + '\t<central>-<ligand>' per column; rows '%d' CN + '\t%d' per column = number of central atoms of the column with that CN
+
+   r2 is sqr_distance (box.cpp:297-305): differences of the positions aztot_md_to_host returns, delta_periodic (one shift by L where |d| > L / 2),
+   (dx*dx + dy*dy) + dz*dz in fp64 without contraction.  R may exceed L / 2: each pair is still tested once, through its nearest image.
+   An atom has a count in every column whose central group is its own, whatever the count; a central group without atoms gives an all-zero column.
+   Where the reference is broken rather than peculiar, we do the sane thing:
+     - out_ncn leaves the last atom out of its min / max (i < nAt - 1, out_md.cpp:301) and then indexes out[k][coords - mn] with it (out of bounds):
+       here min / max run over all atoms;
+     - a name twice in one outCN list, or the same (nucleus1, nucleus2) twice under ncn, leaves holes in the reference's tables: rejected
+       (the parser with ERROR[201] / [202] / [b010], aztot_cn_setup with AZTOT_ERR_ARG);
+     - an unknown nucleus name under ncn is used after the error message (out_md.cpp:246-262): rejected with ERROR[b010] / ERROR[b011].
+   Counts are integers and a sample is a snapshot: aztot_cn_sample replaces the previous sample of its kind, nothing accumulates.
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.
+   Errors: null handle, unknown kind, group index out of range, radius <= 0, no columns, sampling before the set-up, reading before a sample
+   -> AZTOT_ERR_ARG; a handle that failed earlier refuses to sample but can still be read. */
+enum { AZTOT_CN_SPECIES = 0, AZTOT_CN_NUCLEI = 1 };
+typedef struct aztot_cn_column
+{
+    int32_t central, ligand;     /* group indices: species (AZTOT_CN_SPECIES) or nuclei (AZTOT_CN_NUCLEI) */
+    double radius;
+} aztot_cn_column;
+/* (re)allocate for `kind`: replaces its columns and forgets its last sample; the other kind is untouched.  AZTOT_CN_SPECIES: all radii must be equal */
+int aztot_cn_setup(aztot_md *md, int kind, const aztot_cn_column *cols, int n_cols);
+/* one snapshot of the current configuration (the positions aztot_md_to_host would return) */
+int aztot_cn_sample(aztot_md *md, int kind);
+/* the rows of the file: columns, first and last CN of the last sample (cn_max < cn_min: no row) */
+int aztot_cn_shape(aztot_md *md, int kind, int *n_cols, int *cn_min, int *cn_max);
+/* counts[atom id * n_cols + column] of the last sample, -1 where the atom is not of the column's central group (if cap >= n_atoms * n_cols);
+   returns n_atoms * n_cols */
+int aztot_cn_per_atom(aztot_md *md, int kind, int32_t *counts, int cap);
+/* table[(cn - cn_min) * n_cols + column] = central atoms of the column with that CN (if cap >= rows * n_cols); returns rows * n_cols */
+int aztot_cn_table(aztot_md *md, int kind, int64_t *table, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
