@@ -100,6 +100,7 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_set_state", "aztot_get_clock", "aztot_set_clock", "aztot_cell_table", "aztot_kernel_times", "aztot_reset_kernel_times", "aztot_set_profile", "aztot_comm_id_bytes", "aztot_comm_make_id", "aztot_comm_selftest", "aztot_comm_ranks",
            "aztot_init_device_slab", "aztot_rdf_setup", "aztot_rdf_sample", "aztot_rdf_reset", "aztot_rdf_shape", "aztot_rdf_counts", "aztot_rdf_values",
            "aztot_cn_setup", "aztot_cn_sample", "aztot_cn_shape", "aztot_cn_per_atom", "aztot_cn_table",
+           "aztot_tcf_setup", "aztot_tcf_sample", "aztot_tcf_reset", "aztot_tcf_shape", "aztot_tcf_sums", "aztot_tcf_values",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
@@ -215,6 +216,12 @@ def lib():
         L.aztot_cn_shape.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip]
         L.aztot_cn_per_atom.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
         L.aztot_cn_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
+        L.aztot_tcf_setup.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.aztot_tcf_sample.argtypes = [C.c_void_p]
+        L.aztot_tcf_reset.argtypes = [C.c_void_p]
+        L.aztot_tcf_shape.argtypes = [C.c_void_p, _ip, _ip, C.POINTER(C.c_int64)]
+        L.aztot_tcf_sums.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]
+        L.aztot_tcf_values.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -574,6 +581,45 @@ class Engine:
         out = np.zeros(max(n, 1), dtype=np.int64)
         _check(lib().aztot_cn_table(self.h, CN_KINDS[kind], out.ctypes.data_as(C.POINTER(C.c_int64)), n))
         return mn, out[:n].reshape(-1, nc)
+
+    # ---- time correlation functions (aztot_tcf_*; terms, summation tree and ring of origins are stated in include/aztot.h) ----
+    def tcf_setup(self, n_origins=1, origin_every=1):
+        """a ring of n_origins time origins, one taken every origin_every samples; forgets an earlier set-up.  Returns n_lags = n_origins * origin_every"""
+        return _check(lib().aztot_tcf_setup(self.h, int(n_origins), int(origin_every)))
+
+    def tcf_sample(self):
+        """one sample of the current state: correlated with every live origin, and stored as an origin when its number is a multiple of origin_every"""
+        _check(lib().aztot_tcf_sample(self.h))
+
+    def tcf_reset(self):
+        """zero sums and counts and forget the origins: the next sample is sample 0"""
+        _check(lib().aztot_tcf_reset(self.h))
+
+    def tcf_shape(self):
+        """(n_lags, n_species, samples since the set-up or the last reset)"""
+        nl, ns, sm = C.c_int32(), C.c_int32(), C.c_int64()
+        _check(lib().aztot_tcf_shape(self.h, C.byref(nl), C.byref(ns), C.byref(sm)))
+        return nl.value, ns.value, sm.value
+
+    def _tcf_range(self, lag0, n):
+        nl, ns, _ = self.tcf_shape()
+        return (nl - lag0 if n is None else int(n)), ns
+
+    def tcf_sums(self, lag0=0, n=None):
+        """raw accumulators of lags [lag0, lag0 + n) (default: to the last): count int64 [n], msd_sum and vaf_sum fp64 [n, n_species]"""
+        n, ns = self._tcf_range(lag0, n)
+        need = _check(lib().aztot_tcf_sums(self.h, lag0, n, None, None, None, 0))
+        cnt, a, b = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(need, 1)), np.zeros(max(need, 1))
+        _check(lib().aztot_tcf_sums(self.h, lag0, n, cnt.ctypes.data_as(C.POINTER(C.c_int64)), a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), need))
+        return cnt[:n], a[:need].reshape(n, ns), b[:need].reshape(n, ns)
+
+    def tcf_values(self, lag0=0, n=None):
+        """(msd, vaf) [n, n_species]: sums / (count * atoms of the species), 0 where that is 0"""
+        n, ns = self._tcf_range(lag0, n)
+        need = _check(lib().aztot_tcf_values(self.h, lag0, n, None, None, 0))
+        a, b = np.zeros(max(need, 1)), np.zeros(max(need, 1))
+        _check(lib().aztot_tcf_values(self.h, lag0, n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), need))
+        return a[:need].reshape(n, ns), b[:need].reshape(n, ns)
 
     def close(self):
         if getattr(self, "h", None):

@@ -121,6 +121,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  nuclei (nucleus index of each species)  n_nuclei
 //  outcn (present, R, nCentral, nLigand, central species ids..., ligand species ids...: the 'outCN' line of control.txt; 0, 0, 0, 0 without one)
 //  ncn (n, then per line: central nucleus, ligand nucleus, R: the 'ncn' block of control.txt; n = 0 without one)
+//  vaf (steps between two rows of vaf.dat: the 'vaf' line of control.txt; 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -193,6 +194,7 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             v = {(double)m.ncn_central.size()};
             for (size_t i = 0; i < m.ncn_central.size(); i++) { v.push_back(m.ncn_central[i]); v.push_back(m.ncn_ligand[i]); v.push_back(m.ncn_radius[i]); }
         }
+        else if (k == "vaf") v = {(double)m.vaf};
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -521,6 +523,78 @@ int aztot_cn_table(aztot_md* md, int kind, int64_t* table, int cap)
         std::vector<long long> v;
         md->eng->cn_table(kind, v);
         for (int k = 0; k < need; k++) table[k] = v[k];
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_tcf_setup(aztot_md* md, int n_origins, int origin_every)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int nLags = 0;
+    const int rc = guarded([&] { nLags = md->eng->tcf_setup(n_origins, origin_every); });
+    return rc < 0 ? rc : nLags;
+}
+
+int aztot_tcf_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->tcf_sample(); });
+}
+
+int aztot_tcf_reset(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->tcf_reset(); });
+}
+
+int aztot_tcf_shape(aztot_md* md, int* n_lags, int* n_species, int64_t* samples)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] {
+        int nl = 0, ns = 0;
+        long long sm = 0;
+        md->eng->tcf_shape(nl, ns, sm);
+        if (n_lags) *n_lags = nl;
+        if (n_species) *n_species = ns;
+        if (samples) *samples = sm;
+    });
+}
+
+int aztot_tcf_sums(aztot_md* md, int lag0, int n, int64_t* count, double* msd_sum, double* vaf_sum, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nl = 0, ns = 0;
+        long long sm = 0;
+        md->eng->tcf_shape(nl, ns, sm);
+        const bool fill = cap >= (long long)std::max(n, 0) * ns;
+        std::vector<long long> c;
+        std::vector<double> a, b;
+        // (the range is checked whether or not anything is filled)
+        md->eng->tcf_sums(lag0, n, fill && count ? &c : nullptr, fill && msd_sum ? &a : nullptr, fill && vaf_sum ? &b : nullptr);
+        need = n * ns;
+        for (size_t k = 0; k < c.size(); k++) count[k] = c[k];
+        if (!a.empty()) std::memcpy(msd_sum, a.data(), a.size() * sizeof(double));
+        if (!b.empty()) std::memcpy(vaf_sum, b.data(), b.size() * sizeof(double));
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_tcf_values(aztot_md* md, int lag0, int n, double* msd, double* vaf, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nl = 0, ns = 0;
+        long long sm = 0;
+        md->eng->tcf_shape(nl, ns, sm);
+        if (cap < (long long)std::max(n, 0) * ns || (!msd && !vaf)) { md->eng->tcf_sums(lag0, n, nullptr, nullptr, nullptr); need = n * ns; return; }
+        std::vector<double> a, b;
+        md->eng->tcf_values(lag0, n, a, b);
+        need = n * ns;
+        if (msd && !a.empty()) std::memcpy(msd, a.data(), a.size() * sizeof(double));
+        if (vaf && !b.empty()) std::memcpy(vaf, b.data(), b.size() * sizeof(double));
     });
     return rc < 0 ? rc : need;
 }

@@ -123,6 +123,15 @@ public:
     void cn_per_atom(int kind, std::vector<int32_t>& out);             // [atom id][column], -1 where the atom is not the column's central
     void cn_table(int kind, std::vector<long long>& out);              // [cn - cnMin][column]
 
+    // time correlation functions (tcf.hip.h; aztot_tcf_* in include/aztot.h, which states the terms, the summation tree and the ring of origins)
+    int tcf_setup(int nOrigins, int originEvery);                      // (re)allocates and zeroes; returns the number of lags
+    void tcf_sample();                                                 // one sample of the state as aztot_md_to_host would return it
+    void tcf_reset();                                                  // zero sums and counts, forget the origins
+    void tcf_shape(int& nLags, int& nSpec, long long& samples);
+    // lags [lag0, lag0 + n): pairs seen and the raw sums [lag - lag0][species] (each output optional)
+    void tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf);
+    void tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf);     // sum / (count * atoms of the species), 0 where that is 0
+
 private:
     void step_body(int nsteps);
     bool settle_now() const;
@@ -172,7 +181,7 @@ private:
     hipStream_t stream_ = nullptr;
     hipStream_t commStream_ = nullptr;      // slab ranks, plain steps: the coordinate exchange runs here while the interior cells' pair forces run on stream_
     hipEvent_t evIntegrated_ = nullptr, evHalo_ = nullptr;
-    DeviceArena mem_;               // every device buffer below except the pair lists', the RDF sampler's and the coordination numbers'
+    DeviceArena mem_;               // every device buffer below except the pair lists' and the samplers' (RDF, coordination numbers, time correlation functions)
     bool profile_ = false;
     KernelTimers timers_;
     int capacity_ = 0;          // atoms that fit in the per-atom arrays (owned + ghosts + slack)
@@ -298,6 +307,19 @@ private:
         unsigned long long* table = nullptr;
     } cn_[2];
     CnState& cn_state(int kind, bool needSetup, bool needSample);
+    // time correlation functions (tcf.hip.h): the current state and a ring of origins in atom-id order, accumulators per lag
+    struct TcfState
+    {
+        int M = 0, E = 0;               // origins in the ring and samples between two of them; M == 0: not set up
+        long long samples = 0;          // since the set-up or the last reset
+        int nSpec = 0, nChunk = 0, nChunkPad = 0;
+        size_t nPad = 0;                // ids padded to a multiple of kTcfChunk
+        DeviceArena mem;
+        double *cur = nullptr, *ring = nullptr, *partials = nullptr, *msdSum = nullptr, *vafSum = nullptr;
+        int32_t* type = nullptr;        // species by atom id, -1 in the padding
+        long long* count = nullptr;
+        int n_lags() const { return M * E; }
+    } tcf_;
 
     // -- graphs: hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was
     // captured in (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue

@@ -19,6 +19,7 @@
 #include "pair_list.hip.h"
 #include "rdf.hip.h"
 #include "cn.hip.h"
+#include "tcf.hip.h"
 #include "slab.hip.h"
 
 namespace aztot {
@@ -2300,6 +2301,122 @@ void Engine::cn_table(int kind, std::vector<long long>& out)
     if (out.empty() || model_.nAt == 0) return;
     HIP_CHECK(hipStreamSynchronize(stream_));
     HIP_CHECK(hipMemcpy(out.data(), S.table, out.size() * 8, hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Time correlation functions (tcf.hip.h; terms, summation tree and ring of origins are stated in include/aztot.h).  As the other samplers: launched
+// between two aztot_step calls, reads the current per-atom arrays, writes only its own buffers, returns with the device idle.
+// ---------------------------------------------------------------------------------------------------
+int Engine::tcf_setup(int nOrigins, int originEvery)
+{
+    if (nranks_ > 1) throw std::runtime_error("out of scope: time correlation functions of a slab-decomposed (multi-GPU) run are not supported");
+    if (nOrigins < 1 || originEvery < 1) throw ArgError("tcf: n_origins and origin_every must be at least 1");
+    if ((long long)nOrigins * originEvery > AZTOT_TCF_MAX_LAGS) throw ArgError("tcf: too many lags (n_origins x origin_every > 2^24)");
+    sync_all();
+    tcf_ = TcfState();              // (frees the buffers of an earlier set-up: the stream has just drained)
+    TcfState T;
+    T.M = nOrigins; T.E = originEvery; T.nSpec = model_.nSpec();
+    T.nChunk = std::max(1, div_up(model_.nAt, kTcfChunk));
+    T.nChunkPad = 1;
+    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
+    T.nPad = (size_t)T.nChunk * kTcfChunk;
+    const size_t nAcc = (size_t)T.n_lags() * T.nSpec;
+    try
+    {
+        T.cur = T.mem.alloc<double>(6 * T.nPad, true, stream_);
+        T.ring = T.mem.alloc<double>((size_t)T.M * 6 * T.nPad, true, stream_);
+        T.type = T.mem.alloc<int32_t>(T.nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.type, 0xff, sizeof(int32_t) * T.nPad, stream_));
+        T.partials = T.mem.alloc<double>((size_t)T.M * 2 * T.nSpec * T.nChunkPad, true, stream_);
+        T.msdSum = T.mem.alloc<double>(nAcc, true, stream_); T.vafSum = T.mem.alloc<double>(nAcc, true, stream_);
+        T.count = T.mem.alloc<long long>((size_t)T.n_lags(), true, stream_);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    catch (...)
+    {   // no room: no sampler, and the handle steps on (the refused allocation must not surface at the next launch check)
+        (void)hipStreamSynchronize(stream_);
+        (void)hipGetLastError();
+        throw;
+    }
+    tcf_ = std::move(T);
+    return tcf_.n_lags();
+}
+
+void Engine::tcf_reset()
+{
+    TcfState& T = tcf_;
+    if (!T.M) throw ArgError("tcf: aztot_tcf_setup has not been called");
+    const size_t nAcc = (size_t)T.n_lags() * T.nSpec;
+    HIP_CHECK(hipMemsetAsync(T.msdSum, 0, nAcc * 8, stream_));
+    HIP_CHECK(hipMemsetAsync(T.vafSum, 0, nAcc * 8, stream_));
+    HIP_CHECK(hipMemsetAsync(T.count, 0, (size_t)T.n_lags() * 8, stream_));
+    T.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Engine::tcf_sample()
+{
+    TcfState& T = tcf_;
+    if (!T.M) throw ArgError("tcf: aztot_tcf_setup has not been called");
+    if (!failed_.empty()) throw std::runtime_error("this handle failed in an earlier call: " + failed_);
+    settle();                       // the deferred end of the last aztot_step call: positions and velocities are those aztot_md_to_host would return
+    const int N = model_.nAt;
+    const long long c = T.samples;
+    TcfBox B;
+    for (int k = 0; k < 3; k++) { B.L[k] = model_.L[k]; B.invL[k] = P_.invL[k]; B.half[k] = P_.half[k]; }
+    const bool isOrigin = c % T.E == 0;
+    double* org = isOrigin ? T.ring + (size_t)((c / T.E) % T.M) * 6 * T.nPad : nullptr;
+    if (N > 0)
+        timed("k_tcf_gather", [&] { hipLaunchKernelGGL(k_tcf_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, B, cur(), N, T.nPad, T.cur, org, T.type); });
+    const int nLive = (int)std::min<long long>(c / T.E + 1, T.M);
+    timed("k_tcf_correlate", [&] {
+        hipLaunchKernelGGL(k_tcf_correlate, dim3(T.nChunk), dim3(kBlock), 0, stream_, B, T.nSpec, T.nPad, T.nChunkPad, nLive, T.cur, T.type, T.ring, T.partials);
+    });
+    timed("k_tcf_fold", [&] {
+        hipLaunchKernelGGL(k_tcf_fold, dim3(nLive * 2 * T.nSpec), dim3(kBlock), 0, stream_, T.nSpec, T.nChunkPad, c, T.E, T.M, T.partials, T.count, T.msdSum, T.vafSum);
+    });
+    check_launch("tcf kernels");
+    T.samples++;
+    // leave the engine settled AND drained, as rdf_sample does (and for its reason: the next aztot_step must open on an idle stream)
+    sync();
+}
+
+void Engine::tcf_shape(int& nLags, int& nSpec, long long& samples)
+{
+    if (!tcf_.M) throw ArgError("tcf: aztot_tcf_setup has not been called");
+    nLags = tcf_.n_lags(); nSpec = tcf_.nSpec; samples = tcf_.samples;
+}
+
+void Engine::tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf)
+{
+    const TcfState& T = tcf_;
+    if (!T.M) throw ArgError("tcf: aztot_tcf_setup has not been called");
+    if (lag0 < 0 || n < 0 || (long long)lag0 + n > T.n_lags()) throw ArgError("tcf: lag range outside [0, n_lags)");
+    const size_t nv = (size_t)n * T.nSpec, at = (size_t)lag0 * T.nSpec;
+    if (count) count->assign((size_t)n, 0);
+    if (msd) msd->assign(nv, 0.0);
+    if (vaf) vaf->assign(nv, 0.0);
+    if (n == 0) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (count) HIP_CHECK(hipMemcpy(count->data(), T.count + lag0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (msd && nv) HIP_CHECK(hipMemcpy(msd->data(), T.msdSum + at, nv * 8, hipMemcpyDeviceToHost));
+    if (vaf && nv) HIP_CHECK(hipMemcpy(vaf->data(), T.vafSum + at, nv * 8, hipMemcpyDeviceToHost));
+}
+
+// displ / number and vaf / number of the reference (out_md.cpp:120,577-579), over all pairs of a lag: sum / (count * n_s); 0 where count * n_s == 0
+void Engine::tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf)
+{
+    std::vector<long long> count;
+    tcf_sums(lag0, n, &count, &msd, &vaf);
+    const int nSpec = tcf_.nSpec;
+    for (int l = 0; l < n; l++)
+        for (int s = 0; s < nSpec; s++)
+        {
+            const long long w = count[l] * (long long)model_.species[s].number;
+            const size_t e = (size_t)l * nSpec + s;
+            msd[e] = w ? msd[e] / (double)w : 0.0;
+            vaf[e] = w ? vaf[e] / (double)w : 0.0;
+        }
 }
 
 }  // namespace aztot

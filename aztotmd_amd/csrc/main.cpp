@@ -10,9 +10,22 @@
 //   rdf<k>.dat      running RDFs at the samples with (c - 1) % out_every == 0, k = c - 1 (and rdf_n<k>.dat)
 //   CN.dat          coordination numbers of species at the end of the run, with 'outCN R nCentral names.. nLigand names..' (out_cn, out_md.cpp:389-504; main.cu:446)
 //   nCN.dat         the same per nucleus pair, with 'ncn n' + n lines 'nucleus1 nucleus2 R'          (out_ncn, out_md.cpp:196-387; main.cu:448)
+//   displ.dat       with 'vaf n' too: mean-square displacement per species from the time origin, one row per stat row: the '<name>-msd' columns of the serial program's msd.dat
+//                   (msd_header / out_msd, out_md.cpp:19-29,89-124; main.cpp:163).  msd.dat itself follows the GPU program (wall-crossing counters)
+//   vaf.dat         velocity autocorrelation per species, with 'vaf n': a row every n steps after the equilibration (vaf_header / vaf_info, out_md.cpp:547-582;
+//                   main.cpp:71-75,115-117)
+// Both files are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
+// MSD / VAF schedule: ONE sampler (aztot_tcf_*) with a single origin, n_origins = 1 and origin_every = the number of samples the run takes.  Sample 0 is the
+// initial state (x0s, sys_init.cpp:545); a step c < nequil that writes a stat row samples and writes a displ.dat row; at c == nequil (> 0) the sampler is
+// reset and the state becomes the new origin (main.cpp:126-136; a stat row of that step follows and shows 0, as in the reference, which replaces x0s
+// before out_msd runs); at c > nequil a sample is taken when c writes a stat row (displ.dat) or c % vaf == 0 (vaf.dat), one sample serving both.
+// Deviations from the serial program: the time column is aztot_stats.time = c * dt (the serial vaf_info prints the time of the step before, because
+// calc_chars advances it afterwards, main.cpp:117,142); with 'nequil 0' the VAF origin is the initial state (the reference never calls vaf_init then and
+// reads unset memory); an empty species prints 0 (the reference's MSD prints 0 / 0).
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
-// stat row (c % stat == 0, and the last step) or an RDF sample (which only reads the state: its place against the stat row of the same step does not matter).
+// stat row (c % stat == 0, and the last step), an RDF sample (which only reads the state: its place against the stat row of the same step does not matter),
+// the end of the equilibration or a vaf.dat row.
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -82,6 +95,14 @@ static bool write_cn(aztot_md* md, int kind, const std::vector<aztot_cn_column>&
     }
     std::fclose(f);
     return true;
+}
+
+// "<time>\t<step>" + "\t%f" per species: the row layout of out_msd's MSD columns and of vaf_info
+static void write_tcf_row(FILE* f, double time, int step, const std::vector<double>& v)
+{
+    std::fprintf(f, "%f\t%d", time, step);
+    for (double e : v) std::fprintf(f, "\t%f", e);
+    std::fprintf(f, "\n");
 }
 
 static double q1(const aztot_model* m, const char* key)
@@ -162,6 +183,34 @@ int main(int argc, char** argv)
         for (int i = 0; i < nn; i++) { char b[16]; aztot_model_nucleus_name(model, i, b, 16); nnames.push_back(b); }
     }
     auto rdf_due = [&](int c) { return rdfOn && c >= 1 && (c - 1) % rdfEvery == 0; };
+    // mean-square displacement and velocity autocorrelation: one sampler with a single origin (see the header comment)
+    const int nEq = (int)q1(model, "nequil"), vafEvery = (int)q1(model, "vaf");
+    auto stat_row = [&](int c) { return c % stat == 0 || c == nStep; };
+    auto vaf_row = [&](int c) { return vafEvery > 0 && c > nEq && c % vafEvery == 0; };
+    auto tcf_due = [&](int c) { return c == 0 || (nEq > 0 && c == nEq) || stat_row(c) || vaf_row(c); };
+    int tcfSamples = 0;
+    for (int c = 0; c <= nStep; c++) tcfSamples += tcf_due(c) ? 1 : 0;
+    bool tcfOn = vafEvery > 0;
+    if (tcfOn && (aztot_tcf_setup(md, 1, tcfSamples) < 0 || aztot_tcf_sample(md) != AZTOT_OK))
+    {
+        std::fprintf(stderr, "WARNING: no room for the MSD / VAF sampler (%s): no displ.dat, no vaf.dat\n", aztot_last_error());
+        tcfOn = false;
+    }
+    FILE *df = nullptr, *vf = nullptr;
+    if (tcfOn)
+    {
+        df = std::fopen((out + "/displ.dat").c_str(), "w");
+        if (!df) { std::perror("displ.dat"); return 1; }
+        std::fprintf(df, "Time\tStep");
+        for (int j = 0; j < nSpec; j++) std::fprintf(df, "\t%s-msd", names[j].c_str());
+        std::fprintf(df, "\n");
+        vf = std::fopen((out + "/vaf.dat").c_str(), "w");
+        if (!vf) { std::perror("vaf.dat"); return 1; }
+        std::fprintf(vf, "time,ps\tiStep");
+        for (int j = 0; j < nSpec; j++) std::fprintf(vf, "\t%s", names[j].c_str());
+        std::fprintf(vf, "\n");
+    }
+    std::vector<double> msdRow(std::max(nSpec, 1)), vafRow(std::max(nSpec, 1));
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
@@ -170,6 +219,11 @@ int main(int argc, char** argv)
         {   // next sample: the smallest c > done with (c - 1) % every == 0
             const int next = done < 1 ? 1 : done + 1 + (rdfEvery - (done % rdfEvery)) % rdfEvery;
             n = std::min(n, next - done);
+        }
+        if (tcfOn)
+        {
+            if (done < nEq) n = std::min(n, nEq - done);
+            n = std::min(n, (std::max(done, nEq) / vafEvery + 1) * vafEvery - done);
         }
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
@@ -182,8 +236,22 @@ int main(int argc, char** argv)
                 if (nucl) write_rdf(md, AZTOT_RDF_NUCLEI, nnames, out + "/rdf_n" + std::to_string(done - 1) + ".dat");
             }
         }
-        if (done % stat != 0 && done != nStep) continue;
+        const bool tcfNow = tcfOn && tcf_due(done);
+        if (!stat_row(done) && !tcfNow) continue;
         if (aztot_get_stats(md, &st) != AZTOT_OK) die("stats");
+        if (tcfNow)
+        {
+            if (nEq > 0 && done == nEq && aztot_tcf_reset(md) != AZTOT_OK) die("tcf reset");
+            if (aztot_tcf_sample(md) != AZTOT_OK) die("tcf sample");
+            int64_t taken = 0;
+            if (aztot_tcf_shape(md, nullptr, nullptr, &taken) != AZTOT_OK) die("tcf shape");
+            // one origin, sample 0: the lag of this sample is its number
+            if (aztot_tcf_values(md, (int)taken - 1, 1, msdRow.data(), vafRow.data(), nSpec) < 0) die("tcf values");
+            msdRow.resize(nSpec); vafRow.resize(nSpec);
+            if (stat_row(done)) write_tcf_row(df, st.time, (int)st.step, msdRow);
+            if (vaf_row(done)) write_tcf_row(vf, st.time, (int)st.step, vafRow);
+        }
+        if (!stat_row(done)) continue;
         std::fprintf(sf, "%f\t%d\t%f\t%f\t%f\t%f\t%f", st.time, (int)st.step, st.engTot, st.engKin, st.engVdW, st.engCoul, st.engCoulRec);
         if (radi) std::fprintf(sf, "\t%f", st.engTemp);
         if (hasB) std::fprintf(sf, "\t%f", st.engBond);
@@ -199,6 +267,8 @@ int main(int argc, char** argv)
     }
     std::fclose(sf);
     std::fclose(mf);
+    if (df) std::fclose(df);
+    if (vf) std::fclose(vf);
     if (rdfOn)
     {
         write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf.dat");

@@ -114,6 +114,8 @@ struct Model
     // 'ncn n' + n lines 'nucleus1 nucleus2 R' (out_ncn, out_md.cpp:219-271): nucleus indices, one directed column per line
     std::vector<int32_t> ncn_central, ncn_ligand;
     std::vector<double> ncn_radius;
+    // 'vaf n' (read_sim, sys_init.cpp:883-884): steps between two rows of vaf.dat after the equilibration; 0: off
+    int vaf = 0;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

@@ -371,6 +371,9 @@ void read_sim(const std::string& dir, Model& m)
 
     if (seek_value(f, " cell_list %lf ", &m.desired_cell_size)) m.use_clist = 1;   // sys_init.cpp:862-865
     if (!seek_value(f, " stat %d ", &m.stat)) m.stat = 1000;
+    // velocity autocorrelation function: 'vaf n', a row of vaf.dat every n steps after the equilibration (sys_init.cpp:883-884); 0 or no line: off
+    m.vaf = seek_int_or(f, " vaf %d ", 0);
+    if (m.vaf < 0) fail("ERROR[414] negative period in 'vaf' directive of control.txt");
     // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
     m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
     if (seek_value(f, " rdf %lf ", &m.rdf_rmax))

@@ -225,6 +225,8 @@ def write_input_files(case, directory, stat=200):
         if case.get("ncn"):             # [(nucleus1, nucleus2, radius)]: out_ncn, out_md.cpp:216-271
             f.write("ncn %d\n" % len(case["ncn"]))
             f.writelines("%s %s %r\n" % (a, b, float(r)) for a, b, r in case["ncn"])
+        if case.get("vaf"):             # rows of vaf.dat every n steps after the equilibration: sys_init.cpp:883-884
+            f.write("vaf\t%d\n" % int(case["vaf"]))
         f.write("stat\t%d\n" % stat)
     if case.get("bonds") is not None and len(case["bonds"]):
         with open(os.path.join(directory, "bonds.txt"), "w") as f:       # read_bondlist, bonds.cpp:25-110

@@ -326,6 +326,59 @@ int aztot_cn_per_atom(aztot_md *md, int kind, int32_t *counts, int cap);
 /* table[(cn - cn_min) * n_cols + column] = central atoms of the column with that CN (if cap >= rows * n_cols); returns rows * n_cols */
 int aztot_cn_table(aztot_md *md, int kind, int64_t *table, int cap);
 
+/* ---- time correlation functions: mean-square displacement (out_msd, out_md.cpp:89-124) and velocity autocorrelation (vaf_init / vaf_info,
+   out_md.cpp:535-582) per species, averaged over a ring of time origins ------------------------------------------------------------------------------
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.
+
+   A SAMPLE reads the state aztot_md_to_host would return at that moment: wrapped x y z, vx vy vz with the last step's second half-kick completed,
+   types.  Samples are numbered c = 0, 1, 2, ... since the last set-up or reset.  Lags are counted IN SAMPLES; equal spacing in time is the caller's
+   business.
+
+   ORIGINS.  With n_origins M and origin_every E, sample c becomes an origin iff c % E == 0 and is then stored (positions and velocities of every
+   atom, by atom id) in ring slot (c / E) % M, replacing the oldest.  n_lags = M * E.  Sample c is correlated with every live origin o, itself
+   included (lag 0): every o with o % E == 0, o <= c and c - o < M * E.  The pair (c, o) contributes to lag c - o; within one sample all live origins
+   have different lags.  The reference's single origin (x0s / vx0 taken once) is M = 1 with E >= the number of samples taken.
+
+   PER-ATOM TERMS, fp64, every operation rounded on its own (no contraction), from atom i's current state and its state in origin o:
+       d = x - x0 per axis, then delta_periodic (box.cpp:180-205): d > L / 2 -> d -= L, else d < -L / 2 -> d += L
+       m_i = (dx*dx + dy*dy) + dz*dz                       (out_md.cpp:105-114)
+       v_i = (vx*vx0 + vy*vy0) + vz*vz0                    (out_md.cpp:571)
+   The minimum-image displacement is the reference's definition.  PRECONDITION: no atom moves farther than L / 2 along an axis within the largest lag;
+   this cannot be detected (the integrator keeps no per-atom image counters), the bounded lag window is what makes it reasonable.
+
+   PER-SPECIES SUMS IN ONE FIXED ORDER.  For species s let t[i] be the term of atom id i if types[i] == s, else +0.0, i = 0 ... N - 1.  Folding an
+   array of 2^k values by halving: for h = 2^(k-1), ..., 2, 1: a[j] = a[j] + a[j + h] for every j < h; the result is a[0].  The sum is this tree:
+     1. the ids, zero-padded to a multiple of 256, in runs of 64 consecutive ids: each run folded by halving (h = 32, ..., 1);
+     2. the four run sums of each chunk of 256 ids folded by halving: (w0 + w2) + (w1 + w3);
+     3. the chunk sums, zero-padded to the next power of two, folded by halving.
+   A sample's sums are therefore a function of the state alone: they do not depend on the order the cell sort has left the atoms in, on the launch
+   shape or on the run, and a few lines of numpy reproduce them bit for bit.  No floating-point atomics anywhere.
+
+   ACCUMULATORS.  Per lag l: count[l] (pairs (c, o) seen) and per species msd_sum[l][s], vaf_sum[l][s], each updated as acc = acc + S once per
+   contributing sample, in sample order.  Values: acc / (double)(count[l] * n_s), n_s = atoms of species s; 0.0 where count[l] == 0 or n_s == 0
+   (the reference prints 0 / 0 for the MSD of an empty species, out_md.cpp:120).  With M = 1 these are the reference's displ / number and
+   vaf / number.
+
+   Memory: M * 48 * N bytes for the ring, 48 * N for the current state, the partial sums and 8 * n_lags * (1 + 2 * n_species) for the accumulators;
+   a set-up that cannot allocate fails with AZTOT_ERR_DEVICE, leaves no sampler and a handle that still steps.
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.
+   Errors: null handle, n_origins or origin_every < 1, n_origins * origin_every > AZTOT_TCF_MAX_LAGS, sampling or reading before the set-up, a lag
+   range outside [0, n_lags) -> AZTOT_ERR_ARG; a handle that failed earlier refuses to sample but can still be read. */
+#define AZTOT_TCF_MAX_LAGS (1 << 24)
+/* (re)allocate and zero: forgets every origin and sum of an earlier set-up; returns n_lags */
+int aztot_tcf_setup(aztot_md *md, int n_origins, int origin_every);
+/* one sample of the current state */
+int aztot_tcf_sample(aztot_md *md);
+/* zero sums and counts, forget the origins: the next sample is sample 0 */
+int aztot_tcf_reset(aztot_md *md);
+/* lags, species and samples since the set-up / reset (each pointer may be null) */
+int aztot_tcf_shape(aztot_md *md, int *n_lags, int *n_species, int64_t *samples);
+/* raw accumulators of lags [lag0, lag0 + n): count[lag - lag0], msd_sum / vaf_sum[(lag - lag0) * n_species + species] (if cap >= n * n_species; each
+   pointer may be null); returns n * n_species */
+int aztot_tcf_sums(aztot_md *md, int lag0, int n, int64_t *count, double *msd_sum, double *vaf_sum, int cap);
+/* the normalised values in the same layout (if cap >= n * n_species); returns n * n_species */
+int aztot_tcf_values(aztot_md *md, int lag0, int n, double *msd, double *vaf, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
