@@ -8,7 +8,13 @@
 //
 // Here nothing per (atom, k) ever touches HBM: both kernels rebuild the three small per-atom harmonic tables in LDS.
 //   k_ewald_sfac    threads <-> k-vectors, 64 atoms per tile in LDS ([atom][harmonic]: the 64 lanes read the same atom, different
-//                   harmonics -> broadcasts); per-block partial S(k) in a fixed order -> bit-reproducible
+//                   harmonics -> broadcasts); per-block partial S(k) in a fixed order -> bit-reproducible.  The summation tree of S(k),
+//                   which tests/test_gpu_ewald.py relies on (two engines agree bit for bit) and tests/ewald_reference.py restates (_tree):
+//                     tile:   64 atoms, owned order, added left to right (a partial last tile is padded with zero charges)
+//                     block:  block b of nB = nBlocksA = min(1024, ceil(capacity / 64)) adds its tiles b, b + nB, b + 2 nB, ... in that
+//                             order into row b of `partial` (the first round stores, later rounds add)
+//                     reduce: group g of 16 adds the rows g, g + 16, g + 32, ... in that order; the 16 group sums are added g = 0..15
+//                   nothing in it depends on timing or on the number of CUs; it does depend on the atoms' owned order and on capacity
 //   k_ewald_reduce  S(k) = sum over blocks (fixed order)                     [multi-GPU: all-reduce of S over the ranks follows]
 //   k_ewald_force   threads <-> atoms, the k loop is wave-uniform (k-vector data and S(k) come through scalar loads), harmonic
 //                   tables in LDS as [harmonic][lane] (conflict-free); exp(i(lx+my)) is reused along the inner n loop

@@ -73,7 +73,7 @@ typedef struct
     int32_t use_cell_list;       /* 'cell_list' present */
     double cell_list;            /* desired cell edge */
     int32_t stat;                /* statistics period */
-    int32_t ewald_k[3];          /* 'elec pme rReal alpha kx ky kz' (read_elec elec.cpp:33-38): k-vectors per axis, 1..16 */
+    int32_t ewald_k[3];          /* 'elec pme rReal alpha kx ky kz' (read_elec elec.cpp:33-38): k-vectors per axis, 1..48 (kEwaldKMax, csrc/model.h) */
 } aztot_control;
 
 /* array form of atoms.xyz + field.txt + control.txt (used by tests / bench; same state as aztot_init_md) */

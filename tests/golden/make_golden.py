@@ -179,7 +179,20 @@ def ewald_fixtures():
     print("E1_ewald", "N=%d" % len(case["types"]), "Econst %.9f Erec %.9f Ereal %.9f" % (d["engElec1"], d["engElec2"], d["engElec3"]))
 
 
+def ewald_reciprocal_fixture():
+    """ewald_reciprocal.npz: the 50-digit reciprocal-space sums of the isolated systems of tests/ewald_reference.py with their coordinates, and
+    the all-mpmath per-atom forces and energies of the dense 500-ion system (tests/test_gpu_ewald.py reads it with numpy alone).  Needs
+    mpmath, not the reference binary; about two minutes."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ewald_reference as er
+    a = er.make_fixture(os.path.join(HERE, "ewald_reciprocal.npz"))
+    print("ewald_reciprocal", "%d arrays" % len(a), "dense pairs %d" % int(a["dense__npairs"]))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["ewald_reciprocal"]:
+        ewald_reciprocal_fixture()
+        sys.exit(0)
     oracle.build()
     if sys.argv[1:] == ["ewald"]:
         ewald_fixtures()
