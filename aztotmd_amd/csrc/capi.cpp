@@ -414,27 +414,27 @@ int aztot_rdf_setup(aztot_md* md, double rmax, double dr, int nuclei)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
     int n = 0;
-    const int rc = guarded([&] { n = md->eng->rdf_setup(rmax, dr, nuclei != 0); });
+    const int rc = guarded([&] { n = md->eng->samplers().rdf_setup(rmax, dr, nuclei != 0); });
     return rc < 0 ? rc : n;
 }
 
 int aztot_rdf_sample(aztot_md* md)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->rdf_sample(); });
+    return guarded([&] { md->eng->samplers().rdf_sample(); });
 }
 
 int aztot_rdf_reset(aztot_md* md)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->rdf_reset(); });
+    return guarded([&] { md->eng->samplers().rdf_reset(); });
 }
 
 int aztot_rdf_shape(aztot_md* md, int kind, int* n_bins, int* n_pairs)
 {
     if (!md || !md->eng || !n_bins || !n_pairs) return fail(AZTOT_ERR_ARG, "null argument");
     long long samples = 0;
-    return guarded([&] { md->eng->rdf_counts(kind, *n_bins, *n_pairs, samples, nullptr); });
+    return guarded([&] { md->eng->samplers().rdf_counts(kind, *n_bins, *n_pairs, samples, nullptr); });
 }
 
 int aztot_rdf_counts(aztot_md* md, int kind, int64_t* samples, uint64_t* counts, int cap)
@@ -444,13 +444,13 @@ int aztot_rdf_counts(aztot_md* md, int kind, int64_t* samples, uint64_t* counts,
     const int rc = guarded([&] {
         int nb = 0, np = 0;
         long long s = 0;
-        md->eng->rdf_counts(kind, nb, np, s, nullptr);
+        md->eng->samplers().rdf_counts(kind, nb, np, s, nullptr);
         need = nb * np;
         if (samples) *samples = s;
         if (counts && cap >= need)
         {
             std::vector<unsigned long long> c;
-            md->eng->rdf_counts(kind, nb, np, s, &c);
+            md->eng->samplers().rdf_counts(kind, nb, np, s, &c);
             for (int k = 0; k < need; k++) counts[k] = c[k];
         }
     });
@@ -464,11 +464,11 @@ int aztot_rdf_values(aztot_md* md, int kind, double* r, double* g, int cap)
     const int rc = guarded([&] {
         int nb = 0, np = 0;
         long long s = 0;
-        md->eng->rdf_counts(kind, nb, np, s, nullptr);
+        md->eng->samplers().rdf_counts(kind, nb, np, s, nullptr);
         need = nb * np;
         if (cap < need) return;
         std::vector<double> rv, gv;
-        md->eng->rdf_values(kind, rv, gv);
+        md->eng->samplers().rdf_values(kind, rv, gv);
         if (r) std::memcpy(r, rv.data(), sizeof(double) * rv.size());
         if (g) std::memcpy(g, gv.data(), sizeof(double) * gv.size());
     });
@@ -478,19 +478,19 @@ int aztot_rdf_values(aztot_md* md, int kind, double* r, double* g, int cap)
 int aztot_cn_setup(aztot_md* md, int kind, const aztot_cn_column* cols, int n_cols)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->cn_setup(kind, cols, n_cols); });
+    return guarded([&] { md->eng->samplers().cn_setup(kind, cols, n_cols); });
 }
 
 int aztot_cn_sample(aztot_md* md, int kind)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->cn_sample(kind); });
+    return guarded([&] { md->eng->samplers().cn_sample(kind); });
 }
 
 int aztot_cn_shape(aztot_md* md, int kind, int* n_cols, int* cn_min, int* cn_max)
 {
     if (!md || !md->eng || !n_cols || !cn_min || !cn_max) return fail(AZTOT_ERR_ARG, "null argument");
-    return guarded([&] { md->eng->cn_shape(kind, *n_cols, *cn_min, *cn_max); });
+    return guarded([&] { md->eng->samplers().cn_shape(kind, *n_cols, *cn_min, *cn_max); });
 }
 
 int aztot_cn_per_atom(aztot_md* md, int kind, int32_t* counts, int cap)
@@ -499,13 +499,13 @@ int aztot_cn_per_atom(aztot_md* md, int kind, int32_t* counts, int cap)
     int need = 0;
     const int rc = guarded([&] {
         int nc = 0, mn = 0, mx = 0;
-        md->eng->cn_shape(kind, nc, mn, mx);
+        md->eng->samplers().cn_shape(kind, nc, mn, mx);
         const long long want = (long long)md->eng->n_atoms_global() * nc;
         if (want > 0x7fffffffLL) throw ArgError("cn: atoms x columns does not fit the int this call returns");
         need = (int)want;
         if (!counts || cap < need) return;
         std::vector<int32_t> v;
-        md->eng->cn_per_atom(kind, v);
+        md->eng->samplers().cn_per_atom(kind, v);
         std::memcpy(counts, v.data(), sizeof(int32_t) * v.size());
     });
     return rc < 0 ? rc : need;
@@ -517,11 +517,11 @@ int aztot_cn_table(aztot_md* md, int kind, int64_t* table, int cap)
     int need = 0;
     const int rc = guarded([&] {
         int nc = 0, mn = 0, mx = 0;
-        md->eng->cn_shape(kind, nc, mn, mx);
+        md->eng->samplers().cn_shape(kind, nc, mn, mx);
         need = std::max(0, mx - mn + 1) * nc;
         if (!table || cap < need) return;
         std::vector<long long> v;
-        md->eng->cn_table(kind, v);
+        md->eng->samplers().cn_table(kind, v);
         for (int k = 0; k < need; k++) table[k] = v[k];
     });
     return rc < 0 ? rc : need;
@@ -531,20 +531,20 @@ int aztot_tcf_setup(aztot_md* md, int n_origins, int origin_every)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
     int nLags = 0;
-    const int rc = guarded([&] { nLags = md->eng->tcf_setup(n_origins, origin_every); });
+    const int rc = guarded([&] { nLags = md->eng->samplers().tcf_setup(n_origins, origin_every); });
     return rc < 0 ? rc : nLags;
 }
 
 int aztot_tcf_sample(aztot_md* md)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->tcf_sample(); });
+    return guarded([&] { md->eng->samplers().tcf_sample(); });
 }
 
 int aztot_tcf_reset(aztot_md* md)
 {
     if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
-    return guarded([&] { md->eng->tcf_reset(); });
+    return guarded([&] { md->eng->samplers().tcf_reset(); });
 }
 
 int aztot_tcf_shape(aztot_md* md, int* n_lags, int* n_species, int64_t* samples)
@@ -553,7 +553,7 @@ int aztot_tcf_shape(aztot_md* md, int* n_lags, int* n_species, int64_t* samples)
     return guarded([&] {
         int nl = 0, ns = 0;
         long long sm = 0;
-        md->eng->tcf_shape(nl, ns, sm);
+        md->eng->samplers().tcf_shape(nl, ns, sm);
         if (n_lags) *n_lags = nl;
         if (n_species) *n_species = ns;
         if (samples) *samples = sm;
@@ -567,12 +567,12 @@ int aztot_tcf_sums(aztot_md* md, int lag0, int n, int64_t* count, double* msd_su
     const int rc = guarded([&] {
         int nl = 0, ns = 0;
         long long sm = 0;
-        md->eng->tcf_shape(nl, ns, sm);
+        md->eng->samplers().tcf_shape(nl, ns, sm);
         const bool fill = cap >= (long long)std::max(n, 0) * ns;
         std::vector<long long> c;
         std::vector<double> a, b;
         // (the range is checked whether or not anything is filled)
-        md->eng->tcf_sums(lag0, n, fill && count ? &c : nullptr, fill && msd_sum ? &a : nullptr, fill && vaf_sum ? &b : nullptr);
+        md->eng->samplers().tcf_sums(lag0, n, fill && count ? &c : nullptr, fill && msd_sum ? &a : nullptr, fill && vaf_sum ? &b : nullptr);
         need = n * ns;
         for (size_t k = 0; k < c.size(); k++) count[k] = c[k];
         if (!a.empty()) std::memcpy(msd_sum, a.data(), a.size() * sizeof(double));
@@ -588,10 +588,10 @@ int aztot_tcf_values(aztot_md* md, int lag0, int n, double* msd, double* vaf, in
     const int rc = guarded([&] {
         int nl = 0, ns = 0;
         long long sm = 0;
-        md->eng->tcf_shape(nl, ns, sm);
-        if (cap < (long long)std::max(n, 0) * ns || (!msd && !vaf)) { md->eng->tcf_sums(lag0, n, nullptr, nullptr, nullptr); need = n * ns; return; }
+        md->eng->samplers().tcf_shape(nl, ns, sm);
+        if (cap < (long long)std::max(n, 0) * ns || (!msd && !vaf)) { md->eng->samplers().tcf_sums(lag0, n, nullptr, nullptr, nullptr); need = n * ns; return; }
         std::vector<double> a, b;
-        md->eng->tcf_values(lag0, n, a, b);
+        md->eng->samplers().tcf_values(lag0, n, a, b);
         need = n * ns;
         if (msd && !a.empty()) std::memcpy(msd, a.data(), a.size() * sizeof(double));
         if (vaf && !b.empty()) std::memcpy(vaf, b.data(), b.size() * sizeof(double));

@@ -12,7 +12,7 @@ namespace aztot {
 
 void check_hip(hipError_t e, const char* what);
 
-// device memory that lives as long as the arena: the engine's, the pair lists' (ListStore), the RDF sampler's
+// device memory that lives as long as the arena: the engine's, the pair lists' (ListStore), each sampler's (Samplers)
 class DeviceArena
 {
 public:

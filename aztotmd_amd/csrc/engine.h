@@ -16,6 +16,7 @@
 #include "list_store.h"
 #include "model.h"
 #include "msg_layout.h"
+#include "samplers.h"
 
 namespace aztot {
 
@@ -85,7 +86,7 @@ namespace aztot {
 //                    step's pair kernel / boundary kernel                  launch_step_kernels (k_boundary_radi)       graph capture, replay
 //  fuseNext_/fuseNow_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   set and consumed inside launch_step_kernels / launch_pair
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
-class Engine
+class Engine final : private Samplers::Host
 {
 public:
     Engine(const Model& model, const aztot_options& opt, int rank, int nranks, Exchanger* xch);
@@ -107,30 +108,7 @@ public:
     int n_atoms_global() const { return model_.nAt; }
     int comm_ranks() const { return xch_ ? xch_->comm_ranks() : 0; }
     void sync_all();                        // everything queued or deferred by earlier calls has happened when this returns (aztot_sync)
-
-    // radial distribution functions (rdf.hip.h; aztot_rdf_* in include/aztot.h): a private cell grid over the current positions, integer totals
-    int rdf_setup(double rmax, double dr, bool nuclei);     // (re)allocates and zeroes; returns the number of bins
-    void rdf_sample();                                       // one sample of the configuration as aztot_md_to_host would return it
-    void rdf_reset();
-    // kind 0 species, 1 nuclei: bins, pairs, samples and (if counts) the totals [bin][pair]
-    void rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts);
-    void rdf_values(int kind, std::vector<double>& r, std::vector<double>& g);     // bin centres and normalised g(r), same layout
-
-    // coordination numbers (cn.hip.h; aztot_cn_* in include/aztot.h, which states the rules of the two kinds)
-    void cn_setup(int kind, const aztot_cn_column* cols, int nCols);   // (re)allocates; replaces the columns and forgets the last sample of `kind`
-    void cn_sample(int kind);                                          // a snapshot of the configuration as aztot_md_to_host would return it
-    void cn_shape(int kind, int& nCols, int& cnMin, int& cnMax);
-    void cn_per_atom(int kind, std::vector<int32_t>& out);             // [atom id][column], -1 where the atom is not the column's central
-    void cn_table(int kind, std::vector<long long>& out);              // [cn - cnMin][column]
-
-    // time correlation functions (tcf.hip.h; aztot_tcf_* in include/aztot.h, which states the terms, the summation tree and the ring of origins)
-    int tcf_setup(int nOrigins, int originEvery);                      // (re)allocates and zeroes; returns the number of lags
-    void tcf_sample();                                                 // one sample of the state as aztot_md_to_host would return it
-    void tcf_reset();                                                  // zero sums and counts, forget the origins
-    void tcf_shape(int& nLags, int& nSpec, long long& samples);
-    // lags [lag0, lag0 + n): pairs seen and the raw sums [lag - lag0][species] (each output optional)
-    void tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf);
-    void tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf);     // sum / (count * atoms of the species), 0 where that is 0
+    Samplers& samplers() { return *samplers_; }     // RDF, coordination numbers, time correlation functions: they see the engine as a Samplers::Host
 
 private:
     void step_body(int nsteps);
@@ -168,6 +146,11 @@ private:
     AtomArrays& oth() { return buf_[cur_ ^ 1]; }
     int left() const { return (rank_ + nranks_ - 1) % nranks_; }       // x-neighbours on the ring of slab ranks
     int right() const { return (rank_ + 1) % nranks_; }
+    // Samplers::Host
+    void quiesce() override { sync_all(); }
+    AtomArrays begin_sample() override;
+    void end_sample(const char* where) override { check_launch(where); sync(); }
+    void launch_timed(const char* name, const std::function<void()>& launch) override { timed(name, launch); }
 
     Model model_;
     aztot_options opt_;
@@ -181,7 +164,7 @@ private:
     hipStream_t stream_ = nullptr;
     hipStream_t commStream_ = nullptr;      // slab ranks, plain steps: the coordinate exchange runs here while the interior cells' pair forces run on stream_
     hipEvent_t evIntegrated_ = nullptr, evHalo_ = nullptr;
-    DeviceArena mem_;               // every device buffer below except the pair lists' and the samplers' (RDF, coordination numbers, time correlation functions)
+    DeviceArena mem_;               // every device buffer below except the pair lists' (ListStore); the samplers own theirs (samplers.h)
     bool profile_ = false;
     KernelTimers timers_;
     int capacity_ = 0;          // atoms that fit in the per-atom arrays (owned + ghosts + slack)
@@ -268,58 +251,7 @@ private:
     double pressure_ = 0.0;
     long long lastPresStep_ = 0;
 
-    // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
-    // each coordination-number set-up has one (different cell edges)
-    struct GridSort
-    {
-        DeviceArena mem;
-        int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
-        double *x = nullptr, *y = nullptr, *z = nullptr;
-        Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
-        DevStats* scanStats = nullptr;
-        RdfGrid grid{};
-    };
-    void grid_setup(GridSort& S, double edge);                      // cells with an edge >= `edge`, at most about N of them; allocates the sort's buffers
-    void grid_fill(GridSort& S, const char* const timerNames[3]);   // bin, scan, place the current positions (timer names of the three stages)
-    struct RdfState : GridSort
-    {
-        double rmax = 0, dr = 0;
-        int nBins = 0;                  // 0: not set up
-        bool nuclei = false;
-        long long samples = 0;
-        int copies = 0;                 // LDS sub-histograms per workgroup of k_rdf_pairs (0: straight into the totals)
-        int blocks = 0;
-        unsigned long long *histS = nullptr, *histN = nullptr;
-    } rdf_;
-    // coordination numbers (cn.hip.h): one state per kind (AZTOT_CN_SPECIES, AZTOT_CN_NUCLEI), each a snapshot of the last sample
-    struct CnState : GridSort
-    {
-        std::vector<aztot_cn_column> cols;          // empty: not set up
-        CnParams par{};
-        int sliceShift = 0;                         // lanes per atom in k_cn_pairs = 1 << sliceShift
-        int nLive[kSpecCap] = {};                   // per central group: its columns ...
-        int colOf[kSpecCap * kCnLive] = {};         // ... and which column each of its counters is
-        bool sampled = false;
-        int cnMin = 0, cnMax = 0, rowsCap = 0;
-        int32_t *slotId = nullptr, *counts = nullptr, *range = nullptr, *dSlotOf = nullptr, *dNLive = nullptr, *dColOf = nullptr;
-        double *dR2Of = nullptr, *dRowMax = nullptr;
-        DeviceArena tableMem;                       // the table alone: it grows when a sample has more rows than any before
-        unsigned long long* table = nullptr;
-    } cn_[2];
-    CnState& cn_state(int kind, bool needSetup, bool needSample);
-    // time correlation functions (tcf.hip.h): the current state and a ring of origins in atom-id order, accumulators per lag
-    struct TcfState
-    {
-        int M = 0, E = 0;               // origins in the ring and samples between two of them; M == 0: not set up
-        long long samples = 0;          // since the set-up or the last reset
-        int nSpec = 0, nChunk = 0, nChunkPad = 0;
-        size_t nPad = 0;                // ids padded to a multiple of kTcfChunk
-        DeviceArena mem;
-        double *cur = nullptr, *ring = nullptr, *partials = nullptr, *msdSum = nullptr, *vafSum = nullptr;
-        int32_t* type = nullptr;        // species by atom id, -1 in the padding
-        long long* count = nullptr;
-        int n_lags() const { return M * E; }
-    } tcf_;
+    std::unique_ptr<Samplers> samplers_;    // made once stream and box exist (construct); its arenas free their memory after release() has drained the streams
 
     // -- graphs: hipGraph replay of a cycle of steps.  Kernel arguments are baked in at capture time, so a graph is valid for the buffer state it was
     // captured in (which AtomArrays is current, which coordinate arrays each of them holds: the sort ping-pongs the buffers, the fused next-step epilogue

@@ -1,0 +1,139 @@
+// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h) and time correlation functions (tcf.hip.h) behind
+// aztot_rdf_* / aztot_cn_* / aztot_tcf_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
+// is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
+//
+// The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
+// arrays - the configuration as aztot_md_to_host would return it: the deferred end of the last aztot_step call has happened - and writes only the samplers'
+// own buffers.  It returns with the engine settled AND drained, as every reader does (aztot_get_stats): the next aztot_step must open on an idle stream.
+// (Returning with a sample still running changed engKin in its last bit in about one run of three: sort_every = 1, seen in test_gpu_rdf.py.)  A set-up
+// replaces buffers only when nothing queued or deferred can still use them, and commits only when everything has been allocated and uploaded.
+#pragma once
+#include <functional>
+#include <vector>
+
+#include "device_md.h"
+#include "device_resources.h"
+#include "model.h"
+
+namespace aztot {
+
+struct Counts;
+
+class Samplers
+{
+public:
+    // The engine as the samplers see it, and all they see of it
+    struct Host
+    {
+        virtual void quiesce() = 0;                         // everything queued or deferred by earlier calls has happened (before a set-up replaces buffers)
+        virtual AtomArrays begin_sample() = 0;              // refuses a failed handle, completes the deferred end of the last aztot_step; the current arrays
+        virtual void end_sample(const char* where) = 0;     // the launch check, then the stream drains: every sample ends here (one with a read-back passes twice)
+        virtual void launch_timed(const char* name, const std::function<void()>& launch) = 0;   // under the per-kernel timer `name` when profiling is on
+    protected:
+        ~Host() = default;
+    };
+    struct Box { double L[3], invL[3], half[3]; };
+
+    Samplers(Host& host, const Model& model, const Box& box, hipStream_t stream, int nranks)
+        : host_(host), model_(model), box_(box), stream_(stream), nranks_(nranks), nuclei_(nuclei_of(model)) {}
+    Samplers(const Samplers&) = delete;
+
+    // radial distribution functions: a private cell grid over the current positions, integer totals
+    int rdf_setup(double rmax, double dr, bool nuclei);     // (re)allocates and zeroes; returns the number of bins
+    void rdf_sample();
+    void rdf_reset();
+    // kind 0 species, 1 nuclei: bins, pairs, samples and (if counts) the totals [bin][pair]
+    void rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts);
+    void rdf_values(int kind, std::vector<double>& r, std::vector<double>& g);     // bin centres and normalised g(r), same layout
+
+    // coordination numbers (include/aztot.h states the rules of the two kinds): each kind keeps a snapshot of its last sample
+    void cn_setup(int kind, const aztot_cn_column* cols, int nCols);   // (re)allocates; replaces the columns and forgets the last sample of `kind`
+    void cn_sample(int kind);
+    void cn_shape(int kind, int& nCols, int& cnMin, int& cnMax);
+    void cn_per_atom(int kind, std::vector<int32_t>& out);             // [atom id][column], -1 where the atom is not the column's central
+    void cn_table(int kind, std::vector<long long>& out);              // [cn - cnMin][column]
+
+    // time correlation functions (include/aztot.h states the terms, the summation tree and the ring of origins)
+    int tcf_setup(int nOrigins, int originEvery);                      // (re)allocates and zeroes; returns the number of lags
+    void tcf_sample();
+    void tcf_reset();                                                  // zero sums and counts, forget the origins
+    void tcf_shape(int& nLags, int& nSpec, long long& samples);
+    // lags [lag0, lag0 + n): pairs seen and the raw sums [lag - lag0][species] (each output optional)
+    void tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf);
+    void tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf);     // sum / (count * atoms of the species), 0 where that is 0
+
+private:
+    // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
+    // each coordination-number set-up has one (different cell edges)
+    struct GridSort
+    {
+        DeviceArena mem;
+        int32_t *cellOf = nullptr, *rankOf = nullptr, *cellCount = nullptr, *cellStart = nullptr, *chunkTot = nullptr, *kind = nullptr;
+        double *x = nullptr, *y = nullptr, *z = nullptr;
+        Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
+        DevStats* scanStats = nullptr;
+        RdfGrid grid{};
+    };
+    struct RdfState : GridSort
+    {
+        double rmax = 0, dr = 0;
+        int nBins = 0;                  // 0: not set up
+        bool nuclei = false;
+        long long samples = 0;
+        int copies = 0;                 // LDS sub-histograms per workgroup of k_rdf_pairs (0: straight into the totals)
+        int blocks = 0;
+        unsigned long long *histS = nullptr, *histN = nullptr;
+    };
+    struct CnState : GridSort
+    {
+        std::vector<aztot_cn_column> cols;          // empty: not set up
+        CnParams par{};
+        int sliceShift = 0;                         // lanes per atom in k_cn_pairs = 1 << sliceShift
+        int nLive[kSpecCap] = {};                   // per central group: its columns ...
+        int colOf[kSpecCap * kCnLive] = {};         // ... and which column each of its counters is
+        bool sampled = false;
+        int cnMin = 0, cnMax = 0, rowsCap = 0;
+        int32_t *slotId = nullptr, *counts = nullptr, *range = nullptr, *dSlotOf = nullptr, *dNLive = nullptr, *dColOf = nullptr;
+        double *dR2Of = nullptr, *dRowMax = nullptr;
+        DeviceArena tableMem;                       // the table alone: it grows when a sample has more rows than any before
+        unsigned long long* table = nullptr;
+    };
+    // the current state and a ring of origins in atom-id order, accumulators per lag
+    struct TcfState
+    {
+        int M = 0, E = 0;               // origins in the ring and samples between two of them; M == 0: not set up
+        long long samples = 0;          // since the set-up or the last reset
+        int nSpec = 0, nChunk = 0, nChunkPad = 0;
+        size_t nPad = 0;                // ids padded to a multiple of kTcfChunk
+        DeviceArena mem;
+        double *cur = nullptr, *ring = nullptr, *partials = nullptr, *msdSum = nullptr, *vafSum = nullptr;
+        int32_t* type = nullptr;        // species by atom id, -1 in the padding
+        long long* count = nullptr;
+        int n_lags() const { return M * E; }
+    };
+
+    // the protocol every sampler follows, once (samplers.hip.h)
+    void need_one_gpu(const char* what) const;
+    static void need_setup(bool isSetUp, const char* name, const char* tail = "");
+    template <typename State, typename F> void set_up(State& slot, State& fresh, F&& allocate);
+    template <typename F> void sample(const char* where, F&& launch);
+    template <typename F> void timed(const char* name, F&& launch) { host_.launch_timed(name, launch); }
+
+    void grid_setup(GridSort& S, double edge);                                              // cells with an edge >= `edge`, at most about N of them; allocates the sort's buffers
+    void grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3]);      // bin, scan, place the positions of A (timer names of the three stages)
+    RdfState& rdf_state();
+    CnState& cn_state(int kind, bool needSetup, bool needSample);
+    TcfState& tcf_state();
+
+    Host& host_;
+    const Model& model_;            // the engine's (outlives the samplers)
+    const Box box_;
+    const hipStream_t stream_;
+    const int nranks_;
+    const Nuclei nuclei_;
+    RdfState rdf_;
+    CnState cn_[2];                 // AZTOT_CN_SPECIES, AZTOT_CN_NUCLEI
+    TcfState tcf_;
+};
+
+}  // namespace aztot

@@ -1,0 +1,466 @@
+// Samplers: the bodies (see samplers.h for the contract).  Included by engine.hip behind the kernel headers and its own helpers (HIP_CHECK, div_up).
+#pragma once
+#include "samplers.h"
+
+namespace aztot {
+
+// ---------------------------------------------------------------------------------------------------
+// The protocol, once
+// ---------------------------------------------------------------------------------------------------
+void Samplers::need_one_gpu(const char* what) const
+{
+    if (nranks_ > 1) throw std::runtime_error(std::string("out of scope: ") + what + " of a slab-decomposed (multi-GPU) run are not supported");
+}
+
+void Samplers::need_setup(bool isSetUp, const char* name, const char* tail)
+{
+    if (!isSetUp) throw ArgError(std::string(name) + ": aztot_" + name + "_setup has not been called" + tail);
+}
+
+// A set-up, all or nothing.  The caller has validated its arguments (a bad call leaves the earlier set-up in place) and filled the host side of `fresh`;
+// `allocate` allocates and uploads the device side of it.  The earlier set-up is freed first - never two generations in memory - and `fresh` is committed only when
+// everything is in place.  No room: no sampler ("not set up"), and the handle steps on - the refused allocation must not surface at the next launch check.
+template <typename State, typename F> void Samplers::set_up(State& slot, State& fresh, F&& allocate)
+{
+    host_.quiesce();
+    slot = State();                 // (nothing can still use its buffers: the stream has just drained)
+    try
+    {
+        allocate();
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    catch (...)
+    {
+        (void)hipStreamSynchronize(stream_);
+        (void)hipGetLastError();
+        throw;
+    }
+    slot = std::move(fresh);
+}
+
+// A sample: the engine settles, `launch` queues the kernels on the arrays as they then stand, and the engine is left settled and drained
+template <typename F> void Samplers::sample(const char* where, F&& launch)
+{
+    const AtomArrays A = host_.begin_sample();
+    launch(A);
+    host_.end_sample(where);
+}
+
+Samplers::RdfState& Samplers::rdf_state() { need_setup(rdf_.nBins != 0, "rdf"); return rdf_; }
+Samplers::TcfState& Samplers::tcf_state() { need_setup(tcf_.M != 0, "tcf"); return tcf_; }
+Samplers::CnState& Samplers::cn_state(int kind, bool needSetup, bool needSample)
+{
+    if (kind != AZTOT_CN_SPECIES && kind != AZTOT_CN_NUCLEI) throw ArgError("cn: kind must be AZTOT_CN_SPECIES or AZTOT_CN_NUCLEI");
+    CnState& S = cn_[kind];
+    if (needSetup) need_setup(!S.cols.empty(), "cn", " for this kind");
+    if (needSample && !S.sampled) throw ArgError("cn: aztot_cn_sample has not been called since the set-up of this kind");
+    return S;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The private cell grid of the RDF and coordination-number samplers
+// ---------------------------------------------------------------------------------------------------
+// cells with an edge >= `edge` (a hair more: the cell of a coordinate is floor(x * nc / L) in fp64), at most about N of them (a dilute gas in a large box
+// would otherwise get mostly empty cells); the buffers of the counting sort.  Histogram fields of the grid are the caller's.
+void Samplers::grid_setup(GridSort& S, double edge)
+{
+    RdfGrid& G = S.grid;
+    const int N = model_.nAt;
+    long long nc[3];
+    for (int k = 0; k < 3; k++) nc[k] = std::max(1LL, (long long)std::floor(box_.L[k] / (edge * (1.0 + 1e-9))));
+    const long long cellCap = std::max(27, N);
+    while (nc[0] * nc[1] * nc[2] > cellCap)
+    {
+        const int k = (nc[0] >= nc[1] && nc[0] >= nc[2]) ? 0 : (nc[1] >= nc[2] ? 1 : 2);
+        nc[k] = std::max(1LL, nc[k] * 3 / 4);
+    }
+    for (int k = 0; k < 3; k++)
+    {
+        G.nc[k] = (int)nc[k];
+        G.L[k] = box_.L[k]; G.invL[k] = box_.invL[k]; G.half[k] = box_.half[k];
+        G.icsz[k] = (double)nc[k] / box_.L[k];
+    }
+    G.nCell = G.nc[0] * G.nc[1] * G.nc[2];
+    G.halfShell = (G.nc[0] >= 3 && G.nc[1] >= 3 && G.nc[2] >= 3) ? 1 : 0;
+    for (int t = 0; t < kSpecCap; t++) G.nucl[t] = t < model_.nSpec() ? nuclei_.of[t] : 0;
+    const size_t n = (size_t)std::max(N, 1);
+    S.cellOf = S.mem.alloc<int32_t>(n, false, stream_); S.rankOf = S.mem.alloc<int32_t>(n, false, stream_); S.kind = S.mem.alloc<int32_t>(n, false, stream_);
+    S.x = S.mem.alloc<double>(n, false, stream_); S.y = S.mem.alloc<double>(n, false, stream_); S.z = S.mem.alloc<double>(n, false, stream_);
+    S.cellCount = S.mem.alloc<int32_t>((size_t)G.nCell, true, stream_); S.cellStart = S.mem.alloc<int32_t>((size_t)(G.nCell + 1), false, stream_);
+    S.chunkTot = S.mem.alloc<int32_t>((size_t)div_up(G.nCell, kScanChunk), false, stream_);
+    S.scanCounts = S.mem.alloc<Counts>(1, true, stream_); S.scanStats = S.mem.alloc<DevStats>(1, true, stream_);
+}
+
+// counting sort of the positions of A into the grid: wrapped coordinates and species | nucleus << 8 in slot order
+void Samplers::grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3])
+{
+    const RdfGrid& G = S.grid;
+    const int N = model_.nAt;
+    const int nb = div_up(N, kBlock);
+    timed(timerNames[0], [&] { hipLaunchKernelGGL(k_rdf_bin, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellCount); });
+    // exclusive scan of the cell counts (which it leaves cleared for the next sample)
+    if (G.nCell <= kScanSingleMax)
+        timed(timerNames[1], [&] { hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, G.nCell, S.cellCount, S.cellStart, S.scanCounts, S.scanStats, 0); });
+    else
+        timed(timerNames[1], [&] {
+            const int nChunk = div_up(G.nCell, kScanChunk);
+            hipLaunchKernelGGL(k_scan_totals, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, S.cellCount, S.chunkTot);
+            hipLaunchKernelGGL(k_scan_apply, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, S.cellCount, S.chunkTot, S.cellStart, S.scanCounts, S.scanStats, 0);
+        });
+    timed(timerNames[2], [&] {
+        hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellStart, S.x, S.y, S.z, S.kind);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Radial distribution functions (rdf.hip.h)
+// ---------------------------------------------------------------------------------------------------
+int Samplers::rdf_setup(double rmax, double dr, bool nuclei)
+{
+    need_one_gpu("radial distribution functions");
+    if (!(rmax > 0.0) || !(dr > 0.0)) throw ArgError("rdf: rmax and dr must be positive");
+    // bins as init_rdf (rdf.cpp:40-48, what sizes the GPU path's buffer): min(rmax, L_x) / dr
+    const double nb = std::min(rmax, box_.L[0]) * (1.0 / dr);
+    if (!(nb >= 1.0)) throw ArgError("rdf: no bin (dr > min(rmax, box x edge))");
+    const int nSpec = model_.nSpec(), nNucl = (int)nuclei_.names.size();
+    const long long nPairS = (long long)nSpec * (nSpec + 1) / 2, nPairN = nuclei ? (long long)nNucl * (nNucl + 1) / 2 : 0;
+    if (nb * (double)(nPairS + nPairN) > (double)(1 << 28)) throw ArgError("rdf: too many bins (min(rmax, box x edge) / dr x pairs > 2^28)");
+    RdfState R;
+    R.rmax = rmax; R.dr = dr; R.nuclei = nuclei; R.nBins = (int)nb;
+    const size_t nEnt = (size_t)R.nBins * (size_t)(nPairS + nPairN);
+    R.copies = (4 * nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget) ? 4 : (nEnt * sizeof(uint32_t) <= (size_t)kRdfLdsBudget ? 1 : 0);
+    R.blocks = std::max(1, std::min(kRdfMaxBlocks, div_up(model_.nAt, kBlock)));
+    set_up(rdf_, R, [&] {
+        grid_setup(R, rmax);
+        RdfGrid& G = R.grid;
+        G.r2max = rmax * rmax; G.idr = 1.0 / dr; G.nBins = R.nBins;
+        G.nSpec = nSpec; G.nPairS = (int)nPairS;
+        G.nNucl = nNucl; G.nPairN = (int)nPairN;
+        R.histS = R.mem.alloc<unsigned long long>((size_t)R.nBins * nPairS, true, stream_);
+        R.histN = R.mem.alloc<unsigned long long>((size_t)R.nBins * std::max(nPairN, 1LL), true, stream_);
+    });
+    return rdf_.nBins;
+}
+
+void Samplers::rdf_reset()
+{
+    RdfState& R = rdf_state();
+    HIP_CHECK(hipMemsetAsync(R.histS, 0, (size_t)R.nBins * R.grid.nPairS * 8, stream_));
+    if (R.grid.nPairN) HIP_CHECK(hipMemsetAsync(R.histN, 0, (size_t)R.nBins * R.grid.nPairN * 8, stream_));
+    R.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Samplers::rdf_sample()
+{
+    RdfState& R = rdf_state();
+    sample("rdf kernels", [&](const AtomArrays& A) {
+        const RdfGrid& G = R.grid;
+        const int N = model_.nAt;
+        if (N < 2) return;
+        static const char* const names[3] = {"k_rdf_bin", "k_rdf_scan", "k_rdf_place"};
+        grid_fill(R, A, names);
+        const size_t lds = (size_t)R.copies * (size_t)R.nBins * (size_t)(G.nPairS + G.nPairN) * sizeof(uint32_t);
+        timed("k_rdf_pairs", [&] {
+            hipLaunchKernelGGL(k_rdf_pairs, dim3(R.blocks), dim3(kBlock), lds, stream_, G, N, R.cellStart, R.x, R.y, R.z, R.kind, R.copies, R.histS, R.histN);
+        });
+    });
+    R.samples++;
+}
+
+void Samplers::rdf_counts(int kind, int& nBins, int& nPairs, long long& samples, std::vector<unsigned long long>* counts)
+{
+    const RdfState& R = rdf_state();
+    if (kind != 0 && kind != 1) throw ArgError("rdf: kind must be AZTOT_RDF_SPECIES or AZTOT_RDF_NUCLEI");
+    if (kind == 1 && !R.nuclei) throw ArgError("rdf: nuclei histograms were not requested at aztot_rdf_setup");
+    nBins = R.nBins;
+    nPairs = kind ? R.grid.nPairN : R.grid.nPairS;
+    samples = R.samples;
+    if (!counts) return;
+    counts->resize((size_t)nBins * nPairs);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(counts->data(), kind ? R.histN : R.histS, counts->size() * 8, hipMemcpyDeviceToHost));
+}
+
+// g(r) as copy_rdf / copy_nrdf / out_rdf (cuStat.cu:514-560,719-760; rdf.cpp:128-175):
+//   g = count * V / (nA nB) * 2 / (sphera dr^3 samples) / (3 i (i + 1) + 1) * C3,   C3 = 1 for A-A, 0.5 for A-B;  0 where nA nB = 0 or no sample
+void Samplers::rdf_values(int kind, std::vector<double>& r, std::vector<double>& g)
+{
+    int nBins = 0, nPairs = 0;
+    long long samples = 0;
+    std::vector<unsigned long long> c;
+    rdf_counts(kind, nBins, nPairs, samples, &c);
+    std::vector<double> num;
+    if (kind == 0) for (const auto& s : model_.species) num.push_back((double)s.number);
+    else for (int v : nuclei_.number) num.push_back((double)v);
+    const int n = (int)num.size();
+    const double sphera = 4.0 * units::pi / 3.0;                        // const.h:15
+    const double dr = rdf_.dr, V = box_.L[0] * box_.L[1] * box_.L[2];
+    const double C1 = samples > 0 ? 2.0 / (sphera * dr * dr * dr * (double)samples) : 0.0;
+    r.resize(nBins);
+    g.assign((size_t)nBins * nPairs, 0.0);
+    for (int i = 0; i < nBins; i++)
+    {
+        r[i] = (i + 0.5) * dr;
+        const double C2 = 1.0 / (3.0 * i * (i + 1.0) + 1.0);
+        int p = 0;
+        for (int a = 0; a < n; a++)
+            for (int b = a; b < n; b++, p++)
+            {
+                const double nAnB = num[a] * num[b];
+                if (nAnB == 0.0) continue;
+                const double C3 = a == b ? 1.0 : 0.5;
+                g[(size_t)i * nPairs + p] = (double)c[(size_t)i * nPairs + p] * V / nAnB * C1 * C2 * C3;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Coordination numbers (cn.hip.h; the rules of the two kinds are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+void Samplers::cn_setup(int kind, const aztot_cn_column* cols, int nCols)
+{
+    need_one_gpu("coordination numbers");
+    cn_state(kind, false, false);
+    if (!cols || nCols <= 0) throw ArgError("cn: no columns");
+    const int nGroups = kind == AZTOT_CN_SPECIES ? model_.nSpec() : (int)nuclei_.names.size();
+    CnState T;
+    std::vector<int32_t> slotOf(kSpecCap * kSpecCap, -1);
+    std::vector<double> r2Of(kSpecCap * kSpecCap, 0.0), rowMax(kSpecCap, -1.0);
+    double rBig = 0.0;
+    for (int c = 0; c < nCols; c++)
+    {
+        const aztot_cn_column& col = cols[c];
+        if (col.central < 0 || col.central >= nGroups || col.ligand < 0 || col.ligand >= nGroups) throw ArgError("cn: group index of a column out of range");
+        if (!(col.radius > 0.0) || !std::isfinite(col.radius)) throw ArgError("cn: the radius of a column must be positive");
+        if (kind == AZTOT_CN_SPECIES && col.radius != cols[0].radius) throw ArgError("cn: AZTOT_CN_SPECIES columns share one radius (outCN has one)");
+        const int e = col.central * kSpecCap + col.ligand;
+        if (slotOf[e] >= 0) throw ArgError("cn: the same (central, ligand) pair names two columns");
+        const int q = T.nLive[col.central]++;           // (<= nGroups <= kCnLive: every ligand of a central group is distinct)
+        slotOf[e] = q;
+        r2Of[e] = col.radius * col.radius;
+        rowMax[col.central] = std::max(rowMax[col.central], r2Of[e]);
+        T.colOf[col.central * kCnLive + q] = c;
+        T.par.maxLive = std::max(T.par.maxLive, q + 1);
+        rBig = std::max(rBig, col.radius);
+    }
+    T.cols.assign(cols, cols + nCols);
+    T.par.shift = kind == AZTOT_CN_SPECIES ? 0 : 8;
+    T.par.inclusive = kind == AZTOT_CN_SPECIES ? 1 : 0;
+    T.par.countSelf = kind == AZTOT_CN_SPECIES ? 1 : 0;
+    T.par.nCols = nCols;
+    // lanes per atom: enough of them that a small system still fills the chip (256 CUs x 4 waves of 64 at the least), never more than one wave
+    const int N = model_.nAt;
+    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    T.rowsCap = 64;
+    set_up(cn_[kind], T, [&] {
+        CnState& S = T;
+        grid_setup(S, rBig);
+        const size_t n = (size_t)std::max(N, 1);
+        S.slotId = S.mem.alloc<int32_t>(n, false, stream_);
+        S.counts = S.mem.alloc<int32_t>(n * (size_t)S.par.maxLive, false, stream_);
+        S.range = S.mem.alloc<int32_t>(2, false, stream_);
+        S.dSlotOf = S.mem.alloc<int32_t>(slotOf.size(), false, stream_); S.dR2Of = S.mem.alloc<double>(r2Of.size(), false, stream_);
+        S.dRowMax = S.mem.alloc<double>(rowMax.size(), false, stream_);
+        S.dNLive = S.mem.alloc<int32_t>(kSpecCap, false, stream_); S.dColOf = S.mem.alloc<int32_t>(kSpecCap * kCnLive, false, stream_);
+        HIP_CHECK(hipMemcpy(S.dSlotOf, slotOf.data(), slotOf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(S.dR2Of, r2Of.data(), r2Of.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(S.dRowMax, rowMax.data(), rowMax.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(S.dNLive, S.nLive, sizeof(S.nLive), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(S.dColOf, S.colOf, sizeof(S.colOf), hipMemcpyHostToDevice));
+        S.table = S.tableMem.alloc<unsigned long long>((size_t)S.rowsCap * nCols, false, stream_);
+    });
+}
+
+template <int NL>
+static void launch_cn_pairs(hipStream_t stream, int blocks, const RdfGrid& G, const CnParams& C, int N, int sliceShift, const int32_t* cellStart, const double* x,
+                            const double* y, const double* z, const int32_t* kind, const int32_t* slotOf, const double* r2Of, const double* rowMax, int32_t* counts)
+{
+    hipLaunchKernelGGL(k_cn_pairs<NL>, dim3(blocks), dim3(kBlock), 0, stream, G, C, N, sliceShift, cellStart, x, y, z, kind, slotOf, r2Of, rowMax, counts);
+}
+
+void Samplers::cn_sample(int kind)
+{
+    CnState& S = cn_state(kind, true, false);
+    sample("cn table", [&](const AtomArrays& A) {
+        const int N = model_.nAt;
+        const CnParams& C = S.par;
+        // rows of the file: out_cn starts its maximum at 0 and writes from CN = 0 (out_md.cpp:392,486); out_ncn starts from mn = 10, mx = 0 (out_md.cpp:300)
+        int range[2] = {kind == AZTOT_CN_SPECIES ? 0 : 10, 0};
+        S.sampled = false;
+        S.cnMin = range[0]; S.cnMax = range[1];
+        if (N == 0) return;
+        static const char* const names[3] = {"k_cn_bin", "k_cn_scan", "k_cn_place"};
+        grid_fill(S, A, names);
+        const int nb = div_up(N, kBlock);
+        timed("k_cn_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId); });
+        const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
+        timed("k_cn_pairs", [&] {
+            auto go = [&](auto nl) {
+                launch_cn_pairs<decltype(nl)::value>(stream_, blocks, S.grid, C, N, S.sliceShift, S.cellStart, S.x, S.y, S.z, S.kind, S.dSlotOf, S.dR2Of, S.dRowMax, S.counts);
+            };
+            if (C.maxLive <= 1) go(std::integral_constant<int, 1>());
+            else if (C.maxLive <= 2) go(std::integral_constant<int, 2>());
+            else if (C.maxLive <= 4) go(std::integral_constant<int, 4>());
+            else if (C.maxLive <= 8) go(std::integral_constant<int, 8>());
+            else go(std::integral_constant<int, kCnLive>());
+        });
+        HIP_CHECK(hipMemcpyAsync(S.range, range, sizeof(range), hipMemcpyHostToDevice, stream_));
+        const int gs = std::max(1, std::min(kCnMaxBlocks, nb));
+        timed("k_cn_range", [&] { hipLaunchKernelGGL(k_cn_range, dim3(gs), dim3(kBlock), 0, stream_, C, N, S.kind, S.dNLive, S.counts, S.range); });
+        HIP_CHECK(hipMemcpyAsync(range, S.range, sizeof(range), hipMemcpyDeviceToHost, stream_));
+        host_.end_sample("cn kernels");     // the table's rows are sized on the host from the range just read back
+        S.cnMin = range[0]; S.cnMax = range[1];
+        const int rows = S.cnMax - S.cnMin + 1;
+        if (rows <= 0) return;
+        if ((double)rows * C.nCols > (double)(1 << 28)) throw ArgError("cn: table too large (rows x columns > 2^28)");
+        if (rows > S.rowsCap)
+        {
+            S.rowsCap = rows + rows / 2;
+            S.tableMem = DeviceArena();
+            S.table = S.tableMem.alloc<unsigned long long>((size_t)S.rowsCap * C.nCols, false, stream_);
+        }
+        const size_t ent = (size_t)rows * C.nCols;
+        HIP_CHECK(hipMemsetAsync(S.table, 0, ent * 8, stream_));
+        const int useLds = ent * sizeof(uint32_t) <= (size_t)kCnLdsBudget ? 1 : 0;
+        timed("k_cn_table", [&] {
+            hipLaunchKernelGGL(k_cn_table, dim3(gs), dim3(kBlock), useLds ? ent * sizeof(uint32_t) : 0, stream_, C, N, S.kind, S.dNLive, S.dColOf, S.counts, S.cnMin,
+                               rows, useLds, S.table);
+        });
+    });
+    S.sampled = true;
+}
+
+void Samplers::cn_shape(int kind, int& nCols, int& cnMin, int& cnMax)
+{
+    const CnState& S = cn_state(kind, true, true);
+    nCols = S.par.nCols; cnMin = S.cnMin; cnMax = S.cnMax;
+}
+
+void Samplers::cn_per_atom(int kind, std::vector<int32_t>& out)
+{
+    const CnState& S = cn_state(kind, true, true);
+    const int N = model_.nAt, nCols = S.par.nCols, ml = S.par.maxLive;
+    out.assign((size_t)N * nCols, -1);
+    if (N == 0) return;
+    std::vector<int32_t> ids(N), kinds(N), cnt((size_t)N * ml);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(ids.data(), S.slotId, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(kinds.data(), S.kind, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(cnt.data(), S.counts, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost));
+    for (int s = 0; s < N; s++)
+    {
+        const int g = (kinds[s] >> S.par.shift) & 255;
+        for (int q = 0; q < S.nLive[g]; q++) out[(size_t)ids[s] * nCols + S.colOf[g * kCnLive + q]] = cnt[(size_t)s * ml + q];
+    }
+}
+
+void Samplers::cn_table(int kind, std::vector<long long>& out)
+{
+    const CnState& S = cn_state(kind, true, true);
+    const int rows = std::max(0, S.cnMax - S.cnMin + 1);
+    out.assign((size_t)rows * S.par.nCols, 0);
+    if (out.empty() || model_.nAt == 0) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(out.data(), S.table, out.size() * 8, hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Time correlation functions (tcf.hip.h; terms, summation tree and ring of origins are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+int Samplers::tcf_setup(int nOrigins, int originEvery)
+{
+    need_one_gpu("time correlation functions");
+    if (nOrigins < 1 || originEvery < 1) throw ArgError("tcf: n_origins and origin_every must be at least 1");
+    if ((long long)nOrigins * originEvery > AZTOT_TCF_MAX_LAGS) throw ArgError("tcf: too many lags (n_origins x origin_every > 2^24)");
+    TcfState T;
+    T.M = nOrigins; T.E = originEvery; T.nSpec = model_.nSpec();
+    T.nChunk = std::max(1, div_up(model_.nAt, kTcfChunk));
+    T.nChunkPad = 1;
+    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
+    T.nPad = (size_t)T.nChunk * kTcfChunk;
+    set_up(tcf_, T, [&] {
+        const size_t nAcc = (size_t)T.n_lags() * T.nSpec;
+        T.cur = T.mem.alloc<double>(6 * T.nPad, true, stream_);
+        T.ring = T.mem.alloc<double>((size_t)T.M * 6 * T.nPad, true, stream_);
+        T.type = T.mem.alloc<int32_t>(T.nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.type, 0xff, sizeof(int32_t) * T.nPad, stream_));
+        T.partials = T.mem.alloc<double>((size_t)T.M * 2 * T.nSpec * T.nChunkPad, true, stream_);
+        T.msdSum = T.mem.alloc<double>(nAcc, true, stream_); T.vafSum = T.mem.alloc<double>(nAcc, true, stream_);
+        T.count = T.mem.alloc<long long>((size_t)T.n_lags(), true, stream_);
+    });
+    return tcf_.n_lags();
+}
+
+void Samplers::tcf_reset()
+{
+    TcfState& T = tcf_state();
+    const size_t nAcc = (size_t)T.n_lags() * T.nSpec;
+    HIP_CHECK(hipMemsetAsync(T.msdSum, 0, nAcc * 8, stream_));
+    HIP_CHECK(hipMemsetAsync(T.vafSum, 0, nAcc * 8, stream_));
+    HIP_CHECK(hipMemsetAsync(T.count, 0, (size_t)T.n_lags() * 8, stream_));
+    T.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Samplers::tcf_sample()
+{
+    TcfState& T = tcf_state();
+    sample("tcf kernels", [&](const AtomArrays& A) {
+        const int N = model_.nAt;
+        const long long c = T.samples;
+        TcfBox B;
+        for (int k = 0; k < 3; k++) { B.L[k] = box_.L[k]; B.invL[k] = box_.invL[k]; B.half[k] = box_.half[k]; }
+        const bool isOrigin = c % T.E == 0;
+        double* org = isOrigin ? T.ring + (size_t)((c / T.E) % T.M) * 6 * T.nPad : nullptr;
+        if (N > 0)
+            timed("k_tcf_gather", [&] { hipLaunchKernelGGL(k_tcf_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, B, A, N, T.nPad, T.cur, org, T.type); });
+        const int nLive = (int)std::min<long long>(c / T.E + 1, T.M);
+        timed("k_tcf_correlate", [&] {
+            hipLaunchKernelGGL(k_tcf_correlate, dim3(T.nChunk), dim3(kBlock), 0, stream_, B, T.nSpec, T.nPad, T.nChunkPad, nLive, T.cur, T.type, T.ring, T.partials);
+        });
+        timed("k_tcf_fold", [&] {
+            hipLaunchKernelGGL(k_tcf_fold, dim3(nLive * 2 * T.nSpec), dim3(kBlock), 0, stream_, T.nSpec, T.nChunkPad, c, T.E, T.M, T.partials, T.count, T.msdSum, T.vafSum);
+        });
+    });
+    T.samples++;
+}
+
+void Samplers::tcf_shape(int& nLags, int& nSpec, long long& samples)
+{
+    const TcfState& T = tcf_state();
+    nLags = T.n_lags(); nSpec = T.nSpec; samples = T.samples;
+}
+
+void Samplers::tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf)
+{
+    const TcfState& T = tcf_state();
+    if (lag0 < 0 || n < 0 || (long long)lag0 + n > T.n_lags()) throw ArgError("tcf: lag range outside [0, n_lags)");
+    const size_t nv = (size_t)n * T.nSpec, at = (size_t)lag0 * T.nSpec;
+    if (count) count->assign((size_t)n, 0);
+    if (msd) msd->assign(nv, 0.0);
+    if (vaf) vaf->assign(nv, 0.0);
+    if (n == 0) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (count) HIP_CHECK(hipMemcpy(count->data(), T.count + lag0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (msd && nv) HIP_CHECK(hipMemcpy(msd->data(), T.msdSum + at, nv * 8, hipMemcpyDeviceToHost));
+    if (vaf && nv) HIP_CHECK(hipMemcpy(vaf->data(), T.vafSum + at, nv * 8, hipMemcpyDeviceToHost));
+}
+
+// displ / number and vaf / number of the reference (out_md.cpp:120,577-579), over all pairs of a lag: sum / (count * n_s); 0 where count * n_s == 0
+void Samplers::tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf)
+{
+    std::vector<long long> count;
+    tcf_sums(lag0, n, &count, &msd, &vaf);
+    const int nSpec = tcf_.nSpec;
+    for (int l = 0; l < n; l++)
+        for (int s = 0; s < nSpec; s++)
+        {
+            const long long w = count[l] * (long long)model_.species[s].number;
+            const size_t e = (size_t)l * nSpec + s;
+            msd[e] = w ? msd[e] / (double)w : 0.0;
+            vaf[e] = w ? vaf[e] / (double)w : 0.0;
+        }
+}
+
+}  // namespace aztot
