@@ -578,11 +578,11 @@ void ListStore::allocate(int candCapNew, int iterCapNew)
     candCapNew = std::max(kListMinCand * waves, std::min((candCapNew + 63) & ~63, kListCandMax));
     iterCapNew = std::max(kListMinIter, std::min((iterCapNew + 7) & ~7, kListIterMax));
     PairLists probe;
-    probe.candCap = probe.candLds = candCapNew; probe.iterCap = probe.iterLds = iterCapNew; probe.recBytes = pair_list_rec_bytes(P); probe.waves = waves;
+    probe.candCap = probe.candLds = probe.stageLds = candCapNew; probe.iterCap = probe.iterLds = iterCapNew; probe.recBytes = pair_list_rec_bytes(P); probe.waves = waves;
     while (candCapNew > kListMinCand && (pair_list_lds_bytes(P, probe) > ldsMax_ || build_lists_lds_bytes(probe) > ldsMax_))
     {
         candCapNew -= 64;
-        probe.candCap = probe.candLds = candCapNew;
+        probe.candCap = probe.candLds = probe.stageLds = candCapNew;
     }
     while (iterCapNew > 2 * kListMinIter && build_lists_lds_bytes(probe) > ldsMax_) { iterCapNew -= 8; probe.iterCap = probe.iterLds = iterCapNew; }
     const size_t nc = (size_t)P.nCellLocal;
@@ -591,7 +591,7 @@ void ListStore::allocate(int candCapNew, int iterCapNew)
     pairs = mem_.alloc<uint16_t>(nc * (size_t)waves * (size_t)iterCapNew * kWave, true, stream_);   // every entry is a tile offset at all times (k_pair_list reads ahead)
     report = mem_.alloc<int32_t>(LR_COUNT, true, stream_); rel = mem_.alloc<float4>((size_t)capacity_ + kWave, true, stream_);
     candCap = candCapNew; iterCap = iterCapNew;
-    candLds = candCapNew; iterLds = iterCapNew;          // (tightened once the builder has reported what the cells really hold: tighten / adapt)
+    candLds = stageLds = candCapNew; iterLds = iterCapNew;          // (tightened once the builder has reported what the cells really hold: tighten / adapt)
     {   // header: -1 = no list ; second word: the cell's coordinates in the local grid (the kernels decode them with shifts)
         std::vector<int32_t> mx(4 * nc, 0);
         const int ncy = P.nc[1], ncz = P.nc[2];
@@ -634,13 +634,13 @@ PairLists ListStore::pair_lists() const
     if (on)
     {
         pl.cand = cand; pl.meta = meta; pl.pairs = pairs; pl.noList = report;
-        pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.entryScale = pair_list_entry_scale(*P_); pl.waves = waves;
+        pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.stageLds = stageLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.entryScale = pair_list_entry_scale(*P_); pl.waves = waves;
         pl.rel = rel;
     }
     return pl;
 }
 
-// Records of k_pair_list's LDS tile for cells of at most maxT candidates.  LDS per wave bounds the kernel's occupancy and the hardware hands LDS out in
+// Records of k_pair_list's LDS tile for cells that keep at most maxT candidates.  LDS per wave bounds the kernel's occupancy and the hardware hands LDS out in
 // blocks of 1 280 B (gfx950: 160 KiB in 128 blocks), so the tile is the largest one that costs no more blocks than the smallest one that would do
 // (largest cell + 1 % + 1): C4's largest tile of 305 candidates gives 319 records in six blocks - 21 waves per CU by LDS - where "largest + 4 % + 6" took seven.
 int ListStore::tile_records_for(int maxT) const
@@ -651,6 +651,9 @@ int ListStore::tile_records_for(int maxT) const
     //  what bounds a step of a few thousand cells: + 6 %)
     const bool roomy = P_->nranks == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
     const int need = std::max(4 * kWave, std::min(candCap, roomy ? maxT + maxT / 16 + 4 : maxT + maxT / 100 + 1));
+    // (a tile of up to 256 records is served by the kernel that gathers four groups of candidates up front instead of five: never a few records more than
+    //  that for the sake of a full LDS block)
+    if (need <= 4 * kWave) return need;
     L.candLds = need;
     const size_t blocks = (pair_list_lds_bytes(*P_, L) + kLdsBlock - 1) / kLdsBlock;
     int best = need;
@@ -663,21 +666,29 @@ int ListStore::tile_records_for(int maxT) const
     return best;
 }
 
-// LDS per wave is what bounds the occupancy of k_pair_list: the tiles are sized from the largest cell ever recorded (+ 6 %), not from the capacity of
-// the arrays; the builder's list buffer from the longest list (+ 1/8)
-void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& iterLdsNew) const
+// The builder's staging area for cells that stage at most maxStaged candidates (+ 6 %; the builder rounds it up to whole mask words of 128 anyway, so this
+// does too: its LDS bounds nothing that runs every step)
+int ListStore::stage_records_for(int maxStaged) const
+{
+    return std::max(4 * kWave, std::min(candCap, (maxStaged + maxStaged / 16 + 4 + 127) & ~127));
+}
+
+// LDS per wave is what bounds the occupancy of k_pair_list: its tile is sized from the largest KEPT candidate set ever recorded, not from the capacity of
+// the arrays; the builder's staging area from the largest STAGED set, its list buffer from the longest list (+ 1/8)
+void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& stageLdsNew, int& iterLdsNew) const
 {
     candLdsNew = tile_records_for(rep[LR_MAX_TILE]);
+    stageLdsNew = stage_records_for(rep[LR_MAX_STAGED]);
     iterLdsNew = std::max(2 * kListMinIter, std::min(iterCap, (rep[LR_MAX_ITERS] + rep[LR_MAX_ITERS] / 8 + 2 + 7) & ~7));
 }
 
 bool ListStore::tighten(const int32_t* rep)
 {
-    if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_MAX_TILE] <= 0) return false;
-    int c, i;
-    lds_for(rep, c, i);
-    if (c >= candLds && i >= iterLds) return false;
-    candLds = std::min(candLds, c); iterLds = std::min(iterLds, i);
+    if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_KEPT_FULL] != 0 || rep[LR_MAX_STAGED] <= 0) return false;
+    int c, s, i;
+    lds_for(rep, c, s, i);
+    if (c >= candLds && s >= stageLds && i >= iterLds) return false;
+    candLds = std::min(candLds, c); stageLds = std::min(stageLds, s); iterLds = std::min(iterLds, i);
     return true;
 }
 
@@ -689,22 +700,25 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
     const bool frozen = debug & DBG_SHORT_LISTS;
     if (debug & DBG_LIST_STATS)
     {   // measurement aid: mean list length / tile size / atoms per cell over the cells recorded since the last look
-        std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates, %.2f atoms\n", (double)rep[LR_SUM_ITERS] / rep[LR_RECORDED], (double)rep[LR_SUM_CANDS] / rep[LR_RECORDED], (double)rep[LR_SUM_ATOMS] / rep[LR_RECORDED]);
-        HIP_CHECK(hipMemset(&report[LR_SUM_ITERS], 0, sizeof(int32_t) * 3));
+        std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates staged, %.1f kept, %.2f atoms\n", (double)rep[LR_SUM_ITERS] / rep[LR_RECORDED],
+                     (double)rep[LR_SUM_STAGED] / rep[LR_RECORDED], (double)rep[LR_SUM_CANDS] / rep[LR_RECORDED], (double)rep[LR_SUM_ATOMS] / rep[LR_RECORDED]);
+        HIP_CHECK(hipMemset(&report[LR_SUM_ITERS], 0, sizeof(int32_t) * 4));
     }
     // (LR_UNLISTED_NOW stays: it describes the lists in force; the maxima are all-time)
     HIP_CHECK(hipMemsetAsync(&report[LR_UNLISTED], 0, sizeof(int32_t) * 2, stream_));
-    HIP_CHECK(hipMemsetAsync(&report[LR_TILE_FULL], 0, sizeof(int32_t) * 2, stream_));
-    const int tileFull = rep[LR_TILE_FULL], listFull = rep[LR_LIST_FULL], recorded = rep[LR_RECORDED], unlisted = rep[LR_UNLISTED];
+    HIP_CHECK(hipMemsetAsync(&report[LR_TILE_FULL], 0, sizeof(int32_t) * 3, stream_));
+    // ("tile full": the staged candidates did not fit the builder's staging area; "kept full": the kept ones did not fit the tile of k_pair_list)
+    const int tileFull = rep[LR_TILE_FULL], keptFull = rep[LR_KEPT_FULL], listFull = rep[LR_LIST_FULL], recorded = rep[LR_RECORDED], unlisted = rep[LR_UNLISTED];
     if (std::getenv("AZTOT_VERBOSE"))
-        std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: tile full, %d: list full); largest tile %d of %d (LDS %d), longest list %d of %d (LDS %d)\n",
-                     recorded, unlisted, tileFull, listFull, rep[LR_MAX_TILE], candCap, candLds, rep[LR_MAX_ITERS], iterCap, iterLds);
+        std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: staging full, %d: tile full, %d: list full); most staged %d of %d (LDS %d), largest tile %d (LDS %d), longest list %d of %d (LDS %d)\n",
+                     recorded, unlisted, tileFull, keptFull, listFull, rep[LR_MAX_STAGED], candCap, stageLds, rep[LR_MAX_TILE], candLds, rep[LR_MAX_ITERS], iterCap, iterLds);
     // A cell that does not fit next time keeps no list for one interval (exact: the clean-up launch serves it) and is counted; then the tiles grow again.
-    int candLdsNew, iterLdsNew;
-    lds_for(rep, candLdsNew, iterLdsNew);
-    if (tileFull > 0) candLdsNew = std::min(candCap, std::max(candLdsNew, candLds + 32));
+    int candLdsNew, stageLdsNew, iterLdsNew;
+    lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew);
+    if (tileFull > 0) stageLdsNew = std::min(candCap, std::max(stageLdsNew, stageLds + 128));
+    if (keptFull > 0) candLdsNew = std::min(candCap, std::max(candLdsNew, candLds + 32));
     if (listFull > 0) iterLdsNew = std::min(iterCap, std::max(iterLdsNew, iterLds + 8));
-    if (frozen) { candLdsNew = candLds; iterLdsNew = iterLds; }
+    if (frozen) { candLdsNew = candLds; stageLdsNew = stageLds; iterLdsNew = iterLds; }
     // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
     // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
     const int wWant = std::max(waves, waves_wanted((double)rep[LR_MAX_TILE], rep[LR_MAX_ITERS]));
@@ -717,23 +731,23 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
         v.rebuild = v.launchChanged = true;
         return v;
     }
-    const bool capFull = (tileFull > 0 && candLds == candCap) || (listFull > 0 && iterLds == iterCap);
+    const bool capFull = (tileFull > 0 && stageLds == candCap) || (keptFull > 0 && candLds == candCap) || (listFull > 0 && iterLds == iterCap);
     // (one GPU: ANY cell that does not fit costs an engine that runs without the clean-up launch a window of steps run again, so the arrays grow at once
     //  while they still can; slab ranks and the last growth wait until it is more than a handful)
-    if (capFull && !frozen && (double)(tileFull + listFull) > ((P_->nranks == 1 && growths < 3) ? 0.0 : 0.0005 * (double)recorded))
+    if (capFull && !frozen && (double)(tileFull + keptFull + listFull) > ((P_->nranks == 1 && growths < 3) ? 0.0 : 0.0005 * (double)recorded))
     {   // the arrays themselves are too small: larger ones if the limits allow (twice), and the next step rebuilds; else - cells of more than 64 atoms
         // never fit - the plain steps go back to staging once that is more than 2 % of the cells
-        const int candNew = tileFull > 0 ? std::min(kListCandMax, (candCap * 3 / 2 + 63) & ~63) : candCap;
+        const int candNew = tileFull + keptFull > 0 ? std::min(kListCandMax, (candCap * 3 / 2 + 63) & ~63) : candCap;
         const int itersNew = listFull > 0 ? std::min(kListIterMax, (iterCap * 2 + 7) & ~7) : iterCap;
         v.launchChanged = true;
         if (growths < 3 && (candNew > candCap || itersNew > iterCap)) { growths++; regrow(candNew, itersNew); v.rebuild = true; }
     }
-    else if (candLdsNew != candLds || iterLdsNew != iterLds)
+    else if (candLdsNew != candLds || stageLdsNew != stageLds || iterLdsNew != iterLds)
     {
-        candLds = candLdsNew; iterLds = iterLdsNew;
+        candLds = candLdsNew; stageLds = stageLdsNew; iterLds = iterLdsNew;
         v.launchChanged = true;               // (launch parameters are baked into the graphs)
     }
-    if (on && (double)unlisted > 0.02 * (double)recorded && !frozen && tileFull + listFull < unlisted / 2)
+    if (on && (double)unlisted > 0.02 * (double)recorded && !frozen && tileFull + keptFull + listFull < unlisted / 2)
     {   // mostly cells of more than 64 atoms: no list will ever hold them
         on = false;
         v.launchChanged = true;

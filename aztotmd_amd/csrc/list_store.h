@@ -27,7 +27,9 @@ struct ListStore
     int32_t* report = nullptr;      // [LR_COUNT] the builder's report (enum ListReport, pair_tile.hip.h)
     float4* rel = nullptr;          // [capacity + 64] position relative to the own cell's centre (f32) + cell z index, written by the sort for the list builder
     int candCap = 0, iterCap = 0;   // capacities of the lists per cell (PairLists); grown when too many cells turn out not to fit
-    int candLds = 0, iterLds = 0;   // what the LDS tiles of k_pair_list / k_build_lists are sized for (<= the capacities; from the largest cell recorded)
+    int candLds = 0, iterLds = 0;   // what the LDS tile of k_pair_list (the candidates a cell KEEPS) and the builder's list buffer are sized for (<= the capacities;
+                                    // from the largest cell recorded)
+    int stageLds = 0;               // what the builder's staging area is sized for: the candidates a cell STAGES before the unreachable ones are dropped (<= candCap)
     int waves = 1;                  // waves per cell in k_pair_list (PairLists::waves)
     int growths = 0;
 
@@ -39,7 +41,7 @@ struct ListStore
     void release() noexcept;        // behind a stream synchronisation
     PairLists pair_lists() const;   // what the kernels are launched with (all-null when off)
     // LDS sizes that hold the largest cell of a report
-    void lds_for(const int32_t* rep, int& candLds, int& iterLds) const;
+    void lds_for(const int32_t* rep, int& candLds, int& stageLds, int& iterLds) const;
     // the first lists of an engine's life: tighter LDS sizes right away, if every cell fitted.  True when they changed
     bool tighten(const int32_t* rep);
     // at a look, for a report with cells recorded: tighten or widen the LDS sizes, more waves per cell, larger arrays, or give up
@@ -48,6 +50,7 @@ struct ListStore
 private:
     void allocate(int candCap, int iterCap);
     int tile_records_for(int maxT) const;
+    int stage_records_for(int maxStaged) const;
     int waves_wanted(double tileRecords, int iters) const;
     DeviceArena mem_;
     const StepParams* P_ = nullptr; // the engine's (outlives the store)

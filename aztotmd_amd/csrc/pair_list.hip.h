@@ -3,7 +3,7 @@
 //
 // Replaces the reference's cell_list5a + cell_list4b_noshared + pair_1 (cuPairs.cu:2266,1474,117).  The reference rebuilds everything every step
 // (main.cu:300-326); here the cells are rebuilt every K-th step only (Engine::step) and the rebuild leaves two lists per cell:
-//   * the candidates: every atom of the cell's stencil within rc + skin of the cell's box (atom index + periodic image code, tile order), and
+//   * the candidates: every atom of the cell's stencil within rc + skin of at least one atom of the cell (atom index + periodic image code, tile order), and
 //   * for every atom of the cell its partners among them - the candidates within rc + skin of the atom -, dealt round-robin to the lanes that
 //     serve the atom.  An entry is the byte offset of the candidate's record in the LDS tile of k_pair_list.
 // Until the next rebuild atoms keep their slots and nobody moves farther than skin / 2 (checked every step by whoever integrates; a violation makes
@@ -22,8 +22,11 @@
 
 namespace aztot {
 
-constexpr int kListPreload = 5;            // groups of 64 candidate entries every wave of k_pair_list asks for before it knows the cell's T (candCap >= 320)
+constexpr int kListPreload = 5;            // most groups of 64 candidate entries a wave of k_pair_list asks for before it knows the cell's T (candCap >= 320)
 constexpr int kListMinCand = 64 * kListPreload;
+// groups gathered up front by every wave of k_pair_list, a compile-time parameter of the kernel: four cover a tile of up to 256 records (a liquid's cells
+// of rc + skin keep ~160 candidates, never more than ~210), five the larger ones; the builder pads the candidate array to that many groups
+__host__ __device__ inline int list_preload(int candLds) { return candLds <= 4 * kWave ? 4 : kListPreload; }
 constexpr int kListMinIter = 16;           // two chunks of 8 iterations are asked for up front
 constexpr int kListMaxSlices = 32;         // slices per atom (a cell of one or two atoms still uses half a wave)
 
@@ -61,7 +64,8 @@ inline int pair_list_entry_scale(const StepParams& P) { return P.single_lj ? 24 
 // cell on the 1 M-atom liquid); true: W = PairLists::waves waves share the cell's tile.
 // TSTAT = true (launches that fuse the next step in a run with the radiative thermostat; never with ENG: the call's last step does not fuse): the epilogue
 // applies the thermostat between closing this step and opening the next, operation for operation what k_boundary_radi does in a launch of its own.
-template <int MODE, int VDW, bool ENG, bool MULTI, bool TSTAT = false>
+// PRE: groups of candidates gathered up front (list_preload: 4 for tiles of up to 256 records, else 5).
+template <int MODE, int VDW, bool ENG, bool MULTI, bool TSTAT = false, int PRE = kListPreload>
 __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_list(StepParams P, SpecTable S, const DevPot* __restrict__ pots, AtomArrays A,
                                                      const int32_t* __restrict__ cellStart, int firstCell, int nCellsRun,
                                                      double* __restrict__ partials, int maxBlocks, const Counts* __restrict__ counts, int blockBase, PairLists L,
@@ -88,15 +92,15 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     NextAcc nacc;                                                    // (touched only in launches that fuse the next step: no initialisation on the others)
     if (N.xn) next_acc_clear(nacc);
     // everything that depends on the cell number only is requested at once, before anything is known about the cell (the loads stay inside the
-    // arrays whatever they return): list header, five groups of candidate entries, the lane's first two list chunks.  A wave's life is then two
+    // arrays whatever they return): list header, PRE groups of candidate entries, the lane's first two list chunks.  A wave's life is then two
     // memory round trips (these, then the coordinates) and the loop
     const int cell = firstCell + min(cr, nCellsRun - 1);
-    // (candidate groups are dealt to the waves round-robin: wave w gathers groups w, w + W, ...; candCap >= 64 * 5 * W keeps the five preloads inside the array)
+    // (candidate groups are dealt to the waves round-robin: wave w gathers groups w, w + W, ...; candCap >= 64 * 5 * W keeps the preloads inside the array)
     const uint32_t* const myList = L.cand + (size_t)cell * L.candCap + lane;
     const uint4* const pl = (const uint4*)(L.pairs + ((size_t)cell * W + wave) * L.iterCap * kWave) + lane;
-    uint32_t ent[kListPreload];
+    uint32_t ent[PRE];
 #pragma unroll
-    for (int u = 0; u < kListPreload; u++) ent[u] = myList[(wave + u * W) * kWave];
+    for (int u = 0; u < PRE; u++) ent[u] = myList[(wave + u * W) * kWave];
     uint4 w = pl[0];
     uint4 w1 = pl[kWave];                                           // (the second chunk too: 16 iterations cover a liquid's cells, and a chunk asked for only
                                                                     //  8 iterations ahead arrives late)
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         int ti = 0;
         if (!kOneSpecies) ti = A.type[myl];
         if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) radi = A.rad[myl];
-        // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  Five groups are gathered whatever T is (stale
+        // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  PRE groups are gathered whatever T is (stale
         // entries are atom indices too: the array starts out zeroed and only indices are ever written); all their loads travel together
         {
             const int gx0 = lx + P.cx0;
@@ -183,17 +187,29 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
                 if (kRadii) trad[u * kWave + lane + 1] = c.rad;
                 if (MODE == PM_GENERIC) ttyp0[u * kWave + lane + 1] = (uint8_t)c.typ;
             };
-            // this wave's groups are wave + q W, q = 0, 1, ...  Five of them are gathered whatever T is - straight-line code, fifteen loads in flight together
-            // (the builder fills all five groups of the array: behind the last candidate with the cell's first atom, one cache line for the whole wave)
-            const Cand c0 = fetch(ent[0]), c1 = fetch(ent[1]), c2 = fetch(ent[2]), c3 = fetch(ent[3]), c4 = fetch(ent[4]);
+            // this wave's groups are wave + q W, q = 0, 1, ...  PRE of them are gathered whatever T is - straight-line code, 3 PRE loads in flight together
+            // (the builder fills all PRE groups of the array: behind the last candidate with the cell's first atom, one cache line for the whole wave.
+            //  Skipping the last group's fetch behind a wave-uniform test of T where it holds only padding - most cells of a liquid - was measured: ~1 us of
+            //  85 on the 1 M-atom box, inside the spread of the runs at 85 K: not kept, NOTES.md)
+            Cand cd[PRE];
+#pragma unroll
+            for (int u = 0; u < PRE; u++) cd[u] = fetch(ent[u]);
             using ImgYes = std::integral_constant<bool, true>;
             using ImgNo = std::integral_constant<bool, false>;
             // (two copies of the straight-line code rather than a wave-uniform branch inside every put: interior cells - nearly all - shift nothing)
-            if (images) { put(ImgYes(), wave, ent[0], c0); put(ImgYes(), wave + W, ent[1], c1); put(ImgYes(), wave + 2 * W, ent[2], c2); put(ImgYes(), wave + 3 * W, ent[3], c3); put(ImgYes(), wave + 4 * W, ent[4], c4); }
-            else { put(ImgNo(), wave, ent[0], c0); put(ImgNo(), wave + W, ent[1], c1); put(ImgNo(), wave + 2 * W, ent[2], c2); put(ImgNo(), wave + 3 * W, ent[3], c3); put(ImgNo(), wave + 4 * W, ent[4], c4); }
-            if (T > kListPreload * W * kWave)
+            if (images)
+            {
+#pragma unroll
+                for (int u = 0; u < PRE; u++) put(ImgYes(), wave + u * W, ent[u], cd[u]);
+            }
+            else
+            {
+#pragma unroll
+                for (int u = 0; u < PRE; u++) put(ImgNo(), wave + u * W, ent[u], cd[u]);
+            }
+            if (T > PRE * W * kWave)
             {   // dense systems: the rest of the tile, four groups per round trip
-                for (int q0 = kListPreload; (wave + q0 * W) * kWave < T; q0 += 4)
+                for (int q0 = PRE; (wave + q0 * W) * kWave < T; q0 += 4)
                 {
                     uint32_t en[4];
 #pragma unroll
@@ -344,37 +360,55 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
 // plus a whole number of cell edges, whatever the periodic wrap: no image shifts, no fp64, one 16-byte load per candidate.  Per cell, one wave:
 //   1. the z-runs of the stencil are looked up by the lanes in parallel; the loads of up to eight runs travel together (a wave's life is two memory
 //      round trips and the arithmetic);
-//   2. candidates are pruned against the cell's box and packed into LDS with wave ballot + popcount prefix, together with their list entries
-//      (atom index + image code, which k_pair_list needs for its fp64 gather);
+//   2. candidates are pruned against the box of the cell's atoms and packed ("staged") into LDS with wave ballot + popcount prefix, together with their
+//      list entries (atom index + image code, which k_pair_list needs for its fp64 gather);
 //   3. per group of 16 atoms of the cell ONE v_mfma_f32_16x16x4_f32 per 16 candidates tests 256 pairs against the list radius
 //      (D = thr - |ri - rj|^2 with a threshold widened by the f32 error bound: conservative);
-//   4. every lane pops its hits into its atom's stretch of a compact per-cell array; then every lane of k_pair_list's layout
-//      (lane = atom * NS + slice) reads ITS entries out of that array (entry slice + t NS of its atom) and the list leaves as whole 1 KiB chunks.
-// A cell whose candidates exceed the tile, whose lists exceed iterCap or that holds more than 64 atoms keeps no list (header -1): the clean-up
-// launch of k_pair_tile stages it on every step, and the engine grows the capacities when that happens.
+//   4. every lane pops its hits (staged candidate numbers) into its atom's stretch of a compact per-cell array, and the hit masks are ORed over the
+//      cell's atoms;
+//   5. only the candidates that some atom of the cell hit are KEPT (the dilated box holds ~30 % more than the union of the atoms' spheres): they
+//      are renumbered in tile order - so the gathers of k_pair_list stay runs of consecutive atoms and every atom's hit sequence is what it was -
+//      and leave as the cell's candidate list, T = the kept count;
+//   6. every lane of k_pair_list's layout (lane = atom * NS + slice) reads ITS entries out of the hit array (entry slice + t NS of its atom), maps
+//      them to the kept candidates' records, and the list leaves as whole 1 KiB chunks.
+// A cell whose staged candidates exceed the staging area (PairLists::stageLds), whose kept ones exceed the tile of k_pair_list (candLds), whose lists
+// exceed iterCap or that holds more than 64 atoms per wave keeps no list (header -1): the clean-up launch of k_pair_tile stages it on every step, and
+// the engine grows the capacities when that happens.  A cell whose atoms reach nobody keeps a list with T = 0: k_pair_list writes its forces as zero.
 // ---------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kBuildEntRegs = 8;           // k_build_lists: list entries of up to 512 staged candidates wait in registers while the filter runs
 struct BuildLds
 {
-    int capS;            // floats per coordinate array: candLds rounded up to whole mask words (the matrix filter reads 8 blocks of 16 candidates at a time)
+    int capS;            // floats per coordinate array: stageLds rounded up to whole mask words (the matrix filter reads 8 blocks of 16 candidates at a time)
     int nWords;          // 32-bit hit-mask words per lane and atom group: capS / 128
     int hitCap;          // entries of the compact hit array: iterLds x 64 x waves per cell
     int nTab;            // entries of each of the three small tables (staging table: <= 64 runs ; per atom of the cell: <= 64 x waves)
-    __host__ __device__ BuildLds(int candLds, int iterLds, int waves)
-        : capS((candLds + 127) & ~127), nWords((candLds + 127) / 128), hitCap(iterLds * kWave * waves), nTab(kWave * waves) {}
-    __host__ __device__ size_t union_bytes() const { const size_t a = sizeof(uint32_t) * (size_t)capS, b = sizeof(uint16_t) * (size_t)hitCap; return ((a > b ? a : b) + 15) & ~(size_t)15; }
-    __host__ __device__ size_t bytes() const { return sizeof(float) * 4 * (size_t)capS + union_bytes() + sizeof(uint32_t) * (size_t)nWords * kWave + sizeof(int32_t) * 3 * (size_t)nTab; }
+    __host__ __device__ BuildLds(int stageLds, int iterLds, int waves)
+        : capS((stageLds + 127) & ~127), nWords((stageLds + 127) / 128), hitCap(iterLds * kWave * waves), nTab(kWave * waves) {}
+    // The staged candidates' list entries outlive the filter (only then is it known who is kept), which fills the hit array.  Up to kBuildEntRegs x 64 staged
+    // candidates they wait in registers meanwhile and the hit array takes their place in LDS (a liquid's cells: LDS per wave bounds the builder's occupancy
+    // too); larger staging areas keep both
+    __host__ __device__ bool ent_in_regs() const { return capS <= kBuildEntRegs * kWave; }
+    __host__ __device__ size_t ent_hit_bytes() const
+    {
+        const size_t a = sizeof(uint32_t) * (size_t)capS, b = sizeof(uint16_t) * (size_t)hitCap;
+        return ((ent_in_regs() ? (a > b ? a : b) : a + b) + 15) & ~(size_t)15;
+    }
+    // tile, entries + hit array, hit masks of the group in flight, the three small tables
+    __host__ __device__ size_t bytes() const { return sizeof(float) * 4 * (size_t)capS + ent_hit_bytes() + sizeof(uint32_t) * (size_t)nWords * kWave + sizeof(int32_t) * 3 * (size_t)nTab; }
 };
 
 __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32_t* __restrict__ cellStart, int firstCell, int nCellsRun, PairLists L)
 {
     extern __shared__ float ldsBuild[];
     const int W = L.waves;
-    const BuildLds G(L.candLds, L.iterLds, W);
-    float4* const tile = (float4*)ldsBuild;                         // {x, y, z, -(x^2 + y^2 + z^2)} of every candidate, relative to the cell centre: one 16-byte store each;
+    const BuildLds G(L.stageLds, L.iterLds, W);
+    float4* const tile = (float4*)ldsBuild;                         // {x, y, z, -(x^2 + y^2 + z^2)} of every staged candidate, relative to the cell centre: one 16-byte store each;
                                                                     // lane (row c, component k) of the matrix operand reads float 4 (16 b + perm(c)) + k: 64 different banks
-    uint32_t* const tent = (uint32_t*)(tile + G.capS);              // list entries of the candidates (atom index | image code << 26), tile order ...
-    uint16_t* const hits = (uint16_t*)tent;                         // ... and, once those have left, the compact hit array (entries of k_pair_list's lists, atom by atom)
-    uint32_t* const maskBuf = (uint32_t*)((char*)tent + G.union_bytes());      // [nWords][64] hit masks of the atom group in flight
+    uint16_t* const remap = (uint16_t*)ldsBuild;                    // ... and, once the filter has run: staged candidate number -> list entry of its record in k_pair_list's tile
+    uint32_t* const tent = (uint32_t*)(tile + G.capS);              // list entries of the staged candidates (atom index | image code << 26), tile order ...
+    const bool entInRegs = G.ent_in_regs();                         // ... which wait in registers while the filter runs, if they are few enough (BuildLds) ...
+    uint16_t* const hits = (uint16_t*)(entInRegs ? tent : tent + G.capS);      // ... and leave their place to the compact hit array (staged candidate numbers, atom by atom)
+    uint32_t* const maskBuf = (uint32_t*)((char*)tent + G.ent_hit_bytes());    // [nWords][64] hit masks of the atom group in flight
     int32_t* const entJ = (int32_t*)(maskBuf + (size_t)G.nWords * kWave);      // staging table: first atom, count (<= 64), codes ; later, per atom of the cell:
     int32_t* const entN = entJ + G.nTab;                            //   tile slot / offset / hit count
     int32_t* const entC = entN + G.nTab;
@@ -394,15 +428,15 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     auto no_list = [&](int why) { if (lane == 0) { L.meta[4 * cell] = -1; atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); if (why != LR_NONE) atomicAdd(&L.noList[why], 1); } };
     if (nthis > kWave * W) { no_list(LR_NONE); return; }                 // (W waves of k_pair_list share the cell: up to 64 atoms each)
     const int RECB = L.entryScale;                                  // record number -> list entry (k_pair_list's mode decides: byte offset or number)
-    const int candLds = L.candLds;
+    const int stageLds = L.stageLds;
     const float cs0 = (float)P.csz[0], cs1 = (float)P.csz[1], cs2 = (float)P.csz[2];
     // f32 pruning radius: the list radius + what rounding can do to a coordinate (an atom's own-cell offset is rounded to f32, |x| < a few cell edges:
     // 2^-22 relative on the square is far more than that)
     const float pruneF = (float)(P.pruneR2 * (1.0 + 1e-5));
     // The candidates are pruned against the bounding box of the cell's ATOMS, not against the cell: a dozen atoms leave on average an eighth of the cell's
-    // edge empty on either side, and the box dilated by the list radius holds 15 % fewer candidates (C4: 299 -> 255) - less to filter here, and in
-    // k_pair_list a smaller LDS tile (its occupancy), a fifth group of candidates that is mostly padding, shorter gathers.  Conservative: an atom farther than
-    // the list radius from the box is farther than that from every atom inside it.
+    // edge empty on either side, and the box dilated by the list radius holds 15 % fewer candidates (C4: 299 -> 255) - less to filter here.  Conservative: an
+    // atom farther than the list radius from the box is farther than that from every atom inside it.  (What k_pair_list gathers is smaller still: only
+    // the staged candidates that the filter finds within the list radius of some atom of the cell are kept, below.)
     float bc0, bc1, bc2, bh0, bh1, bh2;
     {
         float lo0 = 3e38f, lo1 = 3e38f, lo2 = 3e38f, hi0 = -3e38f, hi1 = -3e38f, hi2 = -3e38f;
@@ -499,7 +533,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
                         const bool keep = (lane < gjn[u]) && (bx * bx + by * by + bz * bz) <= pruneF;
                         const unsigned long long mask = __ballot(keep);
                         const int nk = __popcll(mask);
-                        if (T + nk > candLds) { overflow = true; }
+                        if (T + nk > stageLds) { overflow = true; }
                         else
                         {
                             if (keep)
@@ -519,12 +553,6 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     if (overflow) { no_list(LR_TILE_FULL); return; }
     if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 1) return;                                 // (phase timing: staging only)
 
-    // ---- candidates: written out in whole groups of 64 (k_pair_list gathers whole groups: the last one is filled with a valid atom, the cell's first)
-    {
-        uint32_t* const myList = L.cand + (size_t)cell * L.candCap;
-        const int Tpad = max((T + kWave - 1) & ~(kWave - 1), kListPreload * W * kWave);      // (k_pair_list gathers five groups per wave whatever T is)
-        for (int q = lane; q < Tpad; q += kWave) myList[q] = (q < T) ? tent[q] : ((uint32_t)ib | (0x15u << 26));
-    }
     // far-away, finite dummies behind the last candidate up to the end of its mask word: the filter reads whole words of 8 x 16 candidates, without guards
     for (int q = T + lane; q < ((T + 127) & ~127); q += kWave) tile[q] = make_float4(-1e18f, 0.0f, 0.0f, -3e38f);
     // where the cell's own atoms sit in the tile (they are candidates too, unshifted): found by their list entries
@@ -534,7 +562,13 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         const int rel = (int)(en & 0x3FFFFFFu) - ib;
         if ((en >> 26) == 0x15u && rel >= 0 && rel < nthis) entJ[rel] = q;
     }
-    __builtin_amdgcn_wave_barrier();                                // (from here on the entries' place holds the hit array)
+    uint32_t te[kBuildEntRegs];                                     // entries of the staged candidates 64 u + lane
+#pragma unroll
+    for (int u = 0; u < kBuildEntRegs; u++) te[u] = (entInRegs && u * kWave < T) ? tent[u * kWave + lane] : 0u;
+    __builtin_amdgcn_wave_barrier();                                // (from here on the entries' place may hold the hit array)
+    // hit masks ORed over all atoms of the cell: the word of (mask word wd, quarter kq) - candidate 128 wd + kq + 4 p at bit 31 - p - is kept by lane 16 kq + wd
+    // (at most 15 mask words: 1 920 candidates)
+    uint32_t keepAcc = 0u;
 
     // ---- filter + compaction, one group of 16 atoms at a time.  Matrix operand maps (gfx950, v_mfma_f32_16x16x4_f32): A[row l & 15][k l >> 4],
     // B[k l >> 4][col l & 15], C/D[row 4 (l >> 4) + reg][col l & 15].  Rows are fed in the order perm(c) = (c >> 2) + 4 (c & 3), which makes register r
@@ -589,6 +623,13 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
             if (kSelf >= 0 && (kSelf & 3) == kq && (kSelf >> 7) == wd) m &= ~(0x80000000u >> ((kSelf & 127) >> 2));
             maskBuf[wd * kWave + lane] = m;
             h += __popc(m);
+            // who is hit by anybody: OR over the 16 atoms of the group (the lanes of one kq are one DPP row: four rotations), then into the cell's keep word
+            uint32_t any = m;
+            any |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)any, 0x128, 0xF, 0xF, false);      // row_ror:8
+            any |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)any, 0x124, 0xF, 0xF, false);      // row_ror:4
+            any |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)any, 0x122, 0xF, 0xF, false);      // row_ror:2
+            any |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)any, 0x121, 0xF, 0xF, false);      // row_ror:1
+            if (c16 == wd) keepAcc |= any;
         }
         // where this lane's hits go: behind those of the lower quarters of its atom, which come behind the atoms before it
         int below = 0, total = 0;
@@ -609,17 +650,17 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         nIter = max(nIter, ((total + NS - 1) * rcpNS) >> 16);
         if (hitBase > G.hitCap) { tooLong = 1; break; }              // (wave-uniform)
         if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 2) continue;                           // (phase timing: no compaction)
-        // candidate k = 128 wd + kq + 4 p sits in record k + 1 of k_pair_list's tile
+        // bit 31 - p of word wd is the staged candidate 128 wd + kq + 4 p
         uint16_t* dst = hits + myOff + below;
         for (int wd = 0; wd < nW; wd++)
         {
             uint32_t cur = maskBuf[wd * kWave + lane];
-            const int base = (128 * wd + kq + 1) * RECB;
+            const int base = 128 * wd + kq;
             while (cur != 0u)
             {
                 const int p = __clz(cur);
                 cur &= ~(0x80000000u >> p);
-                *dst++ = (uint16_t)(base + p * 4 * RECB);
+                *dst++ = (uint16_t)(base + p * 4);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -627,7 +668,40 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     if ((P.debugMask & DBG_BUILD_PHASE_MASK) >= 2) return;                                 // (phase timing: no read-out)
     nIter = wave_max_int(nIter);
     // (DBG_SHORT_LISTS, tests: lists hold 14 iterations only - part of a liquid's cells then keep no list and go through the clean-up launch)
-    const bool usable = !tooLong && nIter <= ((P.debugMask & DBG_SHORT_LISTS) ? 14 : L.iterCap);
+    bool usable = !tooLong && nIter <= ((P.debugMask & DBG_SHORT_LISTS) ? 14 : L.iterCap);
+    // ---- the candidates some atom of the cell reaches are kept, in tile order: kept candidate n sits in record n + 1 of k_pair_list's tile.  They are
+    // written out in whole groups of 64 (k_pair_list gathers whole groups: the last one is filled with a valid atom, the cell's first)
+    int kept = 0;
+    if (usable)
+    {
+        __builtin_amdgcn_wave_barrier();                            // (the tile has served: its place takes the renumbering)
+        uint32_t* const myList = L.cand + (size_t)cell * L.candCap;
+        auto keep_chunk = [&](int q0, uint32_t entry) {
+            const int q = q0 + lane;
+            const uint32_t kw = (uint32_t)__shfl((int)keepAcc, ((q & 3) << 4) | (q >> 7), kWave);
+            const bool keep = q < T && ((kw << ((q & 127) >> 2)) & 0x80000000u) != 0u;
+            const unsigned long long mask = __ballot(keep);
+            if (keep)
+            {
+                const int n = kept + lanes_below(mask);
+                remap[q] = (uint16_t)((n + 1) * RECB);
+                myList[n] = entry;
+            }
+            kept += __popcll(mask);
+        };
+        if (entInRegs)
+        {
+#pragma unroll
+            for (int u = 0; u < kBuildEntRegs; u++) if (u * kWave < T) keep_chunk(u * kWave, te[u]);
+        }
+        else
+            for (int q0 = 0; q0 < T; q0 += kWave) keep_chunk(q0, tent[min(q0 + lane, T - 1)]);
+        const int Tpad = max((kept + kWave - 1) & ~(kWave - 1), list_preload(L.candLds) * W * kWave);      // (k_pair_list gathers that many groups per wave whatever T is)
+        for (int q = kept + lane; q < Tpad; q += kWave) myList[q] = (uint32_t)ib | (0x15u << 26);
+        __builtin_amdgcn_wave_barrier();
+    }
+    const bool keptFull = usable && kept > L.candLds;               // (staged, filtered, and still too many for the walk's tile: served by the clean-up launch until the tile has grown)
+    if (keptFull) usable = false;
     if (usable)
     {   // every lane of k_pair_list's layout collects ITS entries: lane = slot * NS + slice of wave w walks entries slice, slice + NS, ... of atom w aw + slot;
         // 0 = no candidate
@@ -646,7 +720,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
                 for (int u = 0; u < 8; u++)
                 {
                     const int e = (c * 8 + u) * NS + slice;
-                    v[u] = (e < cnt) ? (uint32_t)src[e] : 0u;
+                    v[u] = (e < cnt) ? (uint32_t)remap[src[e]] : 0u;
                 }
                 out[c * kWave] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
             }
@@ -656,13 +730,17 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     {
         // header: candidates | iterations << 12 | slices per atom << 20 ; then the cell's first atom and atoms | (65536 / slices + 1) << 12 - all k_pair_list needs to
         // know about the cell arrives in one 16-byte scalar load
-        L.meta[4 * cell] = usable ? (T | (nIter << 12) | (NS << 20)) : -1;
+        L.meta[4 * cell] = usable ? (kept | (nIter << 12) | (NS << 20)) : -1;
         L.meta[4 * cell + 2] = ib;
         L.meta[4 * cell + 3] = nthis | (rcpNS << 12);
-        if (T > L.noList[LR_MAX_TILE]) atomicMax(&L.noList[LR_MAX_TILE], T);           // (a read first: after the first few cells nobody has a new record to report)
+        if (T > L.noList[LR_MAX_STAGED]) atomicMax(&L.noList[LR_MAX_STAGED], T);       // (a read first: after the first few cells nobody has a new record to report)
+        if (kept > L.noList[LR_MAX_TILE]) atomicMax(&L.noList[LR_MAX_TILE], kept);
         if (usable && nIter > L.noList[LR_MAX_ITERS]) atomicMax(&L.noList[LR_MAX_ITERS], nIter);
-        if (P.debugMask & DBG_LIST_STATS) { atomicAdd(&L.noList[LR_SUM_ITERS], nIter); atomicAdd(&L.noList[LR_SUM_CANDS], T); atomicAdd(&L.noList[LR_SUM_ATOMS], nthis); }      // measurement aid (slow)
-        if (!usable) { atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); atomicAdd(&L.noList[LR_LIST_FULL], 1); }
+        if (P.debugMask & DBG_LIST_STATS)
+        {   // measurement aid (slow)
+            atomicAdd(&L.noList[LR_SUM_ITERS], nIter); atomicAdd(&L.noList[LR_SUM_CANDS], kept); atomicAdd(&L.noList[LR_SUM_ATOMS], nthis); atomicAdd(&L.noList[LR_SUM_STAGED], T);
+        }
+        if (!usable) { atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); atomicAdd(&L.noList[keptFull ? LR_KEPT_FULL : LR_LIST_FULL], 1); }
     }
 }
 
@@ -671,10 +749,10 @@ inline void launch_build_lists(const PairLaunch& C, PairRange R, PairLists L)
 {
     pair_range_default(C.P, R);
     if (R.n == 0) return;
-    const BuildLds G(L.candLds, L.iterLds, L.waves);
+    const BuildLds G(L.stageLds, L.iterLds, L.waves);
     hipLaunchKernelGGL(k_build_lists, dim3(pair_range_grid(R.n)), dim3(kWave), G.bytes(), C.stream, C.P, C.cellStart, R.first, R.n, L);
 }
-inline size_t build_lists_lds_bytes(const PairLists& L) { return BuildLds(L.candLds, L.iterLds, L.waves).bytes(); }
+inline size_t build_lists_lds_bytes(const PairLists& L) { return BuildLds(L.stageLds, L.iterLds, L.waves).bytes(); }
 
 template <int MODE, int VDW>
 inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, NextStep N, bool energies)
@@ -684,7 +762,9 @@ inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, N
     // thermostat-fused epilogue: modes that do not read radii (the thermostat rewrites them while other waves would still be gathering), never on a step
     // whose energies are wanted (Engine::launch_step_kernels)
     constexpr bool kCanFuseTstat = !pair_mode_reads_radii(MODE);
-#define AZTOT_LAUNCH_LIST(E, M, T) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T>), grid, block, lds, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials, C.maxBlocks, C.cnt, R.blockBase, L, N)
+    const bool four = list_preload(L.candLds) == 4;                 // groups gathered up front: compiled in
+#define AZTOT_LAUNCH_LIST_PRE(E, M, T, G) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T, G>), grid, block, lds, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials, C.maxBlocks, C.cnt, R.blockBase, L, N)
+#define AZTOT_LAUNCH_LIST(E, M, T) do { if (four) AZTOT_LAUNCH_LIST_PRE(E, M, T, 4); else AZTOT_LAUNCH_LIST_PRE(E, M, T, kListPreload); } while (0)
     if (N.photons)
     {
         if (energies || !kCanFuseTstat) throw std::runtime_error("k_pair_list: the thermostat cannot be fused into this launch");
@@ -693,6 +773,7 @@ inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, N
     else if (L.waves == 1) { if (energies) AZTOT_LAUNCH_LIST(true, false, false); else AZTOT_LAUNCH_LIST(false, false, false); }
     else { if (energies) AZTOT_LAUNCH_LIST(true, true, false); else AZTOT_LAUNCH_LIST(false, true, false); }
 #undef AZTOT_LAUNCH_LIST
+#undef AZTOT_LAUNCH_LIST_PRE
 }
 
 // a plain step: the list kernel for every cell (launch_pair_list), then the clean-up launch of the staging kernel for the cells that keep no list

@@ -420,17 +420,20 @@ enum ListReport : int
     LR_UNLISTED = 0,        // cells recorded without a list since the host last looked
     LR_RECORDED = 1,        // cells recorded since the host last looked
     LR_UNLISTED_NOW = 2,    // cells without a list in the lists in force (zeroed before every recording launch)
-    LR_MAX_TILE = 3,        // largest T (candidates of a cell) ever recorded
+    LR_MAX_TILE = 3,        // largest T (candidates a cell KEPT: the tile of k_pair_list) ever recorded
     LR_MAX_ITERS = 4,       // largest iteration count ever recorded
-    LR_TILE_FULL = 5,       // cells that did not fit the tile since the host last looked
+    LR_TILE_FULL = 5,       // cells whose STAGED candidates did not fit the builder's staging area since the host last looked
     LR_LIST_FULL = 6,       // ... that did not fit the list
-    LR_SUM_ITERS = 8, LR_SUM_CANDS = 9, LR_SUM_ATOMS = 10,     // DBG_LIST_STATS: totals over the cells recorded (three in a row: cleared together)
+    LR_KEPT_FULL = 7,       // ... whose kept candidates did not fit the tile of k_pair_list (three in a row: cleared together)
+    LR_SUM_ITERS = 8, LR_SUM_CANDS = 9, LR_SUM_ATOMS = 10, LR_SUM_STAGED = 11,     // DBG_LIST_STATS: totals over the cells recorded (four in a row: cleared together)
+    LR_MAX_STAGED = 12,     // largest number of candidates a cell staged (box-pruned, before the unreachable ones were dropped) ever recorded
     LR_COUNT = 16,
     LR_NONE = -1            // (k_build_lists: a cell without a list that no counter of its own explains - more than 64 atoms per wave)
 };
 struct PairLists
 {
-    uint32_t* cand = nullptr;      // [nCell][candCap]: atom index | image code << 26 of every candidate, in tile order; padded with valid entries to a multiple of 64
+    uint32_t* cand = nullptr;      // [nCell][candCap]: atom index | image code << 26 of every candidate some atom of the cell reaches, in tile order; padded with
+                                   //          valid entries to a multiple of 64
     int32_t* meta = nullptr;       // [nCell][4]: {candidates T | list iterations << 12 | slices per atom << 20, cell coordinates lx | cy << 10 | cz << 20 (written once by the host),
                                    //          the cell's first atom, atoms in the cell | (65536 / slices + 1) << 12} ;
                                    //          first word -1: this cell keeps no list (more candidates than the tile holds, more than 64 atoms, or more
@@ -440,8 +443,9 @@ struct PairLists
     int32_t* noList = nullptr;     // [LR_COUNT]: the builder's report to the host (enum ListReport)
     int32_t candCap = 0;           // candidates per cell in `cand` (multiple of 64)
     int32_t iterCap = 0;           // list iterations per cell in `pairs` (multiple of 8)
-    int32_t candLds = 0;           // candidates the LDS tiles of k_pair_list / k_build_lists hold (>= 256, <= candCap): sized by the engine from the largest T
+    int32_t candLds = 0;           // candidates the LDS tile of k_pair_list holds (>= 256, <= candCap): sized by the engine from the largest KEPT count
                                    //      seen, because LDS per wave is what bounds the occupancy of k_pair_list (7.7 KiB: 95 us, 10.8 KiB: 106 us on the 1 M-atom box)
+    int32_t stageLds = 0;          // candidates the builder's staging area holds (>= candLds, <= candCap): from the largest STAGED count seen
     int32_t iterLds = 0;           // iterations the builder's LDS list buffer holds (multiple of 8, <= iterCap)
     int32_t waves = 1;             // waves per cell in k_pair_list (1, 2 or 4): they share ONE tile and split the cell's atoms - where a cell's candidates are
                                    //      many and the cells few (dense systems, slab ranks), LDS per wave and wave lifetime are what bounds the kernel.
