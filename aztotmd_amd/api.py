@@ -133,6 +133,8 @@ class DebugBit(enum.IntFlag):
     DBG_ONE_WAVE_PER_CELL = 67108864
     DBG_ENERGIES_EVERY_STEP = 134217728
     DBG_SETTLE_EVERY_CALL = 268435456
+    DBG_NO_FOLD_KICK = 536870912
+    DBG_FOLD_KICK = 1073741824
 
 
 def library_path():

@@ -121,7 +121,18 @@ enum DebugBit : unsigned
     DBG_NO_BOUNDARY_RADI = 33554432,     // thermostat runs close a step and open the next in two launches
     DBG_ONE_WAVE_PER_CELL = 67108864,    // one wave per cell in the staging kernel whatever the system
     DBG_ENERGIES_EVERY_STEP = 134217728, // = options.energies_every_step
-    DBG_SETTLE_EVERY_CALL = 268435456    // every aztot_step call ends with the look / statistics / synchronisation (one GPU defers them to the next look or read)
+    DBG_SETTLE_EVERY_CALL = 268435456,   // every aztot_step call ends with the look / statistics / synchronisation (one GPU defers them to the next look or read)
+    DBG_NO_FOLD_KICK = 536870912,        // both half-kicks in the list kernel (KICK_BOTH, Engine::foldKickOk_) off ...
+    DBG_FOLD_KICK = 1073741824           // ... or on, whatever the system size (small systems then neither fuse the next step nor kick in the tile kernel's epilogue)
+};
+
+// StepParams::fuseKick, what the pair kernel's epilogue does with the velocities besides summing the force
+enum KickFuse
+{
+    KICK_NONE = 0,                       // nothing: the force is stored, somebody else kicks
+    KICK_SECOND = 1,                     // this step's second half-kick (+ the kinetic energy on steps that book energies); force and velocity are stored
+    KICK_BOTH = 2                        // k_pair_list only, never with the clean-up launch: this step's second half-kick AND the next step's first, as two
+                                         // separate roundings; the velocity is stored, the force is NOT - the next step is a drift (k_drift_plain2)
 };
 
 // StepParams::potSet, the potential set the pair kernels are chosen for (Engine::construct decides, AZTOT_PAIR_DISPATCH): any mix of potentials, radii and species;
@@ -159,7 +170,7 @@ struct StepParams
     // slab decomposition
     double xlo, xhi;              // owned x-range [xlo, xhi)
     int32_t rank, nranks;
-    int32_t fuseKick;             // 1: the pair kernel also applies the second half-kick and books the kinetic energy (plain NVE steps)
+    int32_t fuseKick;             // KickFuse: which half-kicks the pair kernel's epilogue applies (plain NVE steps)
     int32_t vdwFamily;            // POTSET_ONE_FAMILY: the one potential type all defined species pairs share (1 lnjs, 2 buck, 3 p746, 4 bmhs)
     int32_t cycleStep;            // lazy re-sort: which step since the last rebuild of the cells this launch belongs to (0: the rebuilding step itself)
     int32_t boundSkip;            // 1: plain steps may skip the per-atom displacement check while the displacement bound allows (Counts::cycMaxRun)

@@ -84,7 +84,11 @@ namespace aztot {
 //                                                                                                                      integrate kernel pay it)
 //  preIntegrated_    the step being launched was opened by the previous    launch_pair (next-step fusion),             sort_and_forces (consumes it), run_steps,   -
 //                    step's pair kernel / boundary kernel                  launch_step_kernels (k_boundary_radi)       graph capture, replay
-//  fuseNext_/fuseNow_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   set and consumed inside launch_step_kernels / launch_pair
+//  kickFolded_       the step being launched was kicked by the previous    launch_pair (the list launch that took up   sort_and_forces (consumes it: k_drift_plain2 -
+//                    step's k_pair_list (KICK_BOTH), which stored v and    foldKick_)                                  instead of k_integrate_plain2), graph        a folded step is always followed by a plain
+//                    no f: the state is NOT the canonical one                                                          capture, replay                             step of the same run_steps, so no entry point,
+//                                                                                                                                                                  look, snapshot or rebuild ever sees it set
+//  fuseNext_/fuseNow_/foldKick_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   set and consumed inside launch_step_kernels / launch_pair
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 class Engine final : private Samplers::Host
 {
@@ -286,6 +290,11 @@ private:
     bool kickOwed_ = false;
     bool fuseEpilogue_ = false;     // small plain-NVE runs: the tile kernel's epilogue applies integrate2
     bool fuseNow_ = false;          // the pair launch in flight also does integrate2's job (plain NVE steps, tile kernel)
+    // large plain-NVE runs on one GPU that walk pair lists: on a step that books no energies and is followed by a plain step of the same run, k_pair_list
+    // applies both half-kicks (this step's second, the next step's first) and stores the velocity instead of the force; the next step is a drift
+    bool foldKickOk_ = false;       // this engine may fold (decided once)
+    bool foldKick_ = false;         // the list launch of the step being launched is asked to fold
+    bool kickFolded_ = false;       // ... and the previous step's did: the step being launched opens with k_drift_plain2
     bool overlapHalo_ = false;      // the pair launch in flight is split: interior cells now, boundary cells once evHalo_ has fired
     int candMode_ = 0;              // for the pair launch in flight: 0 none, 1 record, 2 plain step of the lazy re-sort
     // next-step fusion (pair_tile.hip.h NextStep): on plain NVE steps of a lazy run on one GPU the pair kernel's epilogue also does the next step's

@@ -285,7 +285,14 @@ void Engine::construct()
         // small systems / slabs are bound by launch latency: the tile kernel's epilogue does it (one kernel less: C2 0.083 -> 0.063 ms).
         // On 1 M atoms that 13-lane read-modify-write of the velocities makes L2 write lines back several times (rocprofv3: 221 MB
         // instead of 63 + 76 MB per step) for no gain, so large systems fold it into the next step's streaming k_integrate1_bin.
-        fuseEpilogue_ = plainNve && variant >= 2 && capacity_ <= kFuseKickMaxAtoms && !(debug_ & DBG_LARGE_KICK_PATH);
+        // Large systems on one GPU that walk pair lists go one step further: on steps that book no energies and are followed by a plain step of the same
+        // run, k_pair_list applies this step's second half-kick AND the next step's first and stores the velocity instead of the force (KICK_BOTH); the next
+        // step is then a drift (k_drift_plain2: 76 B per atom instead of k_integrate_plain2's 124).  Above the sizes that fuse the next step (they keep what
+        // they have); DBG_FOLD_KICK forces it on whatever the size - such an engine neither fuses the next step nor kicks in the tile kernel's epilogue -,
+        // DBG_NO_FOLD_KICK switches it off.  Which steps fold: launch_step_kernels.
+        foldKickOk_ = plainNve && nranks_ == 1 && lists_.on && variant == 2 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & (DBG_NO_FOLD_KICK | DBG_PLAIN_ONE_ATOM)) &&
+                      (capacity_ > 2 * kFuseKickMaxAtoms || (debug_ & DBG_FOLD_KICK)) && !((debug_ & DBG_FUSE_NEXT) && !(debug_ & DBG_NO_FUSE_NEXT));
+        fuseEpilogue_ = plainNve && variant >= 2 && capacity_ <= kFuseKickMaxAtoms && !(debug_ & DBG_LARGE_KICK_PATH) && !foldKickOk_;
         // (bonded and reciprocal-space forces are added behind the pair kernel and are complete before the next step's integrate kernel just the same: runs with
         //  bonds / angles / the Ewald sum defer the kick too - they cannot take the pair kernel's epilogue, which would kick with the pair forces alone.
         //  M4: one 17 us launch per step less)
@@ -304,7 +311,7 @@ void Engine::construct()
         const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP) && !P_.use_radii && P_.potSet != POTSET_ONE_SURK && (P_.single_lj || P_.potSet == POTSET_ONE_FAMILY) &&
                               nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
         fuseNextTstat_ = radiFuse && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
-        if (((plainNve && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
+        if (((plainNve && !foldKickOk_ && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
         {
             fuseNextOk_ = true;
             for (int b = 0; b < 2; b++)
@@ -971,7 +978,7 @@ void Engine::launch_pair()
     if (variant == 2)
     {
         StepParams Q = P_;
-        Q.fuseKick = fuseNow_ ? 1 : 0;
+        Q.fuseKick = fuseNow_ ? KICK_SECOND : KICK_NONE;
         const PairLaunch C = pair_launch(Q);
         // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
         // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
@@ -1033,7 +1040,13 @@ void Engine::launch_pair()
                 if (fuseNext_ && fuseNextTstat_) { nx.photons = dPhotons_; nx.uvx = dUvx_; nx.uvy = dUvy_; nx.uvz = dUvz_; pairClosedStep_ = true; }
                 else nx.pendingAfter = lazyKick_ ? 1 : -1;         // this step's second half-kick is owed to the next k_integrate1_bin (a call may open
                                                                     // with a plain step, where no scan re-arms the flag)
-                timed("pair_list", [&] { splitBlocks = launch_pair_list(C, PairRange(), pl, nx, wantEnergies); });
+                // both half-kicks in this launch (launch_step_kernels decided; no clean-up launch follows, which has no such epilogue): neither kick is owed
+                const bool fold = foldKick_ && skipCleanup && !fuseNext_ && !wantEnergies;
+                foldKick_ = false;
+                StepParams QL = Q;
+                if (fold) { QL.fuseKick = KICK_BOTH; nx.pendingAfter = 0; kickFolded_ = true; }
+                const PairLaunch CL = pair_launch(QL);
+                timed("pair_list", [&] { splitBlocks = launch_pair_list(CL, PairRange(), pl, nx, wantEnergies); });
                 if (!skipCleanup)
                     timed("pair_cleanup", [&] { splitBlocks += launch_pair_cleanup(C, PairRange(), pl, nx); });
                 if (fuseNext_)
@@ -1053,6 +1066,7 @@ void Engine::launch_pair()
                                dCellOfSorted_, dPartials_, maxBlocks_);
         });
     if (variant < 2) fuseNow_ = false;           // only the tile kernels have the fused epilogue (cannot happen: see the constructor)
+    foldKick_ = false;                           // (a request no list launch took up is dropped)
     notes_.pairBlocksUsed = (variant == 2) ? (splitBlocks ? splitBlocks : pair_tile_grid(P_) * split_.n) : div_up(capacity_, kBlock);
     notes_.blocksEver = std::max(notes_.blocksEver, std::max(notes_.pairBlocksUsed, div_up(capacity_, kBlock)) + 1);
 }
@@ -1112,6 +1126,14 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     if (stepMode == STEP_PLAIN)
     {   // plain step of the lazy re-sort: integrate only; slots, cells and buffers stay as they are
         if (preIntegrated_) preIntegrated_ = false;                 // the previous step's pair kernel has opened this step already (NextStep)
+        else if (kickFolded_)
+        {   // the previous step's pair kernel applied both half-kicks and stored no force (KICK_BOTH): the drift alone
+            kickFolded_ = false;
+            timed("drift", [&] {
+                hipLaunchKernelGGL(k_drift_plain2, dim3(div_up(div_up(capacity_, 2), kBlock)), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dPartials_,
+                                   maxBlocks_, dStats_, ref_);
+            });
+        }
         else if (nranks_ == 1 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & DBG_PLAIN_ONE_ATOM))
             // one GPU (the owned range starts at 0: 16-byte loads are aligned), nothing scales the velocities at the start of the step: two atoms per thread
             timed("integrate1", [&] {
@@ -1152,6 +1174,7 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     }
     else
     {
+    if (kickFolded_) throw std::runtime_error("a step that needs the forces follows a pair kernel that stored none");      // (cannot happen: launch_step_kernels)
     candMode_ = (stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? 1 : 0;       // a step that opens an interval of plain steps records the lists
     if (integrate_first)
         timed("integrate1_bin", [&] {
@@ -1265,6 +1288,12 @@ void Engine::launch_step_kernels()
         // (and one wave per cell: in the multi-wave kernels of dense systems the thermostat's registers cost the loop more than the launch saves -
         //  measured with a second radius array for case study 2's surk kernel: S40 0.076 -> 0.093 ms/step, case study 2 unchanged; not kept)
         if (fuseNextTstat_) fuseNext_ = fuseNext_ && optimistic_ && !equil && lists_.waves == 1 && !(debug_ & DBG_ENERGIES_EVERY_STEP);
+        // ... or kick for it?  (foldKickOk_: plain NVE on one GPU, no next-step fusion.)  The same walk of the lists with no clean-up launch behind it, a step
+        // that books no energies, and a plain step of this run to follow: whoever else may come next - a rebuild (k_integrate1_bin and k_rank_gather need
+        // the force and the kick state they know), a look, the end of the call and everything that can read the state there - finds the canonical state,
+        // velocities half-kicked, forces valid, DevStats::pendingKick as ever.  (stepsLeftInRun_ > 0 inside nextPlain: this is not the step whose
+        // energies are wanted either, but for DBG_ENERGIES_EVERY_STEP.)
+        foldKick_ = foldKickOk_ && lists && nextPlain && optimistic_ && !(debug_ & DBG_ENERGIES_EVERY_STEP);
     }
     pairClosedStep_ = false;
     sort_and_forces(stepMode);
@@ -1397,7 +1426,7 @@ void Engine::replay_from_snapshot()
     drop_graphs();
     set_buf_state(snap_.buf);
     copy_state(snap_, live());
-    forget_interval(); preIntegrated_ = false; haloInfoPending_ = false; unlistedState_ = 0;
+    forget_interval(); preIntegrated_ = false; kickFolded_ = false; haloInfoPending_ = false; unlistedState_ = 0;
     kickOwed_ = false;
     hostStep_ = snap_.hostStep;
     if (nranks_ > 1) lazyK_ = 1;
@@ -1579,6 +1608,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     {
         sinceSort_ = kNoSort;
         preIntegrated_ = false;
+        kickFolded_ = false;
         for (int k = 0; k < cycle; k++) { stepsLeftInRun_ = cycle - 1 - k; launch_step_kernels(); }
     }
     catch (...)
@@ -1588,6 +1618,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
         if (broken) (void)hipGraphDestroy(broken);
         capturing_ = false;
         preIntegrated_ = false;
+        kickFolded_ = false;
         sinceSort_ = sinceBefore;
         set_buf_state(now);
         adopt_launch_notes(notesBefore);

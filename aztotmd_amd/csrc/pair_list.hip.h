@@ -307,17 +307,29 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             const double fxi = -q * P.E[0] + acc.fx;   // clear_force integrators.cpp:17-39
             const double fyi = -q * P.E[1] + acc.fy;
             const double fzi = -q * P.E[2] + acc.fz;
+            if (P.fuseKick == KICK_BOTH)
+            {   // this step's second half-kick and the next step's first: the two roundings k_integrate_plain2 would make from the stored force (the kick
+                // it owes, then its own).  The velocity leaves instead of the force, which nobody reads before the next pair kernel: the next step is a
+                // drift (k_drift_plain2).  Never a step whose energies are booked, never with NextStep (Engine::launch_step_kernels)
+                const double rM = S.rMhdt[ti];
+                double vx = v0x + rM * fxi, vy = v0y + rM * fyi, vz = v0z + rM * fzi;
+                vx += rM * fxi; vy += rM * fyi; vz += rM * fzi;
+                A.vx[myi] = vx; A.vy[myi] = vy; A.vz[myi] = vz;
+            }
+            else
+            {
             A.fx[myi] = fxi; A.fy[myi] = fyi; A.fz[myi] = fzi;
             if (P.fuseKick || N.xn)
             {   // second half-kick + kinetic energy of integrate2 (integrators.cpp:486-531 ; verlet_2stage cuMDfunc.cu:521-600); with NextStep also the
                 // next step's k_integrate1_bin<2>
                 const double rM = S.rMhdt[ti], m = S.mass[ti];
                 double vx = v0x + rM * fxi, vy = v0y + rM * fyi, vz = v0z + rM * fzi;
-                if (ENG && P.fuseKick) eK += (vx * vx + vy * vy + vz * vz) * m;     // (the kinetic energy too is looked at after a call's last step only)
+                if (ENG && P.fuseKick == KICK_SECOND) eK += (vx * vx + vy * vy + vz * vz) * m;     // (the kinetic energy too is looked at after a call's last step only)
                 if (TSTAT && N.xn)      // close the step as k_integrate2_post does: the thermostat acts on the fully kicked velocity; its draws are keyed by this step's number
                     (void)post_tstat_atom(P, S, A, N.st, N.photons, N.uvx, N.uvy, N.uvz, myi, vx, vy, vz, N.st->stepAtSort + (long long)P.cycleStep);
                 if (N.xn) next_step_atom(P, S, N, myi, ti, xr, yr, zr, fxi, fyi, fzi, vx, vy, vz, r0x, r0y, r0z, nacc);
                 A.vx[myi] = vx; A.vy[myi] = vy; A.vz[myi] = vz;
+            }
             }
         }
         if (ENG) { eV = acc.eV; eC = acc.eC; }
@@ -338,7 +350,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         }
         if (dropped != 0.0) partials[(size_t)PS_DROPPED * maxBlocks + pb] += dropped;
     }
-    if (ENG && P.fuseKick)
+    if (ENG && P.fuseKick == KICK_SECOND)
     {
         eK = wave_sum(eK);
         if (lane == 0) partials[(size_t)PS_EKIN * maxBlocks + pb] = 0.5 * eK;
