@@ -189,9 +189,22 @@ def ewald_reciprocal_fixture():
     print("ewald_reciprocal", "%d arrays" % len(a), "dense pairs %d" % int(a["dense__npairs"]))
 
 
+def thermostat_atoms_fixture():
+    """thermostat_atoms.npz: the designed atoms of tests/thermostat_cases.py (photon table, velocities, internal energies) and step 1 of the radiative
+    thermostat for 141 of them at 50 digits (tests/thermostat_reference.py; tests/test_gpu_thermostat_atoms.py reads it with numpy alone).  Needs
+    mpmath and the library's host code, not the reference binary; a few seconds."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import thermostat_reference as tr
+    a = tr.make_fixture(os.path.join(HERE, "thermostat_atoms.npz"))
+    print("thermostat_atoms", "%d arrays" % len(a), "%d atoms at 50 digits" % len(a["atoms"]))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["ewald_reciprocal"]:
         ewald_reciprocal_fixture()
+        sys.exit(0)
+    if sys.argv[1:] == ["thermostat_atoms"]:
+        thermostat_atoms_fixture()
         sys.exit(0)
     oracle.build()
     if sys.argv[1:] == ["ewald"]:
