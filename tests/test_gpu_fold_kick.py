@@ -16,6 +16,7 @@ import pytest
 
 from aztotmd_amd import api, inputs
 from aztotmd_amd.api import DebugBit
+from util import on_the_walls, wall_liquid
 
 pytestmark = pytest.mark.gpu
 
@@ -26,21 +27,11 @@ OFF = DebugBit.DBG_NO_FOLD_KICK | LARGE_PATH
 STEP_KERNELS = ("drift", "integrate1", "integrate1_bin")
 
 
-def on_the_walls(case):
-    """the first lattice planes of lj_case sit 0.25 A inside the box (+- 0.15 A of jitter); moved onto the walls, their atoms - 128 per wall, thermal speed
-    1.3 A/ps per axis - cross all six walls in both directions within a few dozen steps at 85 K"""
-    for k, L in zip(("x", "y", "z"), case["box"]):
-        v = np.round(np.mod(case[k] - 0.25, L), 6)
-        v[v >= L] = 0.0
-        case[k] = v
-    return case
-
-
 def system(name):
     # 8^3 FCC cells of 5.735 A: five cells of rc + skin per axis, the fewest a one-GPU engine re-sorts lazily on (it must be able to widen its stencil by a
     # cell) and so the smallest box that keeps pair lists at rc = 8.5 A (2 048 atoms)
     if name == "lj":                 # one species: the one-species LJ kernel
-        return on_the_walls(inputs.lj_case((8, 8, 8), seed=71, vel_T=85.0))
+        return wall_liquid()
     if name == "fennell":            # two charged species, LJ + Fennell: the table-driven kernel
         return on_the_walls(inputs.lj_case((8, 8, 8), seed=72, vel_T=85.0, charges=(0.2, -0.2), elec="fenn"))
     if name == "frozen":             # ... one of them frozen: kicked like any other, never moved

@@ -15,7 +15,7 @@ import pytest
 from aztotmd_amd import api, inputs
 from aztotmd_amd.api import DebugBit
 from oracle import oracle, parse
-from util import FRC, VEL, case_from_parsed, materialise_case_study, per_atom_err, rel_err
+from util import FRC, VEL, case_from_parsed, check_cell_table, materialise_case_study, per_atom_err, rel_err
 
 pytestmark = pytest.mark.gpu
 XVF = ("x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz")
@@ -32,30 +32,6 @@ def cpu_steps(case, nsteps):
     o.step(nsteps)                       # forces start at 0, as on the reference's GPU path (sys_init.cpp:551-553)
     st = o.stats()
     return o.state(), {"engVdW": st["engVdW"], "engCoul": st["engElec3"], "engKin": st["engKin"], "engTot": st["engTot"]}, "oracle"
-
-
-def host_cell_table(s, box, dims):
-    """count_cell (cuSort.cu:114-128): cell = floor(x * cRevSize) per axis, in double; then the exclusive prefix sum."""
-    idx = []
-    for k, key in enumerate(("x", "y", "z")):
-        c = np.floor(s[key] * (dims[k] / box[k])).astype(np.int64) % dims[k]
-        idx.append(c)
-    cell = (idx[0] * dims[1] + idx[1]) * dims[2] + idx[2]
-    hist = np.bincount(cell, minlength=dims[0] * dims[1] * dims[2])
-    start = np.concatenate([[0], np.cumsum(hist)])
-    return cell, start
-
-
-def check_cell_table(e, s, box):
-    dims, start, ids = e.cell_table()
-    cell, ref_start = host_cell_table(s, box, dims)
-    assert np.array_equal(start, ref_start), "cell offsets differ from the host prefix sum"
-    assert np.array_equal(np.sort(ids), np.arange(len(ids))), "every atom sits in exactly one slot"
-    slot_cell = np.repeat(np.arange(len(start) - 1), np.diff(start))
-    assert np.array_equal(cell[ids], slot_cell), "an atom sits in a slot of the wrong cell"
-    same = slot_cell[1:] == slot_cell[:-1]
-    assert np.all(ids[1:][same] > ids[:-1][same]), "atoms of one cell are not in id order"
-    return dims
 
 
 @pytest.mark.parametrize("name", ["C4", "C3"])

@@ -22,6 +22,46 @@ def per_atom_err(a, b, keys=("fx", "fy", "fz"), floor=1e-3):
     return float((d / np.maximum(mag, floor * rms)).max())
 
 
+def host_cell_table(s, box, dims):
+    """count_cell (cuSort.cu:114-128): cell = floor(x * cRevSize) per axis, in double; then the exclusive prefix sum."""
+    idx = []
+    for k, key in enumerate(("x", "y", "z")):
+        c = np.floor(s[key] * (dims[k] / box[k])).astype(np.int64) % dims[k]
+        idx.append(c)
+    cell = (idx[0] * dims[1] + idx[1]) * dims[2] + idx[2]
+    hist = np.bincount(cell, minlength=dims[0] * dims[1] * dims[2])
+    start = np.concatenate([[0], np.cumsum(hist)])
+    return cell, start
+
+
+def check_cell_table(e, s, box):
+    dims, start, ids = e.cell_table()
+    cell, ref_start = host_cell_table(s, box, dims)
+    assert np.array_equal(start, ref_start), "cell offsets differ from the host prefix sum"
+    assert np.array_equal(np.sort(ids), np.arange(len(ids))), "every atom sits in exactly one slot"
+    slot_cell = np.repeat(np.arange(len(start) - 1), np.diff(start))
+    assert np.array_equal(cell[ids], slot_cell), "an atom sits in a slot of the wrong cell"
+    same = slot_cell[1:] == slot_cell[:-1]
+    assert np.all(ids[1:][same] > ids[:-1][same]), "atoms of one cell are not in id order"
+    return dims
+
+
+def on_the_walls(case):
+    """the first lattice planes of lj_case sit 0.25 A inside the box (+- 0.15 A of jitter); moved onto the walls, their atoms - 128 per wall, thermal speed
+    1.3 A/ps per axis - cross all six walls in both directions within a few dozen steps at 85 K"""
+    for k, L in zip(("x", "y", "z"), case["box"]):
+        v = np.round(np.mod(case[k] - 0.25, L), 6)
+        v[v >= L] = 0.0
+        case[k] = v
+    return case
+
+
+def wall_liquid():
+    """2 048 LJ atoms at 85 K with lattice planes on all six walls (system("lj") of tests/test_gpu_fold_kick.py): the smallest box that re-sorts lazily at
+    rc = 8.5 A, a few atoms crossing a wall on every step"""
+    return on_the_walls(inputs.lj_case((8, 8, 8), seed=71, vel_T=85.0))
+
+
 VEL = ("vx", "vy", "vz")
 FRC = ("fx", "fy", "fz")
 
