@@ -84,6 +84,12 @@ class _CnColumn(C.Structure):
     _fields_ = [("central", C.c_int32), ("ligand", C.c_int32), ("radius", C.c_double)]
 
 
+class _Stress(C.Structure):
+    _fields_ = [("step", C.c_int64), ("time", C.c_double), ("volume", C.c_double), ("kinetic", C.c_double * 6), ("virial", C.c_double * 6),
+                ("pressure", C.c_double * 6), ("pressure_iso", C.c_double), ("eng_vdw", C.c_double), ("eng_coul", C.c_double),
+                ("pairs", C.c_int64), ("pairs_dropped", C.c_int64)]
+
+
 class _Clock(C.Structure):
     _fields_ = [("step", C.c_int64), ("nose_chit", C.c_double), ("nose_conint", C.c_double), ("eng_kin", C.c_double)]
 
@@ -101,6 +107,7 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_init_device_slab", "aztot_rdf_setup", "aztot_rdf_sample", "aztot_rdf_reset", "aztot_rdf_shape", "aztot_rdf_counts", "aztot_rdf_values",
            "aztot_cn_setup", "aztot_cn_sample", "aztot_cn_shape", "aztot_cn_per_atom", "aztot_cn_table",
            "aztot_tcf_setup", "aztot_tcf_sample", "aztot_tcf_reset", "aztot_tcf_shape", "aztot_tcf_sums", "aztot_tcf_values",
+           "aztot_stress_setup", "aztot_stress_sample", "aztot_stress_get", "aztot_stress_per_atom",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
@@ -224,6 +231,10 @@ def lib():
         L.aztot_tcf_shape.argtypes = [C.c_void_p, _ip, _ip, C.POINTER(C.c_int64)]
         L.aztot_tcf_sums.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]
         L.aztot_tcf_values.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int]
+        L.aztot_stress_setup.argtypes = [C.c_void_p]
+        L.aztot_stress_sample.argtypes = [C.c_void_p]
+        L.aztot_stress_get.argtypes = [C.c_void_p, C.POINTER(_Stress)]
+        L.aztot_stress_per_atom.argtypes = [C.c_void_p, _dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -622,6 +633,31 @@ class Engine:
         a, b = np.zeros(max(need, 1)), np.zeros(max(need, 1))
         _check(lib().aztot_tcf_values(self.h, lag0, n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), need))
         return a[:need].reshape(n, ns), b[:need].reshape(n, ns)
+
+    # ---- pressure tensor (aztot_stress_*; pair set, terms and the order of the sums are stated in include/aztot.h) ----
+    def stress_setup(self):
+        """allocate the pressure-tensor sampler; refused (code -2) for slab handles, models with bonded terms and 'elec pme'"""
+        _check(lib().aztot_stress_setup(self.h))
+
+    def stress_sample(self):
+        """one snapshot of the current state; replaces the previous sample"""
+        _check(lib().aztot_stress_sample(self.h))
+
+    def stress(self):
+        """the totals of the last sample: 6-vectors (xx yy zz xy xz yz) as numpy arrays, kinetic and virial in eV, pressure in atm"""
+        s = _Stress()
+        _check(lib().aztot_stress_get(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k in ("step", "time", "volume", "pressure_iso", "eng_vdw", "eng_coul", "pairs", "pairs_dropped")}
+        for k in ("kinetic", "virial", "pressure"):
+            out[k] = np.array(getattr(s, k), dtype=np.float64)
+        return out
+
+    def stress_per_atom(self):
+        """w[atom id, component] of the last sample, eV: (N, 6) float64"""
+        n = _check(lib().aztot_stress_per_atom(self.h, None, 0))
+        out = np.zeros(max(n, 1))
+        _check(lib().aztot_stress_per_atom(self.h, out.ctypes.data_as(_dp), n))
+        return out[:n].reshape(-1, 6)
 
     def close(self):
         if getattr(self, "h", None):

@@ -122,6 +122,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  outcn (present, R, nCentral, nLigand, central species ids..., ligand species ids...: the 'outCN' line of control.txt; 0, 0, 0, 0 without one)
 //  ncn (n, then per line: central nucleus, ligand nucleus, R: the 'ncn' block of control.txt; n = 0 without one)
 //  vaf (steps between two rows of vaf.dat: the 'vaf' line of control.txt; 0 without one)
+//  stress (steps between two rows of stress.dat: the 'stress' line of control.txt, our extension; 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -195,6 +196,7 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             for (size_t i = 0; i < m.ncn_central.size(); i++) { v.push_back(m.ncn_central[i]); v.push_back(m.ncn_ligand[i]); v.push_back(m.ncn_radius[i]); }
         }
         else if (k == "vaf") v = {(double)m.vaf};
+        else if (k == "stress") v = {(double)m.stress};
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -595,6 +597,43 @@ int aztot_tcf_values(aztot_md* md, int lag0, int n, double* msd, double* vaf, in
         need = n * ns;
         if (msd && !a.empty()) std::memcpy(msd, a.data(), a.size() * sizeof(double));
         if (vaf && !b.empty()) std::memcpy(vaf, b.data(), b.size() * sizeof(double));
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_stress_setup(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().stress_setup(); });
+}
+
+int aztot_stress_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().stress_sample(); });
+}
+
+int aztot_stress_get(aztot_md* md, aztot_stress* out)
+{
+    if (!md || !md->eng || !out) return fail(AZTOT_ERR_ARG, "null argument");
+    return guarded([&] { md->eng->samplers().stress_get(*out); });
+}
+
+int aztot_stress_per_atom(aztot_md* md, double* w, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        aztot_stress probe;
+        md->eng->samplers().stress_get(probe);          // (refuses before the set-up or a sample)
+        const long long want = 6LL * md->eng->n_atoms_global();
+        if (want > 0x7fffffffLL) throw ArgError("stress: 6 x atoms does not fit the int this call returns");
+        need = (int)want;
+        if (!w && cap <= 0) return;
+        if (!w || cap < need) throw ArgError("stress: cap < 6 * n_atoms");
+        std::vector<double> v;
+        md->eng->samplers().stress_per_atom(v);
+        std::memcpy(w, v.data(), sizeof(double) * v.size());
     });
     return rc < 0 ? rc : need;
 }

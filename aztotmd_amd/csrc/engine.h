@@ -155,6 +155,7 @@ private:
     AtomArrays begin_sample() override;
     void end_sample(const char* where) override { check_launch(where); sync(); }
     void launch_timed(const char* name, const std::function<void()>& launch) override { timed(name, launch); }
+    Samplers::PairTables pair_tables() override { return {P_, S_, dPots_, hostStep_}; }
 
     Model model_;
     aztot_options opt_;

@@ -14,7 +14,9 @@
 //                   (msd_header / out_msd, out_md.cpp:19-29,89-124; main.cpp:163).  msd.dat itself follows the GPU program (wall-crossing counters)
 //   vaf.dat         velocity autocorrelation per species, with 'vaf n': a row every n steps after the equilibration (vaf_header / vaf_info, out_md.cpp:547-582;
 //                   main.cpp:71-75,115-117)
-// Both files are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
+//   stress.dat      OUR EXTENSION, with 'stress n' (a control.txt directive the reference does not know): the pressure tensor of aztot_stress_* in atm, a row at every
+//                   step c > 0 with c % n == 0: Pxx Pyy Pzz Pxy Pxz Pyz and P = (Pxx + Pyy + Pzz) / 3.  Without the line: no sampler, no file
+// Both displ.dat and vaf.dat are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
 // MSD / VAF schedule: ONE sampler (aztot_tcf_*) with a single origin, n_origins = 1 and origin_every = the number of samples the run takes.  Sample 0 is the
 // initial state (x0s, sys_init.cpp:545); a step c < nequil that writes a stat row samples and writes a displ.dat row; at c == nequil (> 0) the sampler is
 // reset and the state becomes the new origin (main.cpp:126-136; a stat row of that step follows and shows 0, as in the reference, which replaces x0s
@@ -25,7 +27,7 @@
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
 // stat row (c % stat == 0, and the last step), an RDF sample (which only reads the state: its place against the stat row of the same step does not matter),
-// the end of the equilibration or a vaf.dat row.
+// the end of the equilibration, a vaf.dat row or a stress.dat row.
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -211,6 +213,22 @@ int main(int argc, char** argv)
         std::fprintf(vf, "\n");
     }
     std::vector<double> msdRow(std::max(nSpec, 1)), vafRow(std::max(nSpec, 1));
+    // pressure tensor ('stress n', our extension): a snapshot every n steps
+    const int stressEvery = (int)q1(model, "stress");
+    bool stressOn = stressEvery > 0;
+    if (stressOn && aztot_stress_setup(md) != AZTOT_OK)
+    {
+        std::fprintf(stderr, "WARNING: stress directive not usable (%s): no stress.dat\n", aztot_last_error());
+        stressOn = false;
+    }
+    auto stress_due = [&](int c) { return stressOn && c >= 1 && c % stressEvery == 0; };
+    FILE* pf = nullptr;
+    if (stressOn)
+    {
+        pf = std::fopen((out + "/stress.dat").c_str(), "w");
+        if (!pf) { std::perror("stress.dat"); return 1; }
+        std::fprintf(pf, "time\tstep\tPxx\tPyy\tPzz\tPxy\tPxz\tPyz\tP\n");
+    }
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
@@ -225,8 +243,17 @@ int main(int argc, char** argv)
             if (done < nEq) n = std::min(n, nEq - done);
             n = std::min(n, (std::max(done, nEq) / vafEvery + 1) * vafEvery - done);
         }
+        if (stressOn) n = std::min(n, (done / stressEvery + 1) * stressEvery - done);
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
+        if (stress_due(done))
+        {
+            aztot_stress ps;
+            if (aztot_stress_sample(md) != AZTOT_OK || aztot_stress_get(md, &ps) != AZTOT_OK) die("stress sample");
+            std::fprintf(pf, "%f\t%d", ps.time, (int)ps.step);
+            for (int k = 0; k < 6; k++) std::fprintf(pf, "\t%.12g", ps.pressure[k]);
+            std::fprintf(pf, "\t%.12g\n", ps.pressure_iso);
+        }
         if (rdf_due(done))
         {
             if (aztot_rdf_sample(md) != AZTOT_OK) die("rdf sample");
@@ -269,6 +296,7 @@ int main(int argc, char** argv)
     std::fclose(mf);
     if (df) std::fclose(df);
     if (vf) std::fclose(vf);
+    if (pf) std::fclose(pf);
     if (rdfOn)
     {
         write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf.dat");

@@ -116,6 +116,8 @@ struct Model
     std::vector<double> ncn_radius;
     // 'vaf n' (read_sim, sys_init.cpp:883-884): steps between two rows of vaf.dat after the equilibration; 0: off
     int vaf = 0;
+    // 'stress n' (ours): steps between two rows of stress.dat; 0: off
+    int stress = 0;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

@@ -1,5 +1,5 @@
-// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h) and time correlation functions (tcf.hip.h) behind
-// aztot_rdf_* / aztot_cn_* / aztot_tcf_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
+// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h) and the
+// pressure tensor (stress.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
 // is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
 //
 // The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
@@ -23,12 +23,14 @@ class Samplers
 {
 public:
     // The engine as the samplers see it, and all they see of it
+    struct PairTables { StepParams P; SpecTable S; const DevPot* pots; long long step; };
     struct Host
     {
         virtual void quiesce() = 0;                         // everything queued or deferred by earlier calls has happened (before a set-up replaces buffers)
         virtual AtomArrays begin_sample() = 0;              // refuses a failed handle, completes the deferred end of the last aztot_step; the current arrays
         virtual void end_sample(const char* where) = 0;     // the launch check, then the stream drains: every sample ends here (one with a read-back passes twice)
         virtual void launch_timed(const char* name, const std::function<void()>& launch) = 0;   // under the per-kernel timer `name` when profiling is on
+        virtual PairTables pair_tables() = 0;               // what pair_visit needs, and the number of the last completed step (valid after begin_sample)
     protected:
         ~Host() = default;
     };
@@ -61,6 +63,12 @@ public:
     // lags [lag0, lag0 + n): pairs seen and the raw sums [lag - lag0][species] (each output optional)
     void tcf_sums(int lag0, int n, std::vector<long long>* count, std::vector<double>* msd, std::vector<double>* vaf);
     void tcf_values(int lag0, int n, std::vector<double>& msd, std::vector<double>& vaf);     // sum / (count * atoms of the species), 0 where that is 0
+
+    // pressure tensor of the pair terms (include/aztot.h states the pair set, the terms and the order of the sums): a snapshot of the last sample
+    void stress_setup();
+    void stress_sample();
+    void stress_get(aztot_stress& out);
+    void stress_per_atom(std::vector<double>& w);                      // [atom id][xx yy zz xy xz yz]
 
 private:
     // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
@@ -112,6 +120,18 @@ private:
         int n_lags() const { return M * E; }
     };
 
+    // per-atom columns by atom id (StressCol), their chunk sums and totals; the grid carries the canonical in-cell order
+    struct StressState : GridSort
+    {
+        bool isSetUp = false, sampled = false;
+        int sliceShift = 0, nChunk = 0, nChunkPad = 0;
+        size_t nPad = 0;
+        int32_t *arrivalId = nullptr, *canonRank = nullptr, *slotId = nullptr, *visits = nullptr, *drops = nullptr;
+        double *rad = nullptr, *cols = nullptr, *partials = nullptr, *totals = nullptr;
+        unsigned long long* counters = nullptr;
+        long long step = 0;             // of the last sample
+    };
+
     // the protocol every sampler follows, once (samplers.hip.h)
     void need_one_gpu(const char* what) const;
     static void need_setup(bool isSetUp, const char* name, const char* tail = "");
@@ -121,9 +141,11 @@ private:
 
     void grid_setup(GridSort& S, double edge);                                              // cells with an edge >= `edge`, at most about N of them; allocates the sort's buffers
     void grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3]);      // bin, scan, place the positions of A (timer names of the three stages)
+    void grid_count(GridSort& S, const AtomArrays& A, const char* const timerNames[2]);     // ... the first two: cell, arrival rank and cell offsets
     RdfState& rdf_state();
     CnState& cn_state(int kind, bool needSetup, bool needSample);
     TcfState& tcf_state();
+    StressState& stress_state(bool needSample);
 
     Host& host_;
     const Model& model_;            // the engine's (outlives the samplers)
@@ -134,6 +156,7 @@ private:
     RdfState rdf_;
     CnState cn_[2];                 // AZTOT_CN_SPECIES, AZTOT_CN_NUCLEI
     TcfState tcf_;
+    StressState stress_;
 };
 
 }  // namespace aztot

@@ -1,6 +1,7 @@
 // Samplers: the bodies (see samplers.h for the contract).  Included by engine.hip behind the kernel headers and its own helpers (HIP_CHECK, div_up).
 #pragma once
 #include "samplers.h"
+#include "stress.hip.h"
 
 namespace aztot {
 
@@ -48,6 +49,12 @@ template <typename F> void Samplers::sample(const char* where, F&& launch)
 
 Samplers::RdfState& Samplers::rdf_state() { need_setup(rdf_.nBins != 0, "rdf"); return rdf_; }
 Samplers::TcfState& Samplers::tcf_state() { need_setup(tcf_.M != 0, "tcf"); return tcf_; }
+Samplers::StressState& Samplers::stress_state(bool needSample)
+{
+    need_setup(stress_.isSetUp, "stress");
+    if (needSample && !stress_.sampled) throw ArgError("stress: aztot_stress_sample has not been called since the set-up");
+    return stress_;
+}
 Samplers::CnState& Samplers::cn_state(int kind, bool needSetup, bool needSample)
 {
     if (kind != AZTOT_CN_SPECIES && kind != AZTOT_CN_NUCLEI) throw ArgError("cn: kind must be AZTOT_CN_SPECIES or AZTOT_CN_NUCLEI");
@@ -91,14 +98,13 @@ void Samplers::grid_setup(GridSort& S, double edge)
     S.scanCounts = S.mem.alloc<Counts>(1, true, stream_); S.scanStats = S.mem.alloc<DevStats>(1, true, stream_);
 }
 
-// counting sort of the positions of A into the grid: wrapped coordinates and species | nucleus << 8 in slot order
-void Samplers::grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3])
+// the first two stages of the counting sort: cell and arrival rank of every atom, exclusive scan of the cell counts (which it leaves cleared for the next sample)
+void Samplers::grid_count(GridSort& S, const AtomArrays& A, const char* const timerNames[2])
 {
     const RdfGrid& G = S.grid;
     const int N = model_.nAt;
     const int nb = div_up(N, kBlock);
     timed(timerNames[0], [&] { hipLaunchKernelGGL(k_rdf_bin, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellCount); });
-    // exclusive scan of the cell counts (which it leaves cleared for the next sample)
     if (G.nCell <= kScanSingleMax)
         timed(timerNames[1], [&] { hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, G.nCell, S.cellCount, S.cellStart, S.scanCounts, S.scanStats, 0); });
     else
@@ -107,8 +113,15 @@ void Samplers::grid_fill(GridSort& S, const AtomArrays& A, const char* const tim
             hipLaunchKernelGGL(k_scan_totals, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, S.cellCount, S.chunkTot);
             hipLaunchKernelGGL(k_scan_apply, dim3(nChunk), dim3(kBlock), 0, stream_, G.nCell, S.cellCount, S.chunkTot, S.cellStart, S.scanCounts, S.scanStats, 0);
         });
+}
+
+// counting sort of the positions of A into the grid: wrapped coordinates and species | nucleus << 8 in slot order
+void Samplers::grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3])
+{
+    const int N = model_.nAt;
+    grid_count(S, A, timerNames);
     timed(timerNames[2], [&] {
-        hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellStart, S.x, S.y, S.z, S.kind);
+        hipLaunchKernelGGL(k_rdf_place, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.rankOf, S.cellStart, S.x, S.y, S.z, S.kind);
     });
 }
 
@@ -461,6 +474,115 @@ void Samplers::tcf_values(int lag0, int n, std::vector<double>& msd, std::vector
             msd[e] = w ? msd[e] / (double)w : 0.0;
             vaf[e] = w ? vaf[e] / (double)w : 0.0;
         }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Pressure tensor of the pair terms (stress.hip.h; pair set, terms and the order of the sums are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+void Samplers::stress_setup()
+{
+    // what the sampler cannot see makes the tensor wrong rather than incomplete: refused ("out of scope" -> AZTOT_ERR_INPUT), no sampler, the handle steps on
+    need_one_gpu("pressure tensors");
+    if (!model_.bondA.empty() || !model_.angC.empty()) throw std::runtime_error("out of scope: stress: the virial of bonds and angles is not built (the model has bonded terms)");
+    if (model_.elec_type == AZTOT_ELEC_EWALD) throw std::runtime_error("out of scope: stress: the reciprocal-space virial of 'elec pme' is not built");
+    StressState T;
+    const int N = model_.nAt;
+    T.isSetUp = true;
+    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    T.nChunk = std::max(1, div_up(N, kStressChunk));
+    T.nChunkPad = 1;
+    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
+    T.nPad = (size_t)T.nChunk * kStressChunk;
+    set_up(stress_, T, [&] {
+        const double biggest = std::max(box_.L[0], std::max(box_.L[1], box_.L[2]));
+        grid_setup(T, model_.rMax > 0.0 ? model_.rMax : biggest);
+        const size_t n = (size_t)std::max(N, 1);
+        T.arrivalId = T.mem.alloc<int32_t>(n, false, stream_); T.canonRank = T.mem.alloc<int32_t>(n, false, stream_);
+        T.slotId = T.mem.alloc<int32_t>(n, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.slotId, 0xff, sizeof(int32_t) * n, stream_));
+        T.rad = T.mem.alloc<double>(n, true, stream_);
+        T.cols = T.mem.alloc<double>((size_t)SC_COUNT * T.nPad, true, stream_);
+        T.visits = T.mem.alloc<int32_t>(T.nPad, true, stream_); T.drops = T.mem.alloc<int32_t>(T.nPad, true, stream_);
+        T.partials = T.mem.alloc<double>((size_t)SC_COUNT * T.nChunkPad, true, stream_);
+        T.totals = T.mem.alloc<double>(SC_COUNT, true, stream_);
+        T.counters = T.mem.alloc<unsigned long long>(2, true, stream_);
+    });
+}
+
+void Samplers::stress_sample()
+{
+    StressState& T = stress_state(false);
+    sample("stress kernels", [&](const AtomArrays& A) {
+        const PairTables E = host_.pair_tables();
+        const int N = model_.nAt;
+        T.sampled = false;
+        T.step = E.step;
+        HIP_CHECK(hipMemsetAsync(T.counters, 0, 2 * sizeof(unsigned long long), stream_));
+        if (N > 0)
+        {
+            static const char* const names[2] = {"k_stress_bin", "k_stress_scan"};
+            grid_count(T, A, names);
+            const int nb = div_up(N, kBlock);
+            // arrival order -> ids ascending inside every cell
+            timed("k_stress_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, T.cellOf, T.rankOf, T.cellStart, T.arrivalId); });
+            timed("k_stress_rank", [&] { hipLaunchKernelGGL(k_stress_rank, dim3(nb), dim3(kBlock), 0, stream_, A, N, T.cellOf, T.cellStart, T.arrivalId, T.canonRank); });
+            timed("k_stress_place", [&] {
+                hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, T.grid, A, N, T.cellOf, T.canonRank, T.cellStart, T.x, T.y, T.z, T.kind);
+            });
+            timed("k_stress_gather", [&] {
+                hipLaunchKernelGGL(k_stress_gather, dim3(nb), dim3(kBlock), 0, stream_, E.S, A, N, (int)E.P.use_radii, T.nPad, T.cellOf, T.canonRank, T.cellStart, T.slotId,
+                                   T.rad, T.cols);
+            });
+            const int blocks = (int)((((long long)N << T.sliceShift) + kBlock - 1) / kBlock);
+            timed("k_stress_pairs", [&] {
+                hipLaunchKernelGGL(k_stress_pairs, dim3(blocks), dim3(kBlock), 0, stream_, T.grid, E.P, E.S, E.pots, N, T.sliceShift, T.nPad, T.cellStart, T.x, T.y, T.z,
+                                   T.kind, T.rad, T.slotId, T.cols, T.visits, T.drops);
+            });
+        }
+        timed("k_stress_chunks", [&] {
+            hipLaunchKernelGGL(k_stress_chunks, dim3(T.nChunk), dim3(kBlock), 0, stream_, T.nPad, T.nChunkPad, T.cols, T.visits, T.drops, T.partials, T.counters);
+        });
+        timed("k_stress_fold", [&] { hipLaunchKernelGGL(k_stress_fold, dim3(SC_COUNT), dim3(kBlock), 0, stream_, T.nChunkPad, T.partials, T.totals); });
+    });
+    T.sampled = true;
+}
+
+void Samplers::stress_get(aztot_stress& out)
+{
+    const StressState& T = stress_state(true);
+    double tot[SC_COUNT];
+    unsigned long long cnt[2];
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(tot, T.totals, sizeof(tot), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(cnt, T.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    std::memset(&out, 0, sizeof(out));
+    out.step = T.step;
+    out.time = (double)T.step * model_.tSt;
+    out.volume = box_.L[0] * box_.L[1] * box_.L[2];
+    for (int c = 0; c < 6; c++)
+    {
+        out.virial[c] = tot[SC_WXX + c];
+        out.kinetic[c] = tot[SC_KXX + c];
+        out.pressure[c] = (out.kinetic[c] + out.virial[c]) / out.volume * units::pressure_factor;
+    }
+    out.pressure_iso = (out.pressure[0] + out.pressure[1] + out.pressure[2]) / 3.0;
+    out.eng_vdw = tot[SC_EVDW]; out.eng_coul = tot[SC_ECOUL];
+    out.pairs = (long long)(cnt[0] / 2); out.pairs_dropped = (long long)(cnt[1] / 2);      // every unordered pair is visited from both ends
+}
+
+void Samplers::stress_per_atom(std::vector<double>& w)
+{
+    const StressState& T = stress_state(true);
+    const int N = model_.nAt;
+    w.assign((size_t)N * 6, 0.0);
+    if (N == 0) return;
+    std::vector<double> col((size_t)N);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int c = 0; c < 6; c++)
+    {
+        HIP_CHECK(hipMemcpy(col.data(), T.cols + (size_t)(SC_WXX + c) * T.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+        for (int i = 0; i < N; i++) w[(size_t)i * 6 + c] = col[i];
+    }
 }
 
 }  // namespace aztot

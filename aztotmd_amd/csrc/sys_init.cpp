@@ -374,6 +374,9 @@ void read_sim(const std::string& dir, Model& m)
     // velocity autocorrelation function: 'vaf n', a row of vaf.dat every n steps after the equilibration (sys_init.cpp:883-884); 0 or no line: off
     m.vaf = seek_int_or(f, " vaf %d ", 0);
     if (m.vaf < 0) fail("ERROR[414] negative period in 'vaf' directive of control.txt");
+    // pressure tensor: 'stress n', a row of stress.dat every n steps (our extension: the reference has no such directive); 0 or no line: off
+    m.stress = seek_int_or(f, " stress %d ", 0);
+    if (m.stress < 0) fail("ERROR[415] negative period in 'stress' directive of control.txt");
     // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
     m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
     if (seek_value(f, " rdf %lf ", &m.rdf_rmax))

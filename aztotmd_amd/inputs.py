@@ -227,6 +227,8 @@ def write_input_files(case, directory, stat=200):
             f.writelines("%s %s %r\n" % (a, b, float(r)) for a, b, r in case["ncn"])
         if case.get("vaf"):             # rows of vaf.dat every n steps after the equilibration: sys_init.cpp:883-884
             f.write("vaf\t%d\n" % int(case["vaf"]))
+        if case.get("stress"):          # rows of stress.dat every n steps (our directive: the pressure tensor of aztot_stress_*)
+            f.write("stress\t%d\n" % int(case["stress"]))
         f.write("stat\t%d\n" % stat)
     if case.get("bonds") is not None and len(case["bonds"]):
         with open(os.path.join(directory, "bonds.txt"), "w") as f:       # read_bondlist, bonds.cpp:25-110

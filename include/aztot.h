@@ -379,6 +379,55 @@ int aztot_tcf_sums(aztot_md *md, int lag0, int n, int64_t *count, double *msd_su
 /* the normalised values in the same layout (if cap >= n * n_species); returns n * n_species */
 int aztot_tcf_values(aztot_md *md, int lag0, int n, double *msd, double *vaf, int cap);
 
+/* ---- pressure tensor: virial of the pair terms plus the kinetic part, one snapshot per sample ------------------------------------------------------
+   The reference's only pressure is the momentum carried across the box walls (aztot_stats.pressure, main.cpp:143-163): zero in a crystal at rest, shot
+   noise in a liquid, no off-diagonal components.  This sampler is ours.  aztot_stats.pressure is unchanged by it.
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT; so are a model with bonded terms (the virial of bonds
+   and angles is not built) and 'elec pme' (the reciprocal-space virial is not built).  A refused set-up leaves no sampler and a handle that steps on.
+   Running averages are the caller's business: a sample replaces the previous one.
+
+   A SAMPLE reads the state aztot_md_to_host would return at that moment: wrapped x y z, vx vy vz with the last step's second half-kick completed,
+   types and radii.
+
+   PAIR SEPARATION.  d = r_i - r_j per axis, then delta_periodic (box.cpp:180-205: one shift by L where |d| > L / 2);
+   r2 = (dx*dx + dy*dy) + dz*dz in fp64, every operation rounded on its own: the rule of aztot_cn_sample.
+   PAIR SET.  A pair takes part iff r2 <= rMax^2, rMax the largest cut-off of the model (aztot_model_query "rmax"; at most half the box).
+   PAIR TERM.  The step kernels' own pair function supplies f = -(1/r) dU/dr and both energies: the per-pair VdW cut-off, the charged-species test,
+   direct and Fennell Coulomb, surk with the per-atom radii, and the drop rule f^2 > 1e10 (integrators.cpp:170-174): energy booked, force and virial
+   not.  The external field (elecfield) is not translation-invariant and contributes nothing.
+   VIRIAL, eV, components ab in the order xx yy zz xy xz yz:   w_i[ab] = 1/2 sum_j f_ij d_a d_b,   W[ab] = sum_i w_i[ab].
+   KINETIC.  K[ab] = sum_i m_i v_a v_b, m in internal units (amu * m_scale, aztot_model_query "m_scale"); atoms of a frozen species contribute nothing.
+   PRESSURE, atm.  P[ab] = (K[ab] + W[ab]) / V * 1.58e6, the constant of the wall-momentum pressure (main.cpp:147); pressure_iso = (Pxx + Pyy + Pzz) / 3.
+   eng_vdw, eng_coul: the pair energies of the same walk (half per visit); pairs: unordered pairs inside rMax, exact; pairs_dropped: those the drop
+   rule took the force of.
+
+   ORDER OF THE SUMS.  No floating-point atomics anywhere.  The totals W, K, eng_vdw and eng_coul are the tree of the time correlation functions
+   (above, 'PER-SPECIES SUMS IN ONE FIXED ORDER') over the per-atom values in atom-id order.  The per-atom sums over partners run in an order that is a
+   function of the sampled state alone (wrapped positions, ids, types, radii, N and the box): neighbour cells in a fixed order, ids ascending inside a
+   cell, dealt to a number of lanes that depends on N only and folded in a fixed order.  It does not depend on the slot order the engine's sort has
+   left, on arrival order or on the run: two handles holding the same state return the same bits.
+
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.
+   Out of scope: the virial of bonds and angles, the reciprocal Ewald part, slab ranks, running averages, any change to aztot_stats.pressure.
+   Errors: null handle, sampling or reading before the set-up, reading before a sample, 0 < cap < 6 * n_atoms -> AZTOT_ERR_ARG; a handle that failed
+   earlier refuses to sample but can still be read. */
+typedef struct aztot_stress
+{
+    int64_t step; double time, volume;
+    double kinetic[6], virial[6];      /* eV; xx yy zz xy xz yz */
+    double pressure[6], pressure_iso;  /* atm */
+    double eng_vdw, eng_coul;          /* eV, pair energies of the same walk */
+    int64_t pairs, pairs_dropped;
+} aztot_stress;                        /* 208 bytes */
+/* (re)allocate; forgets the last sample */
+int aztot_stress_setup(aztot_md *md);
+/* one snapshot of the current state; replaces the previous sample */
+int aztot_stress_sample(aztot_md *md);
+/* the totals of the last sample */
+int aztot_stress_get(aztot_md *md, aztot_stress *out);
+/* w[6 * atom id + component] of the last sample; returns 6 * n_atoms (w null and cap 0: the size alone; a shorter buffer is AZTOT_ERR_ARG) */
+int aztot_stress_per_atom(aztot_md *md, double *w, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
