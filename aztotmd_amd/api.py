@@ -84,6 +84,10 @@ class _CnColumn(C.Structure):
     _fields_ = [("central", C.c_int32), ("ligand", C.c_int32), ("radius", C.c_double)]
 
 
+class _AdfColumn(C.Structure):
+    _fields_ = [("central", C.c_int32), ("ligand_a", C.c_int32), ("ligand_b", C.c_int32), ("reserved", C.c_int32), ("radius_a", C.c_double), ("radius_b", C.c_double)]
+
+
 class _Stress(C.Structure):
     _fields_ = [("step", C.c_int64), ("time", C.c_double), ("volume", C.c_double), ("kinetic", C.c_double * 6), ("virial", C.c_double * 6),
                 ("pressure", C.c_double * 6), ("pressure_iso", C.c_double), ("eng_vdw", C.c_double), ("eng_coul", C.c_double),
@@ -108,6 +112,8 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_cn_setup", "aztot_cn_sample", "aztot_cn_shape", "aztot_cn_per_atom", "aztot_cn_table",
            "aztot_tcf_setup", "aztot_tcf_sample", "aztot_tcf_reset", "aztot_tcf_shape", "aztot_tcf_sums", "aztot_tcf_values",
            "aztot_stress_setup", "aztot_stress_sample", "aztot_stress_get", "aztot_stress_per_atom",
+           "aztot_adf_setup", "aztot_adf_sample", "aztot_adf_reset", "aztot_adf_shape", "aztot_adf_edges", "aztot_adf_counts", "aztot_adf_values",
+           "aztot_adf_neighbours",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
@@ -235,6 +241,14 @@ def lib():
         L.aztot_stress_sample.argtypes = [C.c_void_p]
         L.aztot_stress_get.argtypes = [C.c_void_p, C.POINTER(_Stress)]
         L.aztot_stress_per_atom.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.aztot_adf_setup.argtypes = [C.c_void_p, C.c_int, C.POINTER(_AdfColumn), C.c_int]
+        L.aztot_adf_sample.argtypes = [C.c_void_p]
+        L.aztot_adf_reset.argtypes = [C.c_void_p]
+        L.aztot_adf_shape.argtypes = [C.c_void_p, _ip, _ip, C.POINTER(C.c_int64)]
+        L.aztot_adf_edges.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.aztot_adf_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int]
+        L.aztot_adf_values.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
+        L.aztot_adf_neighbours.argtypes = [C.c_void_p, _ip, C.c_int]
         _LIB = L
     return _LIB
 
@@ -658,6 +672,56 @@ class Engine:
         out = np.zeros(max(n, 1))
         _check(lib().aztot_stress_per_atom(self.h, out.ctypes.data_as(_dp), n))
         return out[:n].reshape(-1, 6)
+
+    # ---- bond-angle distributions (aztot_adf_*; columns, separation and the bin rule are stated in include/aztot.h) ----
+    def adf_setup(self, n_bins, cols):
+        """cols: [(central, ligand_a, ligand_b, R_a, R_b)] with species indices; (re)allocates and zeroes, returns n_bins"""
+        c = (_AdfColumn * max(len(cols), 1))()
+        for i, (ce, a, b, ra, rb) in enumerate(cols):
+            c[i].central, c[i].ligand_a, c[i].ligand_b, c[i].reserved, c[i].radius_a, c[i].radius_b = int(ce), int(a), int(b), 0, float(ra), float(rb)
+        return _check(lib().aztot_adf_setup(self.h, int(n_bins), c, len(cols)))
+
+    def adf_sample(self):
+        """add the triplets of the current configuration to the totals; refused (code -2, nothing added) when an atom has more than 256 neighbours"""
+        _check(lib().aztot_adf_sample(self.h))
+
+    def adf_reset(self):
+        _check(lib().aztot_adf_reset(self.h))
+
+    def adf_shape(self):
+        """(n_bins, n_cols, samples)"""
+        nb, nc, sm = C.c_int32(), C.c_int32(), C.c_int64()
+        _check(lib().aztot_adf_shape(self.h, C.byref(nb), C.byref(nc), C.byref(sm)))
+        return nb.value, nc.value, sm.value
+
+    def adf_edges(self):
+        """the n_bins + 1 edge values T_b = cos |cos| of the bin rule"""
+        n = _check(lib().aztot_adf_edges(self.h, None, 0))
+        out = np.zeros(n)
+        _check(lib().aztot_adf_edges(self.h, out.ctypes.data_as(_dp), n))
+        return out
+
+    def adf_counts(self):
+        """(samples, counts[n_bins, n_cols]) - uint64 totals"""
+        nb, nc, _ = self.adf_shape()
+        out = np.zeros(nb * nc, dtype=np.uint64)
+        samples = C.c_int64()
+        _check(lib().aztot_adf_counts(self.h, C.byref(samples), out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size))
+        return samples.value, out.reshape(nb, nc)
+
+    def adf_values(self):
+        """(theta[n_bins] in degrees, p[n_bins, n_cols]): bin centres and the probability density per degree of each column"""
+        nb, nc, _ = self.adf_shape()
+        theta, p = np.zeros(nb), np.zeros(nb * nc)
+        _check(lib().aztot_adf_values(self.h, theta.ctypes.data_as(_dp), p.ctypes.data_as(_dp), p.size))
+        return theta, p.reshape(nb, nc)
+
+    def adf_neighbours(self):
+        """int32 [n_atoms] in ORIGINAL atom order: neighbours at the last sample (a refused one included), -1 where the atom is central to no column"""
+        n = _check(lib().aztot_adf_neighbours(self.h, None, 0))
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().aztot_adf_neighbours(self.h, out.ctypes.data_as(_ip), n))
+        return out[:n]
 
     def close(self):
         if getattr(self, "h", None):

@@ -123,6 +123,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  ncn (n, then per line: central nucleus, ligand nucleus, R: the 'ncn' block of control.txt; n = 0 without one)
 //  vaf (steps between two rows of vaf.dat: the 'vaf' line of control.txt; 0 without one)
 //  stress (steps between two rows of stress.dat: the 'stress' line of control.txt, our extension; 0 without one)
+//  adf (n_bins, every, n, then per line: central, ligand_a, ligand_b species ids, R_a, R_b: the 'adf' block of control.txt, our extension; 0, 0, 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -197,6 +198,11 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
         }
         else if (k == "vaf") v = {(double)m.vaf};
         else if (k == "stress") v = {(double)m.stress};
+        else if (k == "adf")
+        {
+            v = {(double)m.adf_bins, (double)m.adf_every, (double)m.adf_cols.size()};
+            for (const auto& c : m.adf_cols) { v.push_back(c.central); v.push_back(c.ligand_a); v.push_back(c.ligand_b); v.push_back(c.radius_a); v.push_back(c.radius_b); }
+        }
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -634,6 +640,109 @@ int aztot_stress_per_atom(aztot_md* md, double* w, int cap)
         std::vector<double> v;
         md->eng->samplers().stress_per_atom(v);
         std::memcpy(w, v.data(), sizeof(double) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_adf_setup(aztot_md* md, int n_bins, const aztot_adf_column* cols, int n_cols)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int nb = 0;
+    const int rc = guarded([&] { nb = md->eng->samplers().adf_setup(n_bins, cols, n_cols); });
+    return rc < 0 ? rc : nb;
+}
+
+int aztot_adf_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().adf_sample(); });
+}
+
+int aztot_adf_reset(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().adf_reset(); });
+}
+
+int aztot_adf_shape(aztot_md* md, int* n_bins, int* n_cols, int64_t* samples)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] {
+        int nb = 0, nc = 0;
+        long long sm = 0;
+        md->eng->samplers().adf_shape(nb, nc, sm);
+        if (n_bins) *n_bins = nb;
+        if (n_cols) *n_cols = nc;
+        if (samples) *samples = sm;
+    });
+}
+
+int aztot_adf_edges(aztot_md* md, double* T, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        std::vector<double> v;
+        md->eng->samplers().adf_edges(v);
+        need = (int)v.size();
+        if (!T && cap <= 0) return;
+        if (!T || cap < need) throw ArgError("adf: cap < n_bins + 1");
+        std::memcpy(T, v.data(), sizeof(double) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_adf_counts(aztot_md* md, int64_t* samples, uint64_t* counts, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, nc = 0;
+        long long sm = 0;
+        md->eng->samplers().adf_shape(nb, nc, sm);
+        need = nb * nc;
+        if (counts && cap < need) throw ArgError("adf: cap < n_bins * n_cols");
+        if (samples) *samples = sm;
+        if (!counts) return;
+        std::vector<unsigned long long> c;
+        md->eng->samplers().adf_counts(c);
+        for (int k = 0; k < need; k++) counts[k] = c[k];
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_adf_values(aztot_md* md, double* theta, double* p, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, nc = 0;
+        long long sm = 0;
+        md->eng->samplers().adf_shape(nb, nc, sm);
+        need = nb * nc;
+        if ((theta || p) && cap < need) throw ArgError("adf: cap < n_bins * n_cols");
+        if (!theta && !p) return;
+        std::vector<double> tv, pv;
+        md->eng->samplers().adf_values(tv, pv);
+        if (theta) std::memcpy(theta, tv.data(), sizeof(double) * tv.size());
+        if (p) std::memcpy(p, pv.data(), sizeof(double) * pv.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_adf_neighbours(aztot_md* md, int32_t* n, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, nc = 0;
+        long long sm = 0;
+        md->eng->samplers().adf_shape(nb, nc, sm);          // (refuses before the set-up)
+        need = md->eng->n_atoms_global();
+        if (n && cap < need) throw ArgError("adf: cap < n_atoms");
+        std::vector<int32_t> v;
+        md->eng->samplers().adf_neighbours(v);              // (refuses before a sample)
+        if (n) std::memcpy(n, v.data(), sizeof(int32_t) * v.size());
     });
     return rc < 0 ? rc : need;
 }

@@ -19,6 +19,7 @@
 #include "pair_list.hip.h"
 #include "rdf.hip.h"
 #include "cn.hip.h"
+#include "adf.hip.h"
 #include "tcf.hip.h"
 #include "slab.hip.h"
 

@@ -16,6 +16,11 @@
 //                   main.cpp:71-75,115-117)
 //   stress.dat      OUR EXTENSION, with 'stress n' (a control.txt directive the reference does not know): the pressure tensor of aztot_stress_* in atm, a row at every
 //                   step c > 0 with c % n == 0: Pxx Pyy Pzz Pxy Pxz Pyz and P = (Pxx + Pyy + Pzz) / 3.  Without the line: no sampler, no file
+//   adf.dat         OUR EXTENSION, with an 'adf <n_bins> <every> <n>' block (n lines '<central> <ligand1> <ligand2> <R1> <R2>', species names): the bond-angle
+//                   distributions of aztot_adf_*, header "theta" + "\t<ligand1>-<central>-<ligand2>" per column, a row per bin: the bin centre in degrees and the
+//                   probability density per degree of each column.  Sampled after every completed step c > nequil with c % every == 0; with every == 0, or when
+//                   the run ended before the first sample, once on the final configuration.  Without the block: no sampler, no file
+//   adf_n.dat       the same layout with the raw counts
 // Both displ.dat and vaf.dat are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
 // MSD / VAF schedule: ONE sampler (aztot_tcf_*) with a single origin, n_origins = 1 and origin_every = the number of samples the run takes.  Sample 0 is the
 // initial state (x0s, sys_init.cpp:545); a step c < nequil that writes a stat row samples and writes a displ.dat row; at c == nequil (> 0) the sampler is
@@ -27,7 +32,7 @@
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
 // stat row (c % stat == 0, and the last step), an RDF sample (which only reads the state: its place against the stat row of the same step does not matter),
-// the end of the equilibration, a vaf.dat row or a stress.dat row.
+// the end of the equilibration, a vaf.dat row, a stress.dat row or a sample of the bond-angle distributions.
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -97,6 +102,35 @@ static bool write_cn(aztot_md* md, int kind, const std::vector<aztot_cn_column>&
     }
     std::fclose(f);
     return true;
+}
+
+// adf.dat: header "theta\t<ligand1>-<central>-<ligand2>...", rows "%f" theta then "\t%f" per column; adf_n.dat: the same with the raw counts as "%llu"
+static void write_adf(aztot_md* md, const std::vector<aztot_adf_column>& cols, const std::vector<std::string>& names, const std::string& path, const std::string& pathN)
+{
+    int nb = 0, nc = 0;
+    if (aztot_adf_shape(md, &nb, &nc, nullptr) != AZTOT_OK) die("adf shape");
+    std::vector<double> theta(std::max(nb, 1)), p((size_t)std::max(nb * nc, 1));
+    std::vector<uint64_t> cnt(p.size());
+    if (aztot_adf_values(md, theta.data(), p.data(), nb * nc) < 0) die("adf values");
+    if (aztot_adf_counts(md, nullptr, cnt.data(), nb * nc) < 0) die("adf counts");
+    for (int raw = 0; raw < 2; raw++)
+    {
+        const std::string& file = raw ? pathN : path;
+        FILE* f = std::fopen(file.c_str(), "w");
+        if (!f) { std::perror(file.c_str()); std::exit(1); }
+        std::fprintf(f, "theta");
+        for (const auto& c : cols) std::fprintf(f, "\t%s-%s-%s", names[c.ligand_a].c_str(), names[c.central].c_str(), names[c.ligand_b].c_str());
+        std::fprintf(f, "\n");
+        for (int b = 0; b < nb; b++)
+        {
+            std::fprintf(f, "%f", theta[b]);
+            for (int k = 0; k < nc; k++)
+                if (raw) std::fprintf(f, "\t%llu", (unsigned long long)cnt[(size_t)b * nc + k]);
+                else std::fprintf(f, "\t%f", p[(size_t)b * nc + k]);
+            std::fprintf(f, "\n");
+        }
+        std::fclose(f);
+    }
 }
 
 // "<time>\t<step>" + "\t%f" per species: the row layout of out_msd's MSD columns and of vaf_info
@@ -229,6 +263,26 @@ int main(int argc, char** argv)
         if (!pf) { std::perror("stress.dat"); return 1; }
         std::fprintf(pf, "time\tstep\tPxx\tPyy\tPzz\tPxy\tPxz\tPyz\tP\n");
     }
+    // bond-angle distributions ('adf' block, our extension): columns from the model, samples on their own schedule, the files at the end
+    std::vector<double> adfq(3);
+    {
+        const int n = aztot_model_query(model, "adf", nullptr, 0);
+        if (n < 3) die("adf");
+        adfq.resize(n);
+        if (aztot_model_query(model, "adf", adfq.data(), n) < 0) die("adf");
+    }
+    const int adfEvery = (int)adfq[1];
+    bool adfOn = adfq[0] > 0.0;
+    std::vector<aztot_adf_column> adfCols;
+    for (int i = 0; adfOn && i < (int)adfq[2]; i++)
+        adfCols.push_back({(int32_t)adfq[3 + 5 * i], (int32_t)adfq[4 + 5 * i], (int32_t)adfq[5 + 5 * i], 0, adfq[6 + 5 * i], adfq[7 + 5 * i]});
+    if (adfOn && aztot_adf_setup(md, (int)adfq[0], adfCols.data(), (int)adfCols.size()) < 0)
+    {
+        std::fprintf(stderr, "WARNING: adf directive not usable (%s): no adf.dat\n", aztot_last_error());
+        adfOn = false;
+    }
+    auto adf_due = [&](int c) { return adfOn && adfEvery > 0 && c > nEq && c % adfEvery == 0; };
+    int adfTaken = 0;
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
@@ -244,8 +298,14 @@ int main(int argc, char** argv)
             n = std::min(n, (std::max(done, nEq) / vafEvery + 1) * vafEvery - done);
         }
         if (stressOn) n = std::min(n, (done / stressEvery + 1) * stressEvery - done);
+        if (adfOn && adfEvery > 0) n = std::min(n, (std::max(done, nEq) / adfEvery + 1) * adfEvery - done);
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
+        if (adf_due(done))
+        {
+            if (aztot_adf_sample(md) != AZTOT_OK) die("adf sample");
+            adfTaken++;
+        }
         if (stress_due(done))
         {
             aztot_stress ps;
@@ -301,6 +361,11 @@ int main(int argc, char** argv)
     {
         write_rdf(md, AZTOT_RDF_SPECIES, names, out + "/rdf.dat");
         if (nucl) write_rdf(md, AZTOT_RDF_NUCLEI, nnames, out + "/rdf_n.dat");
+    }
+    if (adfOn)
+    {
+        if (adfTaken == 0 && aztot_adf_sample(md) != AZTOT_OK) die("adf sample");
+        write_adf(md, adfCols, names, out + "/adf.dat", out + "/adf_n.dat");
     }
     // coordination numbers: one snapshot of the final configuration (main.cu:446-448)
     auto query_all = [&](const char* key) {

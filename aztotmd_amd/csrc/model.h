@@ -118,6 +118,10 @@ struct Model
     int vaf = 0;
     // 'stress n' (ours): steps between two rows of stress.dat; 0: off
     int stress = 0;
+    // 'adf <n_bins> <every> <n>' and n lines '<central> <ligand1> <ligand2> <R1> <R2>' (ours): bond-angle distributions, a sample every `every` steps after the
+    // equilibration (0: one sample of the final configuration); adf_bins == 0: off
+    int adf_bins = 0, adf_every = 0;
+    std::vector<aztot_adf_column> adf_cols;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

@@ -1,5 +1,5 @@
-// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h) and the
-// pressure tensor (stress.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
+// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h), the
+// pressure tensor (stress.hip.h) and bond-angle distributions (adf.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* / aztot_adf_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
 // is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
 //
 // The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
@@ -18,6 +18,7 @@
 namespace aztot {
 
 struct Counts;
+struct AdfTables;
 
 class Samplers
 {
@@ -69,6 +70,16 @@ public:
     void stress_sample();
     void stress_get(aztot_stress& out);
     void stress_per_atom(std::vector<double>& w);                      // [atom id][xx yy zz xy xz yz]
+
+    // bond-angle distributions (include/aztot.h states the columns, the separation and the bin rule): integer totals over the samples
+    int adf_setup(int nBins, const aztot_adf_column* cols, int nCols); // (re)allocates and zeroes; returns the number of bins
+    void adf_sample();                                                 // refuses (before any total changes) when an atom has more than AZTOT_ADF_MAX_NEIGHBOURS
+    void adf_reset();
+    void adf_shape(int& nBins, int& nCols, long long& samples);
+    void adf_edges(std::vector<double>& T);                            // the n_bins + 1 edge values
+    void adf_counts(std::vector<unsigned long long>& counts);          // [bin][column]
+    void adf_values(std::vector<double>& theta, std::vector<double>& p);   // bin centres in degrees, density per degree [bin][column]
+    void adf_neighbours(std::vector<int32_t>& n);                      // [atom id] at the last sample (a refused one included), -1: not a central atom
 
 private:
     // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
@@ -132,6 +143,22 @@ private:
         long long step = 0;             // of the last sample
     };
 
+    // columns normalised to ligand_a <= ligand_b, the edge table, uint64 totals [bin][column]
+    struct AdfState : GridSort
+    {
+        int nBins = 0;                  // 0: not set up
+        std::vector<aztot_adf_column> cols;
+        std::vector<double> edges;
+        long long samples = 0;
+        bool counted = false;           // the neighbour counts of a sample are there
+        int sliceShift = 0, useLds = 0;
+        int32_t *slotId = nullptr, *neigh = nullptr;
+        unsigned long long *summary = nullptr, *totals = nullptr;   // summary: the largest neighbour count << 32 | the id of an atom that has it
+        AdfTables* tables = nullptr;
+        int8_t* colOf = nullptr;
+        double* dEdges = nullptr;
+    };
+
     // the protocol every sampler follows, once (samplers.hip.h)
     void need_one_gpu(const char* what) const;
     static void need_setup(bool isSetUp, const char* name, const char* tail = "");
@@ -146,6 +173,7 @@ private:
     CnState& cn_state(int kind, bool needSetup, bool needSample);
     TcfState& tcf_state();
     StressState& stress_state(bool needSample);
+    AdfState& adf_state();
 
     Host& host_;
     const Model& model_;            // the engine's (outlives the samplers)
@@ -157,6 +185,7 @@ private:
     CnState cn_[2];                 // AZTOT_CN_SPECIES, AZTOT_CN_NUCLEI
     TcfState tcf_;
     StressState stress_;
+    AdfState adf_;
 };
 
 }  // namespace aztot

@@ -585,4 +585,188 @@ void Samplers::stress_per_atom(std::vector<double>& w)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Bond-angle distributions (adf.hip.h; columns, separation and the bin rule are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+Samplers::AdfState& Samplers::adf_state() { need_setup(adf_.nBins != 0, "adf"); return adf_; }
+
+int Samplers::adf_setup(int nBins, const aztot_adf_column* cols, int nCols)
+{
+    need_one_gpu("bond-angle distributions");
+    if (nBins < 1 || nBins > AZTOT_ADF_MAX_BINS) throw ArgError("adf: n_bins must be in [1, AZTOT_ADF_MAX_BINS]");
+    if (!cols || nCols < 1 || nCols > AZTOT_ADF_MAX_COLUMNS) throw ArgError("adf: the number of columns must be in [1, AZTOT_ADF_MAX_COLUMNS]");
+    const int nSpec = model_.nSpec();
+    AdfState T;
+    AdfTables tab;
+    std::vector<int8_t> colOf(kSpecCap * kSpecCap * kSpecCap, (int8_t)-1);
+    for (int g = 0; g < kSpecCap; g++) { tab.rowMax2[g] = -1.0; tab.ligMask[g] = 0; }
+    for (int c = 0; c < kAdfMaxCols; c++) tab.ra2[c] = tab.rb2[c] = 0.0;
+    double rBig = 0.0;
+    for (int c = 0; c < nCols; c++)
+    {
+        aztot_adf_column col = cols[c];
+        if (col.central < 0 || col.central >= nSpec || col.ligand_a < 0 || col.ligand_a >= nSpec || col.ligand_b < 0 || col.ligand_b >= nSpec)
+            throw ArgError("adf: species index of a column out of range");
+        if (col.reserved != 0) throw ArgError("adf: the reserved field of a column must be 0");
+        if (!(col.radius_a > 0.0) || !(col.radius_b > 0.0) || !std::isfinite(col.radius_a) || !std::isfinite(col.radius_b))
+            throw ArgError("adf: the radii of a column must be positive");
+        if (col.ligand_a == col.ligand_b && col.radius_a != col.radius_b) throw ArgError("adf: equal ligand species need equal radii");
+        if (col.ligand_a > col.ligand_b) { std::swap(col.ligand_a, col.ligand_b); std::swap(col.radius_a, col.radius_b); }
+        int8_t& e = colOf[(col.central * kSpecCap + col.ligand_a) * kSpecCap + col.ligand_b];
+        if (e >= 0) throw ArgError("adf: the same (central, {ligand_a, ligand_b}) names two columns");
+        e = (int8_t)c;
+        colOf[(col.central * kSpecCap + col.ligand_b) * kSpecCap + col.ligand_a] = (int8_t)c;
+        tab.ra2[c] = col.radius_a * col.radius_a; tab.rb2[c] = col.radius_b * col.radius_b;
+        tab.rowMax2[col.central] = std::max(tab.rowMax2[col.central], std::max(tab.ra2[c], tab.rb2[c]));
+        tab.ligMask[col.central] |= (1 << col.ligand_a) | (1 << col.ligand_b);
+        rBig = std::max(rBig, std::max(col.radius_a, col.radius_b));
+        T.cols.push_back(col);
+    }
+    T.nBins = nBins;
+    // T_b = c_b |c_b|, c_b = cos(pi b / n_bins) rounded to double; the exactly known values are forced.  cos(pi b / n) evaluated in double loses its
+    // relative accuracy towards 90 degrees (the argument's rounding error is absolute); here it is the sine of the complementary angle in the middle half
+    // and a cosine of the angle counted from the nearer end elsewhere, in long double: c_b is the nearest double or its neighbour, T_b within 2 ulp
+    T.edges.resize((size_t)nBins + 1);
+    for (int b = 0; b <= nBins; b++)
+    {
+        const long double pi = 3.141592653589793238462643383279502884L, n = (long double)nBins;
+        const int k = nBins - 2 * b;
+        const double cb = 2 * std::abs(k) <= nBins ? (double)sinl(pi * (long double)k / (2.0L * n))
+                                                   : (k > 0 ? (double)cosl(pi * (long double)b / n) : (double)-cosl(pi * (long double)(nBins - b) / n));
+        T.edges[b] = cb * std::fabs(cb);
+    }
+    T.edges[0] = 1.0; T.edges[nBins] = -1.0;
+    if (nBins % 2 == 0) T.edges[nBins / 2] = 0.0;
+    const int N = model_.nAt;
+    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    const size_t nEnt = (size_t)nBins * nCols;
+    T.useLds = nEnt * sizeof(uint32_t) <= (size_t)kAdfHistBudget ? 1 : 0;
+    set_up(adf_, T, [&] {
+        grid_setup(T, rBig);
+        const size_t n = (size_t)std::max(N, 1);
+        T.slotId = T.mem.alloc<int32_t>(n, false, stream_); T.neigh = T.mem.alloc<int32_t>(n, false, stream_);
+        T.summary = T.mem.alloc<unsigned long long>(1, true, stream_);
+        T.totals = T.mem.alloc<unsigned long long>(nEnt, true, stream_);
+        T.tables = T.mem.alloc<AdfTables>(1, false, stream_);
+        T.colOf = T.mem.alloc<int8_t>(colOf.size(), false, stream_);
+        T.dEdges = T.mem.alloc<double>(T.edges.size(), false, stream_);
+        HIP_CHECK(hipMemcpy(T.tables, &tab, sizeof(tab), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(T.colOf, colOf.data(), colOf.size(), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(T.dEdges, T.edges.data(), T.edges.size() * sizeof(double), hipMemcpyHostToDevice));
+    });
+    return adf_.nBins;
+}
+
+void Samplers::adf_reset()
+{
+    AdfState& S = adf_state();
+    HIP_CHECK(hipMemsetAsync(S.totals, 0, (size_t)S.nBins * S.cols.size() * 8, stream_));
+    S.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Samplers::adf_sample()
+{
+    AdfState& S = adf_state();
+    sample("adf kernels", [&](const AtomArrays& A) {
+        const int N = model_.nAt, nCols = (int)S.cols.size();
+        if (N == 0) return;
+        static const char* const names[3] = {"adf_bin", "adf_scan", "adf_place"};
+        grid_fill(S, A, names);
+        const int nb = div_up(N, kBlock);
+        unsigned long long summary = 0;
+        HIP_CHECK(hipMemsetAsync(S.summary, 0, sizeof(summary), stream_));
+        S.counted = false;
+        timed("adf_neigh", [&] {
+            hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId);
+            const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL(k_adf_neigh, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, S.tables, N, S.sliceShift, S.cellStart, S.x, S.y, S.z, S.kind, S.slotId, S.neigh,
+                               S.summary);
+        });
+        HIP_CHECK(hipMemcpyAsync(&summary, S.summary, sizeof(summary), hipMemcpyDeviceToHost, stream_));
+        host_.end_sample("adf neighbours");     // the tile and the lanes per atom are sized on the host from the counts just read back
+        S.counted = true;
+        const long long most = (long long)(summary >> 32);
+        if (most > AZTOT_ADF_MAX_NEIGHBOURS)     // nothing has been added yet: totals and the sample count stay as they were, the engine is settled and drained
+            throw std::runtime_error("adf: atom " + std::to_string((unsigned)(summary & 0xffffffffull)) + " has " + std::to_string(most) +
+                                     " neighbours inside the largest radius of its columns, more than AZTOT_ADF_MAX_NEIGHBOURS = " +
+                                     std::to_string(AZTOT_ADF_MAX_NEIGHBOURS) + ": nothing was added");
+        if (most < 2) return;                    // no atom has a pair of neighbours
+        // lanes per central atom (fitted to the sweep of tools/adf_cost.py): the fewest, from 4, with which the launch has 65536 lanes and the
+        // histogram and the tiles of a workgroup (256 / lanes of them, each `cap` neighbours) stay inside kAdfLdsComfort, so that four workgroups share a CU;
+        // more while they do not fit at all.  Every lane of an atom walks all 27 cells, so the gather's cost per atom grows with the lanes; the pairs do not care
+        const int cap = (int)most;
+        const size_t histBytes = S.useLds ? (size_t)S.nBins * nCols * sizeof(uint32_t) : 0;
+        int laneShift = 2;
+        // AZTOT_ADF_LANES = 4 / 8 / 16 / 32 / 64: a measurement switch (tools/adf_cost.py, tests) that replaces the rule (but for the room in LDS); the results do not depend on it
+        int forced = 0;
+        if (const char* e = std::getenv("AZTOT_ADF_LANES")) forced = std::atoi(e);
+        if (forced == 4 || forced == 8 || forced == 16 || forced == 32 || forced == 64)
+        {
+            while ((1 << laneShift) < forced) laneShift++;
+            while (laneShift < 6 && histBytes + (size_t)(kBlock >> laneShift) * cap * kAdfTileBytes > (size_t)kAdfLdsBudget) laneShift++;
+        }
+        else while (laneShift < 6 && (((long long)N << laneShift) < 65536 || histBytes + (size_t)(kBlock >> laneShift) * cap * kAdfTileBytes > (size_t)kAdfLdsComfort))
+            laneShift++;
+        const int groups = kBlock >> laneShift;
+        const size_t lds = histBytes + (size_t)groups * cap * kAdfTileBytes;
+        // a workgroup serves at most N / blocks + groups atoms between two flushes: the overflow bound stated at k_adf_triplets
+        const int blocks = std::max(div_up(N, kAdfAtomsPerFlush), std::min(kAdfMaxBlocks, div_up(N, groups)));
+        timed("adf_triplets", [&] {
+            hipLaunchKernelGGL(k_adf_triplets, dim3(blocks), dim3(kBlock), lds, stream_, S.grid, S.tables, N, laneShift, cap, S.nBins, nCols, S.useLds, S.cellStart, S.x,
+                               S.y, S.z, S.kind, S.colOf, S.dEdges, S.totals);
+        });
+    });
+    S.samples++;
+}
+
+void Samplers::adf_shape(int& nBins, int& nCols, long long& samples)
+{
+    const AdfState& S = adf_state();
+    nBins = S.nBins; nCols = (int)S.cols.size(); samples = S.samples;
+}
+
+void Samplers::adf_edges(std::vector<double>& T) { T = adf_state().edges; }
+
+void Samplers::adf_counts(std::vector<unsigned long long>& counts)
+{
+    const AdfState& S = adf_state();
+    counts.resize((size_t)S.nBins * S.cols.size());
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(counts.data(), S.totals, counts.size() * 8, hipMemcpyDeviceToHost));
+}
+
+// p[bin][column] = count / (column total * width in degrees): a density per degree that sums to 1 / width; 0 where the column is empty
+void Samplers::adf_values(std::vector<double>& theta, std::vector<double>& p)
+{
+    std::vector<unsigned long long> c;
+    adf_counts(c);
+    const int nBins = adf_.nBins, nCols = (int)adf_.cols.size();
+    const double width = 180.0 / (double)nBins;
+    theta.resize(nBins);
+    p.assign((size_t)nBins * nCols, 0.0);
+    for (int b = 0; b < nBins; b++) theta[b] = (b + 0.5) * width;
+    for (int k = 0; k < nCols; k++)
+    {
+        unsigned long long tot = 0;
+        for (int b = 0; b < nBins; b++) tot += c[(size_t)b * nCols + k];
+        if (!tot) continue;
+        for (int b = 0; b < nBins; b++) p[(size_t)b * nCols + k] = (double)c[(size_t)b * nCols + k] / ((double)tot * width);
+    }
+}
+
+void Samplers::adf_neighbours(std::vector<int32_t>& out)
+{
+    const AdfState& S = adf_state();
+    if (!S.counted) throw ArgError("adf: aztot_adf_sample has not been called since the set-up");
+    const int N = model_.nAt;
+    out.assign((size_t)N, -1);
+    if (N == 0) return;
+    std::vector<int32_t> ids(N), cnt(N);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(ids.data(), S.slotId, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(cnt.data(), S.neigh, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    for (int s = 0; s < N; s++) out[ids[s]] = cnt[s];
+}
+
 }  // namespace aztot

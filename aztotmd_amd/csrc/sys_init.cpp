@@ -377,6 +377,38 @@ void read_sim(const std::string& dir, Model& m)
     // pressure tensor: 'stress n', a row of stress.dat every n steps (our extension: the reference has no such directive); 0 or no line: off
     m.stress = seek_int_or(f, " stress %d ", 0);
     if (m.stress < 0) fail("ERROR[415] negative period in 'stress' directive of control.txt");
+    // bond-angle distributions: 'adf <n_bins> <every> <n>' and n lines '<central> <ligand1> <ligand2> <R1> <R2>' with species names (our extension, the
+    // columns of aztot_adf_setup); no line: off.  ERROR[416]: the shape of the block, ERROR[417]: what its lines name
+    m.adf_bins = m.adf_every = 0; m.adf_cols.clear();
+    char adfWord[64] = {0};
+    if (seek_value(f, " adf %63s", adfWord))
+    {
+        char* end = nullptr;
+        const long nb = std::strtol(adfWord, &end, 10);
+        int every = 0, n = 0;
+        if (end == adfWord || *end != '\0' || std::fscanf(f, " %d %d", &every, &n) != 2) fail("ERROR[416] malformed 'adf' directive in control.txt: adf <n_bins> <every> <n>");
+        if (nb < 1 || nb > AZTOT_ADF_MAX_BINS) fail("ERROR[416] n_bins of the 'adf' directive must be between 1 and " + std::to_string(AZTOT_ADF_MAX_BINS));
+        if (every < 0) fail("ERROR[416] negative period in 'adf' directive of control.txt");
+        if (n < 1 || n > AZTOT_ADF_MAX_COLUMNS) fail("ERROR[416] the 'adf' directive needs between 1 and " + std::to_string(AZTOT_ADF_MAX_COLUMNS) + " lines");
+        for (int i = 0; i < n; i++)
+        {
+            char c[64] = {0}, a[64] = {0}, b[64] = {0};
+            double ra = 0.0, rb = 0.0;
+            const std::string at = " (line " + std::to_string(i + 1) + " of the adf section of control.txt)";
+            if (std::fscanf(f, " %63s %63s %63s %lf %lf", c, a, b, &ra, &rb) != 5 || !(ra > 0.0) || !(rb > 0.0))
+                fail("ERROR[416] malformed line: <central> <ligand1> <ligand2> <R1> <R2> with positive radii" + at);
+            aztot_adf_column col = {species_by_name(m, c), species_by_name(m, a), species_by_name(m, b), 0, ra, rb};
+            if (col.central < 0 || col.ligand_a < 0 || col.ligand_b < 0)
+                fail(std::string("ERROR[417] unknown species name (") + (col.central < 0 ? c : (col.ligand_a < 0 ? a : b)) + ")" + at);
+            if (col.ligand_a == col.ligand_b && ra != rb) fail("ERROR[417] equal ligand species need equal radii" + at);
+            for (const auto& o : m.adf_cols)        // (the ligands are kept in the order of the line: the column's name in adf.dat; aztot_adf_setup normalises)
+                if (o.central == col.central && std::min(o.ligand_a, o.ligand_b) == std::min(col.ligand_a, col.ligand_b) &&
+                    std::max(o.ligand_a, o.ligand_b) == std::max(col.ligand_a, col.ligand_b))
+                    fail(std::string("ERROR[417] the angle ") + a + "-" + c + "-" + b + " is given twice" + at);
+            m.adf_cols.push_back(col);
+        }
+        m.adf_bins = (int)nb; m.adf_every = every;
+    }
     // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
     m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
     if (seek_value(f, " rdf %lf ", &m.rdf_rmax))

@@ -229,6 +229,10 @@ def write_input_files(case, directory, stat=200):
             f.write("vaf\t%d\n" % int(case["vaf"]))
         if case.get("stress"):          # rows of stress.dat every n steps (our directive: the pressure tensor of aztot_stress_*)
             f.write("stress\t%d\n" % int(case["stress"]))
+        if case.get("adf"):             # bond-angle distributions (our directive, aztot_adf_*): (n_bins, every, [(central, ligand1, ligand2, R1, R2)]) with species names
+            nb, every, cols = case["adf"]
+            f.write("adf\t%d\t%d\t%d\n" % (int(nb), int(every), len(cols)))
+            f.writelines("%s %s %s %r %r\n" % (c, a, b, float(ra), float(rb)) for c, a, b, ra, rb in cols)
         f.write("stat\t%d\n" % stat)
     if case.get("bonds") is not None and len(case["bonds"]):
         with open(os.path.join(directory, "bonds.txt"), "w") as f:       # read_bondlist, bonds.cpp:25-110

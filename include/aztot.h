@@ -428,6 +428,67 @@ int aztot_stress_get(aztot_md *md, aztot_stress *out);
 /* w[6 * atom id + component] of the last sample; returns 6 * n_atoms (w null and cap 0: the size alone; a shorter buffer is AZTOT_ERR_ARG) */
 int aztot_stress_per_atom(aztot_md *md, double *w, int cap);
 
+/* ---- bond-angle distributions: the angle at a central atom between two of its neighbours, integer totals over the samples --------------------------
+   The reference has no such output (nothing under its src/ computes an angle between neighbours): like the pressure tensor, this sampler is ours.
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.
+
+   COLUMNS.  Column (c, a, b, R_a, R_b), species indices: the angle at a central atom i of species c between a neighbour j of species a and a
+   neighbour k of species b; i, j and k are three different atoms.  Both shell tests are strict: 0 < r2_ij < R_a^2 and 0 < r2_ik < R_b^2 (an atom at
+   distance exactly 0 has no direction: it is no neighbour).  (c, a, b) and (c, b, a) are the same column: the set-up normalises to a <= b and swaps the
+   radii with them.  a == b: every unordered pair {j, k} is counted once; a != b: every (j, k) once.  A species without atoms is fine: the column stays zero.
+   The set-up rejects with AZTOT_ERR_ARG: a null handle, n_bins outside [1, AZTOT_ADF_MAX_BINS], n_cols outside [1, AZTOT_ADF_MAX_COLUMNS], a species
+   index out of range, a non-zero `reserved`, a radius <= 0, a == b with R_a != R_b, the same (c, {a, b}) twice.  A refused set-up leaves the earlier one.
+
+   SEPARATION.  The rule of aztot_cn_sample on the positions aztot_md_to_host returns: u = r_j - r_i per axis, then delta_periodic (one shift by L where
+   |d| > L / 2); r2 = (ux*ux + uy*uy) + uz*uz in fp64, every operation rounded on its own.  A radius may exceed L / 2: each partner is still seen once,
+   through its nearest image.
+
+   BINS, without acos, sqrt or a division.  n_bins bins of equal width in the angle: bin b is [180 b / n_bins, 180 (b + 1) / n_bins) degrees, the last
+   one includes 180.  The edge table (aztot_adf_edges) is made on the host once per set-up: c_b = cos(pi b / n_bins) rounded to double (evaluated in extended
+   precision, as a sine of the complementary angle towards 90 degrees: the nearest double or its neighbour), T_b = c_b * |c_b| in double (within 2 ulp
+   of its exact value), with the exactly known values forced: T_0 = 1, T_n_bins = -1, and T_(n_bins / 2) = 0 when n_bins is even.  For a triplet with u = r_j - r_i, v = r_k - r_i:
+       dot = (ux*vx + uy*vy) + uz*vz,   s = dot * |dot|,   p = r2_ij * r2_ik          (each operation rounded on its own)
+       bin = #{ b in [1, n_bins - 1] : s <= fl(T_b * p) }
+   a function of the state and the table alone: a few lines of numpy that read the table through aztot_adf_edges reproduce every count exactly.
+
+   TOTALS.  uint64 counts[bin][column] and the number of samples, accumulated over the samples as the RDF's; exact, independent of the order of
+   arrival; cleared by a reset or a set-up only.  Values: p[bin][column] = count / (column total * width in degrees), a probability density per degree
+   (it sums to 1 / width; no sin(theta) weighting), 0 where the column total is 0; theta = (b + 0.5) * width.
+
+   NEIGHBOUR CAP.  A central atom's neighbours are held on chip.  The neighbours of an atom of species c are the atoms j != i with 0 < r2 < R^2, R the
+   largest radius of any column c is central to, whose species is a ligand of such a column.  A sample counts them first (aztot_adf_neighbours).  If any
+   atom has more than AZTOT_ADF_MAX_NEIGHBOURS, the sample fails with AZTOT_ERR_INPUT before any total changes: totals and the sample count stay as they
+   were, the message names an atom id (the largest id among those with the largest count) and its count, the handle is not marked failed and steps on.
+   aztot_adf_neighbours then returns the counts of the refused sample.
+
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.
+   Out of scope: nuclei groups, angles over the bonded topology, slab ranks, dihedrals, sin(theta) weighting.
+   Errors: sampling or reading before the set-up, aztot_adf_neighbours before a sample, a cap too small for a non-null buffer -> AZTOT_ERR_ARG; a handle
+   that failed earlier refuses to sample but can still be read. */
+#define AZTOT_ADF_MAX_BINS 3600
+#define AZTOT_ADF_MAX_COLUMNS 64
+#define AZTOT_ADF_MAX_NEIGHBOURS 256
+typedef struct aztot_adf_column
+{
+    int32_t central, ligand_a, ligand_b, reserved;     /* species indices; reserved must be 0 */
+    double radius_a, radius_b;
+} aztot_adf_column;                                    /* 32 bytes */
+/* (re)allocates and zeroes; returns n_bins */
+int aztot_adf_setup(aztot_md *md, int n_bins, const aztot_adf_column *cols, int n_cols);
+/* adds the triplets of the current configuration to the totals */
+int aztot_adf_sample(aztot_md *md);
+/* zero totals and sample count */
+int aztot_adf_reset(aztot_md *md);
+int aztot_adf_shape(aztot_md *md, int *n_bins, int *n_cols, int64_t *samples);
+/* the n_bins + 1 edge values T_b; returns n_bins + 1 (T null and cap 0: the size alone) */
+int aztot_adf_edges(aztot_md *md, double *T, int cap);
+/* totals counts[bin * n_cols + column]; returns n_bins * n_cols (samples and counts are each optional) */
+int aztot_adf_counts(aztot_md *md, int64_t *samples, uint64_t *counts, int cap);
+/* bin centres in degrees (n_bins of them) and p[bin * n_cols + column]; returns n_bins * n_cols (theta and p are each optional; cap counts p's entries) */
+int aztot_adf_values(aztot_md *md, double *theta, double *p, int cap);
+/* neighbours of each atom (by id) at the last sample, -1: not a central atom; returns n_atoms */
+int aztot_adf_neighbours(aztot_md *md, int32_t *n, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
