@@ -125,6 +125,8 @@ class DebugBit(enum.IntFlag):
     (tests/test_debug_bits.py holds the two lists to each other)."""
     DBG_BUILD_PHASE_MASK = 3
     DBG_ALWAYS_CLEANUP = 4
+    DBG_FOLD_DRIFT = 8
+    DBG_NO_FOLD_DRIFT = 16
     DBG_KICK_EVERY_STEP = 128
     DBG_LARGE_KICK_PATH = 256
     DBG_GENERIC_PAIR = 512

@@ -101,6 +101,8 @@ enum DebugBit : unsigned
 {
     DBG_BUILD_PHASE_MASK = 3,            // NOT result-preserving (phase timing of k_build_lists): 1 staging only, 2 + candidates and filter, 3 + compaction
     DBG_ALWAYS_CLEANUP = 4,              // the clean-up launch behind every k_pair_list whatever the system size (small systems on one GPU run without it: Engine::choose_optimism)
+    DBG_FOLD_DRIFT = 8,                  // the next step's drift in the list kernel too (KICK_DRIFT, Engine::foldDriftOk_) whatever the system size: implies what DBG_FOLD_KICK implies ...
+    DBG_NO_FOLD_DRIFT = 16,              // ... or off: a folded step is KICK_BOTH with k_drift_plain2 behind it
     DBG_KICK_EVERY_STEP = 128,           // k_integrate2 launched every step
     DBG_LARGE_KICK_PATH = 256,           // the deferred half-kick of large systems whatever the size
     DBG_GENERIC_PAIR = 512,              // the generic (switch-based) pair body instead of a specialised mode
@@ -131,8 +133,10 @@ enum KickFuse
 {
     KICK_NONE = 0,                       // nothing: the force is stored, somebody else kicks
     KICK_SECOND = 1,                     // this step's second half-kick (+ the kinetic energy on steps that book energies); force and velocity are stored
-    KICK_BOTH = 2                        // k_pair_list only, never with the clean-up launch: this step's second half-kick AND the next step's first, as two
+    KICK_BOTH = 2,                       // k_pair_list only, never with the clean-up launch: this step's second half-kick AND the next step's first, as two
                                          // separate roundings; the velocity is stored, the force is NOT - the next step is a drift (k_drift_plain2)
+    KICK_DRIFT = 3                       // KICK_BOTH, and the same lane drifts the atom as k_drift_plain2 would: the new position goes into the second set of
+                                         // coordinate arrays (NextStep::xd/yd/zd), the next step opens with no launch of its own
 };
 
 // StepParams::potSet, the potential set the pair kernels are chosen for (Engine::construct decides, AZTOT_PAIR_DISPATCH): any mix of potentials, radii and species;

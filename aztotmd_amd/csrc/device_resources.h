@@ -105,6 +105,17 @@ public:
         pending_.push_back({it->second, a, b});
         if (pending_.size() > 8192) { check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize"); drain(); }
     }
+    // something that happened inside another kernel's launch and has no time of its own (a step opened by the pair kernel of the step before): counted only
+    void count(const char* name)
+    {
+        auto it = index_.find(name);
+        if (it == index_.end())
+        {
+            it = index_.emplace(name, (int)timers_.size()).first;
+            timers_.push_back(KernelTimer{name, 0.0, 0});
+        }
+        timers_[it->second].calls += 1;
+    }
     // (the stream has drained) adds the elapsed times of the launches since the last call to the totals
     void drain()
     {

@@ -82,7 +82,7 @@ namespace aztot {
 //                    applied and settle must apply it                      call), look at the end of a call (replay)   next step_body (the device flag
 //                                                                                                                      DevStats::pendingKick makes the next
 //                                                                                                                      integrate kernel pay it)
-//  preIntegrated_    the step being launched was opened by the previous    launch_pair (next-step fusion),             sort_and_forces (consumes it), run_steps,   -
+//  preIntegrated_    the step being launched was opened by the previous    launch_pair (next-step fusion, KICK_DRIFT), sort_and_forces (consumes it), run_steps,   -
 //                    step's pair kernel / boundary kernel                  launch_step_kernels (k_boundary_radi)       graph capture, replay
 //  kickFolded_       the step being launched was kicked by the previous    launch_pair (the list launch that took up   sort_and_forces (consumes it: k_drift_plain2 -
 //                    step's k_pair_list (KICK_BOTH), which stored v and    foldKick_)                                  instead of k_integrate_plain2), graph        a folded step is always followed by a plain
@@ -296,6 +296,8 @@ private:
     bool foldKickOk_ = false;       // this engine may fold (decided once)
     bool foldKick_ = false;         // the list launch of the step being launched is asked to fold
     bool kickFolded_ = false;       // ... and the previous step's did: the step being launched opens with k_drift_plain2
+    bool foldDriftOk_ = false;      // ... and a folding launch also drifts (KICK_DRIFT; decided once): the new positions go to altXyz_ and the next step is
+                                    // preIntegrated_, not kickFolded_
     bool overlapHalo_ = false;      // the pair launch in flight is split: interior cells now, boundary cells once evHalo_ has fired
     int candMode_ = 0;              // for the pair launch in flight: 0 none, 1 record, 2 plain step of the lazy re-sort
     // next-step fusion (pair_tile.hip.h NextStep): on plain NVE steps of a lazy run on one GPU the pair kernel's epilogue also does the next step's

@@ -284,15 +284,20 @@ void Engine::construct()
         const bool plainNve = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP);
         const int variant = pair_variant();
         // small systems / slabs are bound by launch latency: the tile kernel's epilogue does it (one kernel less: C2 0.083 -> 0.063 ms).
-        // On 1 M atoms that 13-lane read-modify-write of the velocities makes L2 write lines back several times (rocprofv3: 221 MB
-        // instead of 63 + 76 MB per step) for no gain, so large systems fold it into the next step's streaming k_integrate1_bin.
+        // Large systems are not: they fold the kick into the next step's streaming k_integrate1_bin.  (Round 2 measured 221 MB per step for that
+        // 13-lane read-modify-write of the velocities in the tile kernel of the day; in today's k_pair_list the same three arrays read and three
+        // written cost +3-3.7 us and +6 MB of HBM traffic per launch - KICK_BOTH, NOTES.md - which is what the folding below rests on.)
         // Large systems on one GPU that walk pair lists go one step further: on steps that book no energies and are followed by a plain step of the same
         // run, k_pair_list applies this step's second half-kick AND the next step's first and stores the velocity instead of the force (KICK_BOTH); the next
         // step is then a drift (k_drift_plain2: 76 B per atom instead of k_integrate_plain2's 124).  Above the sizes that fuse the next step (they keep what
         // they have); DBG_FOLD_KICK forces it on whatever the size - such an engine neither fuses the next step nor kicks in the tile kernel's epilogue -,
         // DBG_NO_FOLD_KICK switches it off.  Which steps fold: launch_step_kernels.
         foldKickOk_ = plainNve && nranks_ == 1 && lists_.on && variant == 2 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & (DBG_NO_FOLD_KICK | DBG_PLAIN_ONE_ATOM)) &&
-                      (capacity_ > 2 * kFuseKickMaxAtoms || (debug_ & DBG_FOLD_KICK)) && !((debug_ & DBG_FUSE_NEXT) && !(debug_ & DBG_NO_FUSE_NEXT));
+                      (capacity_ > 2 * kFuseKickMaxAtoms || (debug_ & (DBG_FOLD_KICK | DBG_FOLD_DRIFT))) && !((debug_ & DBG_FUSE_NEXT) && !(debug_ & DBG_NO_FUSE_NEXT));
+        // ... and the same lane drifts the atom too (KICK_DRIFT): the step behind a folded one then opens with no launch of its own.  Its positions go to the
+        // second set of coordinate arrays next-step fusion uses, swapped in after the launch.  On by size where kick folding is, DBG_FOLD_DRIFT whatever the
+        // size (it implies DBG_FOLD_KICK), DBG_NO_FOLD_DRIFT off: KICK_BOTH with k_drift_plain2 behind it, as before
+        foldDriftOk_ = foldKickOk_ && !(debug_ & DBG_NO_FOLD_DRIFT) && (capacity_ > 2 * kFuseKickMaxAtoms || (debug_ & DBG_FOLD_DRIFT));
         fuseEpilogue_ = plainNve && variant >= 2 && capacity_ <= kFuseKickMaxAtoms && !(debug_ & DBG_LARGE_KICK_PATH) && !foldKickOk_;
         // (bonded and reciprocal-space forces are added behind the pair kernel and are complete before the next step's integrate kernel just the same: runs with
         //  bonds / angles / the Ewald sum defer the kick too - they cannot take the pair kernel's epilogue, which would kick with the pair forces alone.
@@ -313,11 +318,10 @@ void Engine::construct()
                               nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
         fuseNextTstat_ = radiFuse && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
         if (((plainNve && !foldKickOk_ && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
-        {
             fuseNextOk_ = true;
+        if (fuseNextOk_ || foldDriftOk_)
             for (int b = 0; b < 2; b++)
                 for (int d = 0; d < 3; d++) altXyz_[b][d] = dev_alloc<double>((size_t)capacity_, true);
-        }
     }
     // displacement bound instead of the per-atom check on plain steps: wherever k_integrate1_bin<2> opens every plain step (engines that fuse the next
     // step into the pair kernel keep the per-atom check there); DBG_CHECK_EVERY_ATOM switches it off
@@ -1045,12 +1049,20 @@ void Engine::launch_pair()
                 const bool fold = foldKick_ && skipCleanup && !fuseNext_ && !wantEnergies;
                 foldKick_ = false;
                 StepParams QL = Q;
-                if (fold) { QL.fuseKick = KICK_BOTH; nx.pendingAfter = 0; kickFolded_ = true; }
+                // ... and the next step's drift with them (KICK_DRIFT): that step is then opened like a fused one, not by k_drift_plain2
+                const bool foldDrift = fold && foldDriftOk_;
+                if (fold) { QL.fuseKick = foldDrift ? KICK_DRIFT : KICK_BOTH; nx.pendingAfter = 0; kickFolded_ = !foldDrift; }
+                if (foldDrift)
+                {
+                    nx.xd = altXyz_[cur_][0]; nx.yd = altXyz_[cur_][1]; nx.zd = altXyz_[cur_][2];
+                    nx.driftBlocks = div_up(div_up(capacity_, 2), kBlock);           // (the grid of the k_drift_plain2 launch this replaces, sort_and_forces)
+                    if (profile_ && !capturing_) timers_.count("fold_drift");
+                }
                 const PairLaunch CL = pair_launch(QL);
                 timed("pair_list", [&] { splitBlocks = launch_pair_list(CL, PairRange(), pl, nx, wantEnergies); });
                 if (!skipCleanup)
                     timed("pair_cleanup", [&] { splitBlocks += launch_pair_cleanup(C, PairRange(), pl, nx); });
-                if (fuseNext_)
+                if (fuseNext_ || foldDrift)
                 {   // the next step's positions are in the other set of coordinate arrays now
                     AtomArrays& A = cur();
                     std::swap(A.x, altXyz_[cur_][0]); std::swap(A.y, altXyz_[cur_][1]); std::swap(A.z, altXyz_[cur_][2]);

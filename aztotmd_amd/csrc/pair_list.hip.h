@@ -10,7 +10,8 @@
 // k_pair_list stand down and the clean-up launch of k_pair_tile stage everything with a wider stencil), so no pair inside rc can be missing and a step is
 //   1. gather the candidates into LDS (coordinates relative to the cell centre: same numbers, same arithmetic as k_pair_tile);
 //   2. every lane walks ITS list: entry -> LDS record -> exact r^2 <= rc^2 test -> potential (pair_body, shared with k_pair_tile);
-//   3. optionally (NextStep, small systems) the epilogue opens the next step: second half-kick, first half-kick, drift.
+//   3. optionally the epilogue opens the next step: second half-kick, first half-kick, drift (NextStep, small systems: everything k_integrate1_bin<2>
+//      does; KICK_DRIFT, large ones: the lean form below).
 // Lanes are (atom slot, slice) with slot = lane / NS and NS = min(8, 64 / atoms in the cell) slices per atom: 13-16 atoms run 4 slices each, 17-21
 // three, 22-32 two - whatever the cell holds, at least two thirds of the lanes work (the power-of-two layout of round 2 fell to half at 17 atoms, which
 // is what a liquid's cells of rc + skin hold).  Slices of one atom are neighbouring lanes: they are folded with lane shifts in a fixed order.
@@ -56,6 +57,91 @@ inline size_t pair_list_lds_bytes(const StepParams& P, const PairLists& L)
 }
 inline int pair_list_rec_bytes(const StepParams&) { return 24; }
 inline int pair_list_entry_scale(const StepParams& P) { return P.single_lj ? 24 : 1; }     // what the builder multiplies a record number by: byte offset, or the number itself
+
+// KICK_DRIFT: the drift of the NEXT step behind the two folded kicks, by the lane that has just stored the atom's final velocity - what k_drift_plain2
+// (integrate_plain2_body<false>, kernels.hip.h) does for the atom in a launch of its own, the same operations in the same order with the next step's
+// values (cycle step P.cycleStep + 1), so positions, flags and counters are bit-identical.  That kernel's side effects and who takes care of each here:
+//   x, y, z                      fold_drift_atom; into the second set of coordinate arrays (NextStep::xd/yd/zd: other waves still gather this step's positions)
+//   DevStats::step += 1          k_pair_list's last lines
+//   PS_EFIELD partials zeroed    k_pair_list's last lines, the same entries (NextStep::driftBlocks)
+//   Counts::maxStep2, cycMaxRun  fold_drift_finish: integer-bit atomicMax behind a relaxed load, once per wave - and only in a wave that holds a step
+//                                longer than the maxima it read when it started (after the first waves of a window: nobody)
+//   Counts::lazyViolated / Ever  fold_drift_finish, numbered from the step being opened (next_step_finish's convention)
+//   DevStats::specCross          fold_drift_finish, one atomic per crossing
+//   wall momenta, crossing counts  fold_drift_finish, into this wave's partial slot (next_wall_sum); a wall's momentum sum is then added in another order
+//                                than k_drift_plain2's workgroups add it: equal to a few ulps, the counts exactly
+// Lean, because the kernel is bound by instruction issue: the reference position is read only by a lane the displacement bound cannot clear (P.boundSkip,
+// as in k_drift_plain2; the bound itself is taken in f32, rounded to the safe side: it decides who looks, never what is found); a crossing is one bit, the
+// sums are built by the rare wave that has one; and a wave whose cell has no periodic image in its stencil (`interior`) skips the six image_of evaluations
+// as long as every one of its atoms is and stays within a cell edge and a quarter of its cell's centre - such a position lies strictly inside the box
+// before and after, image 0 both times.
+__device__ __forceinline__ void fold_drift_atom(const StepParams& P, const SpecTable& S, const NextStep& N, int i, int t, double x, double y, double z,
+                                                double xi, double yi, double zi, double vx, double vy, double vz, bool interior, double room2,
+                                                double& len2, int& cross, int& violated)
+{
+    const double x0 = x, y0 = y, z0 = z;
+    double dx = 0.0, dy = 0.0, dz = 0.0;
+    if (!S.frozen[t]) { dx = vx * P.dt; dy = vy * P.dt; dz = vz * P.dt; x += dx; y += dy; z += dz; }
+    len2 = dx * dx + dy * dy + dz * dz;
+    bool full = !interior;
+    if (interior)
+    {   // (xi, yi, zi: the old position relative to the cell's centre, which the lane holds anyway)
+        const double lx = 1.25 * P.csz[0], ly = 1.25 * P.csz[1], lz = 1.25 * P.csz[2];
+        const bool far = fabs(xi) > lx || fabs(xi + dx) > lx || fabs(yi) > ly || fabs(yi + dy) > ly || fabs(zi) > lz || fabs(zi + dz) > lz;
+        full = __any(far) != 0;                                       // (over the lanes that hold an atom)
+    }
+    if (full)
+    {
+        int c;
+        c = image_of(x, P.L[0], P.invL[0]) - image_of(x0, P.L[0], P.invL[0]);
+        if (c < 0) cross |= 1; else if (c > 0) cross |= 2;
+        c = image_of(y, P.L[1], P.invL[1]) - image_of(y0, P.L[1], P.invL[1]);
+        if (c < 0) cross |= 4; else if (c > 0) cross |= 8;
+        c = image_of(z, P.L[2], P.invL[2]) - image_of(z0, P.L[2], P.invL[2]);
+        if (c < 0) cross |= 16; else if (c > 0) cross |= 32;
+    }
+    if (!(room2 > 0.0 && len2 < room2))
+    {
+        const double ex = x - N.R0.x[i], ey = y - N.R0.y[i], ez = z - N.R0.z[i];
+        if (ex * ex + ey * ey + ez * ez > P.lazySlack2) violated = 1;
+    }
+    st_f64(N.xd, i, x); st_f64(N.yd, i, y); st_f64(N.zd, i, z);
+}
+
+// once per wave, all lanes (those without an atom bring zeros): runBits / maxBits are Counts::cycMaxRun / maxStep2 as the wave read them when it started
+__device__ __forceinline__ void fold_drift_finish(const StepParams& P, const SpecTable& S, const NextStep& N, int t, double vx, double vy, double vz, double len2,
+                                                  int cross, int violated, unsigned long long runBits, unsigned long long maxBits,
+                                                  double* __restrict__ partials, int maxBlocks, size_t pb)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const unsigned long long mine = (unsigned long long)__double_as_longlong(len2);
+    if (__any(mine > maxBits || (P.boundSkip && mine > runBits)))
+    {
+        double mx = len2;
+#pragma unroll
+        for (int o = kWave >> 1; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, kWave));
+        if (lane == 0)
+        {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
+            if (bits > __hip_atomic_load(&N.cnt->maxStep2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&N.cnt->maxStep2, bits);
+            if (P.boundSkip && bits > __hip_atomic_load(&N.cnt->cycMaxRun, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&N.cnt->cycMaxRun, bits);
+        }
+    }
+    if (__any(violated) && lane == 0)
+    {
+        if (N.cnt->lazyViolated == 0) N.cnt->lazyViolated = P.cycleStep + 1;
+        N.cnt->lazyViolatedEver = 1;
+    }
+    if (__any(cross != 0))
+    {   // a handful of atoms in a million cross a wall on any one step.  Slots in the order Xn, Xp, Yn, Yp, Zn, Zp (PartialSlot)
+#pragma unroll
+        for (int d = 0; d < 6; d++) if (cross & (1 << d)) atomicAdd(&N.st->specCross[t * 6 + d], 1ULL);
+        const double m = S.mass[t];
+        next_wall_sum(m * (-vx), cross & 1, 1, 0, partials, maxBlocks, pb); next_wall_sum(m * vx, cross & 2, 2, 1, partials, maxBlocks, pb);
+        next_wall_sum(m * (-vy), cross & 4, 4, 2, partials, maxBlocks, pb); next_wall_sum(m * vy, cross & 8, 8, 3, partials, maxBlocks, pb);
+        next_wall_sum(m * (-vz), cross & 16, 16, 4, partials, maxBlocks, pb); next_wall_sum(m * vz, cross & 32, 32, 5, partials, maxBlocks, pb);
+    }
+}
 
 // ENG = false: the launch books no energies (steps whose energies nobody can see: all but the last step of an aztot_step call - the statistics are those of
 // the last step, finish_steps; the reference prints them every `stat` steps, cuStat.cu:308-330).  Forces are the same instructions either way: the energy
@@ -107,7 +193,10 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     // {list header, cell coordinates lx | cy << 10 | cz << 20, the cell's first atom, atoms | rcpNS << 12}: one scalar load - no look at cellStart (a second,
     // dependent round trip), no integer divisions (the builder leaves slices per atom and their reciprocal in the header)
     const int4 mx = ((const int4*)L.meta)[cell];
-    asm volatile("" ::: "memory");                                  // (what follows is issued behind the loads above, not in front of them)
+    // KICK_DRIFT: the longest steps so far, for the displacement bound and for fold_drift_finish (a value from before this launch's first atomic serves both)
+    unsigned long long runBits = 0ULL, maxBits = 0ULL;
+    if (P.fuseKick == KICK_DRIFT) { runBits = N.cnt->cycMaxRun; maxBits = N.cnt->maxStep2; }
+    asm volatile("" ::: "memory");                              // (what follows is issued behind the loads above, not in front of them)
     // after a slack violation (one GPU) the clean-up launch stages every cell with the wider stencil: stand down
     const bool violated = P.nranks == 1 && !P.optimistic && slack_violated(P, counts);
     int meta = mx.x;
@@ -158,10 +247,10 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) radi = A.rad[myl];
         // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  PRE groups are gathered whatever T is (stale
         // entries are atom indices too: the array starts out zeroed and only indices are ever written); all their loads travel together
+        const int gx0 = lx + P.cx0;
+        // does any neighbour cell lie across a periodic boundary (or the seam of a slab ring)?  wave-uniform
+        const bool images = gx0 - P.hw[0] < 0 || gx0 + P.hw[0] >= P.nc[0] || cy - P.hw[1] < 0 || cy + P.hw[1] >= ncy || cz - P.hw[2] < 0 || cz + P.hw[2] >= ncz;
         {
-            const int gx0 = lx + P.cx0;
-            // does any neighbour cell lie across a periodic boundary (or the seam of a slab ring)?  wave-uniform
-            const bool images = gx0 - P.hw[0] < 0 || gx0 + P.hw[0] >= P.nc[0] || cy - P.hw[1] < 0 || cy + P.hw[1] >= ncy || cz - P.hw[2] < 0 || cz + P.hw[2] >= ncz;
             struct Cand { double x, y, z, rad; int typ; };
             auto fetch = [&](uint32_t e) {
                 Cand c;
@@ -300,6 +389,9 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
                 n = s;
             }
         }
+        // KICK_DRIFT: what the lane hands to its wave (fold_drift_finish); lanes without an atom bring zeros
+        double dLen2 = 0.0, dvx = 0.0, dvy = 0.0, dvz = 0.0;
+        int dCross = 0, dViol = 0;
         if (validI && slice == 0)
         {
             double q = 0.0;
@@ -307,14 +399,27 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             const double fxi = -q * P.E[0] + acc.fx;   // clear_force integrators.cpp:17-39
             const double fyi = -q * P.E[1] + acc.fy;
             const double fzi = -q * P.E[2] + acc.fz;
-            if (P.fuseKick == KICK_BOTH)
+            if (P.fuseKick >= KICK_BOTH)
             {   // this step's second half-kick and the next step's first: the two roundings k_integrate_plain2 would make from the stored force (the kick
                 // it owes, then its own).  The velocity leaves instead of the force, which nobody reads before the next pair kernel: the next step is a
-                // drift (k_drift_plain2).  Never a step whose energies are booked, never with NextStep (Engine::launch_step_kernels)
+                // drift (k_drift_plain2, or KICK_DRIFT right here).  Never a step whose energies are booked, never with NextStep (Engine::launch_step_kernels)
                 const double rM = S.rMhdt[ti];
                 double vx = v0x + rM * fxi, vy = v0y + rM * fyi, vz = v0z + rM * fzi;
                 vx += rM * fxi; vy += rM * fyi; vz += rM * fzi;
-                A.vx[myi] = vx; A.vy[myi] = vy; A.vz[myi] = vz;
+                st_f64(A.vx, myi, vx); st_f64(A.vy, myi, vy); st_f64(A.vz, myi, vz);      // (32-bit byte offsets: no 64-bit address arithmetic per store)
+                if (P.fuseKick == KICK_DRIFT)
+                {   // the displacement bound of the step being opened, squared (k_drift_plain2's roomLeft): the slack less P.cycleStep steps of the longest
+                    // length so far - two f32 square roots, each rounded to the safe side by far more than their error; <= 0: every atom is checked
+                    double room2 = -1.0;
+                    if (P.boundSkip)
+                    {
+                        const float room = __builtin_amdgcn_sqrtf((float)P.lazySlack2) * 0.99999f -
+                                           (float)P.cycleStep * (__builtin_amdgcn_sqrtf((float)__longlong_as_double((long long)runBits)) * 1.00001f);
+                        if (room > 0.0f) room2 = (double)(room * room);
+                    }
+                    fold_drift_atom(P, S, N, myi, ti, xr, yr, zr, xi, yi, zi, vx, vy, vz, !images, room2, dLen2, dCross, dViol);
+                    dvx = vx; dvy = vy; dvz = vz;
+                }
             }
             else
             {
@@ -332,6 +437,8 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             }
             }
         }
+        if (P.fuseKick == KICK_DRIFT)
+            fold_drift_finish(P, S, N, ti, dvx, dvy, dvz, dLen2, dCross, dViol, runBits, maxBits, partials, maxBlocks, (size_t)blockBase + (size_t)blockIdx.x * W + wave);
         if (ENG) { eV = acc.eV; eC = acc.eC; }
         dropped = acc.dropped;
     }
@@ -362,6 +469,11 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         if (blockIdx.x == 0 && threadIdx.x == 0) { N.st->step += 1; N.st->pendingKick = 0; }
     }
     else if (N.pendingAfter >= 0 && blockIdx.x == 0 && threadIdx.x == 0) N.st->pendingKick = N.pendingAfter;
+    if (P.fuseKick == KICK_DRIFT && threadIdx.x == 0)
+    {   // what k_drift_plain2 does per launch and per workgroup: the step counter of the step being opened, its PS_EFIELD partials
+        if (blockIdx.x == 0) N.st->step += 1;
+        for (int b = blockIdx.x; b < N.driftBlocks; b += gridDim.x) partials[(size_t)PS_EFIELD * maxBlocks + b] = 0.0;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------

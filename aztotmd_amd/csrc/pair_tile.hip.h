@@ -78,6 +78,10 @@ __device__ __forceinline__ double ld_f64(const double* __restrict__ base, int j)
 {
     return *(const double*)((const char*)base + ((unsigned)j << 3));
 }
+__device__ __forceinline__ void st_f64(double* base, int j, double v)
+{
+    *(double*)((char*)base + ((unsigned)j << 3)) = v;
+}
 __device__ __forceinline__ int ld_i32(const int32_t* __restrict__ base, int j)
 {
     return *(const int32_t*)((const char*)base + ((unsigned)j << 2));
@@ -480,6 +484,10 @@ struct NextStep
     const double *photons = nullptr, *uvx = nullptr, *uvy = nullptr, *uvz = nullptr;
     int pendingAfter = -1;                                   // launches that do NOT fuse, in an engine that sometimes does: what k_pair_list leaves in DevStats::pendingKick
                                                              // (1: this step's second half-kick is owed to the next k_integrate1_bin / k_integrate2 ; -1: hands off)
+    // KICK_DRIFT (k_pair_list, large systems): the lean drift behind the two folded kicks (fold_drift_atom / fold_drift_finish, pair_list.hip.h) stores the next
+    // step's positions here; xn stays nullptr - nothing of the full epilogue above runs
+    double *xd = nullptr, *yd = nullptr, *zd = nullptr;
+    int driftBlocks = 0;                                     // workgroups of the k_drift_plain2 launch this replaces (it zeroes their PS_EFIELD partials)
 };
 
 // per-lane part; the wave-level bookkeeping follows in next_step_finish.  (Scalars on purpose: as two arrays of six the wall sums ended up in scratch
