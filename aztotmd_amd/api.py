@@ -114,6 +114,7 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_stress_setup", "aztot_stress_sample", "aztot_stress_get", "aztot_stress_per_atom",
            "aztot_adf_setup", "aztot_adf_sample", "aztot_adf_reset", "aztot_adf_shape", "aztot_adf_edges", "aztot_adf_counts", "aztot_adf_values",
            "aztot_adf_neighbours",
+           "aztot_sk_setup", "aztot_sk_sample", "aztot_sk_reset", "aztot_sk_shape", "aztot_sk_vectors", "aztot_sk_amplitudes", "aztot_sk_sums", "aztot_sk_values",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
@@ -251,6 +252,14 @@ def lib():
         L.aztot_adf_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int]
         L.aztot_adf_values.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.aztot_adf_neighbours.argtypes = [C.c_void_p, _ip, C.c_int]
+        L.aztot_sk_setup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
+        L.aztot_sk_sample.argtypes = [C.c_void_p]
+        L.aztot_sk_reset.argtypes = [C.c_void_p]
+        L.aztot_sk_shape.argtypes = [C.c_void_p, _ip, _ip, _ip, C.POINTER(C.c_int64)]
+        L.aztot_sk_vectors.argtypes = [C.c_void_p, _ip, _ip, C.c_int]
+        L.aztot_sk_amplitudes.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.aztot_sk_sums.argtypes = [C.c_void_p, C.POINTER(C.c_int64), _dp, C.c_int]
+        L.aztot_sk_values.argtypes = [C.c_void_p, _dp, _ip, _dp, _dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -724,6 +733,55 @@ class Engine:
         out = np.zeros(max(n, 1), dtype=np.int32)
         _check(lib().aztot_adf_neighbours(self.h, out.ctypes.data_as(_ip), n))
         return out[:n]
+
+    # ---- static structure factors (aztot_sk_*; the vector set, the order of the sums and the values are stated in include/aztot.h) ----
+    def sk_setup(self, kmax, dk, max_per_bin=0):
+        """k-vectors with |k| <= kmax in bins of width dk, at most max_per_bin per bin (0: all); (re)allocates and zeroes, returns the number of vectors"""
+        return _check(lib().aztot_sk_setup(self.h, float(kmax), float(dk), int(max_per_bin)))
+
+    def sk_sample(self):
+        """the per-species amplitudes of the current configuration; adds Re rho_a rho_b* to the sums"""
+        _check(lib().aztot_sk_sample(self.h))
+
+    def sk_reset(self):
+        _check(lib().aztot_sk_reset(self.h))
+
+    def sk_shape(self):
+        """(n_vectors, n_bins, n_pairs, samples)"""
+        nk, nb, npair, sm = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        _check(lib().aztot_sk_shape(self.h, C.byref(nk), C.byref(nb), C.byref(npair), C.byref(sm)))
+        return nk.value, nb.value, npair.value, sm.value
+
+    def sk_vectors(self):
+        """(lmn[n_vectors, 3], bin[n_vectors]) - int32, in ascending lexicographic order of (l, m, n)"""
+        nk = self.sk_shape()[0]
+        lmn, b = np.zeros(3 * nk, dtype=np.int32), np.zeros(nk, dtype=np.int32)
+        _check(lib().aztot_sk_vectors(self.h, lmn.ctypes.data_as(_ip), b.ctypes.data_as(_ip), nk))
+        return lmn.reshape(nk, 3), b
+
+    def sk_amplitudes(self):
+        """rho[n_vectors, n_species, 2] of the last sample: (re, im) of sum_j exp(i k r_j) over the atoms of each species"""
+        nk = self.sk_shape()[0]
+        n = _check(lib().aztot_sk_amplitudes(self.h, None, 0))
+        out = np.zeros(n)
+        _check(lib().aztot_sk_amplitudes(self.h, out.ctypes.data_as(_dp), n))
+        return out.reshape(nk, -1, 2)
+
+    def sk_sums(self):
+        """(samples, acc[n_vectors, n_pairs]): Re rho_a rho_b* summed over the samples, pairs a <= b in the RDF's pair order"""
+        nk, _, npair, _ = self.sk_shape()
+        out = np.zeros(nk * npair)
+        samples = C.c_int64()
+        _check(lib().aztot_sk_sums(self.h, C.byref(samples), out.ctypes.data_as(_dp), out.size))
+        return samples.value, out.reshape(nk, npair)
+
+    def sk_values(self):
+        """(k[n_bins], n_in_bin[n_bins], S[n_bins], S_ab[n_bins, n_pairs]): bin centres, kept vectors per bin, the total and the Ashcroft-Langreth partials
+        (means over the vectors of a bin; 0 where n_in_bin is 0)"""
+        _, nb, npair, _ = self.sk_shape()
+        k, cnt, tot, part = np.zeros(nb), np.zeros(nb, dtype=np.int32), np.zeros(nb), np.zeros(nb * npair)
+        _check(lib().aztot_sk_values(self.h, k.ctypes.data_as(_dp), cnt.ctypes.data_as(_ip), tot.ctypes.data_as(_dp), part.ctypes.data_as(_dp), part.size))
+        return k, cnt, tot, part.reshape(nb, npair)
 
     def close(self):
         if getattr(self, "h", None):

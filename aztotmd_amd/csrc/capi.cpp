@@ -124,6 +124,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  vaf (steps between two rows of vaf.dat: the 'vaf' line of control.txt; 0 without one)
 //  stress (steps between two rows of stress.dat: the 'stress' line of control.txt, our extension; 0 without one)
 //  adf (n_bins, every, n, then per line: central, ligand_a, ligand_b species ids, R_a, R_b: the 'adf' block of control.txt, our extension; 0, 0, 0 without one)
+//  sk (kmax, dk, every, max_per_bin: the 'strfac' line of control.txt, our extension; kmax = 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
 {
@@ -203,6 +204,7 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             v = {(double)m.adf_bins, (double)m.adf_every, (double)m.adf_cols.size()};
             for (const auto& c : m.adf_cols) { v.push_back(c.central); v.push_back(c.ligand_a); v.push_back(c.ligand_b); v.push_back(c.radius_a); v.push_back(c.radius_b); }
         }
+        else if (k == "sk") v = {m.sk_kmax, m.sk_dk, (double)m.sk_every, (double)m.sk_max_per_bin};
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -743,6 +745,123 @@ int aztot_adf_neighbours(aztot_md* md, int32_t* n, int cap)
         std::vector<int32_t> v;
         md->eng->samplers().adf_neighbours(v);              // (refuses before a sample)
         if (n) std::memcpy(n, v.data(), sizeof(int32_t) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_sk_setup(aztot_md* md, double kmax, double dk, int max_per_bin)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int nk = 0;
+    const int rc = guarded([&] { nk = md->eng->samplers().sk_setup(kmax, dk, max_per_bin); });
+    return rc < 0 ? rc : nk;
+}
+
+int aztot_sk_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().sk_sample(); });
+}
+
+int aztot_sk_reset(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().sk_reset(); });
+}
+
+int aztot_sk_shape(aztot_md* md, int* n_vectors, int* n_bins, int* n_pairs, int64_t* samples)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] {
+        int nk = 0, nb = 0, np = 0;
+        long long sm = 0;
+        md->eng->samplers().sk_shape(nk, nb, np, sm);
+        if (n_vectors) *n_vectors = nk;
+        if (n_bins) *n_bins = nb;
+        if (n_pairs) *n_pairs = np;
+        if (samples) *samples = sm;
+    });
+}
+
+int aztot_sk_vectors(aztot_md* md, int32_t* lmn, int32_t* bin, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nb = 0, np = 0;
+        long long sm = 0;
+        md->eng->samplers().sk_shape(need, nb, np, sm);
+        if ((lmn || bin) && cap < need) throw ArgError("sk: cap < n_vectors");
+        if (!lmn && !bin) return;
+        std::vector<int32_t> l, b;
+        md->eng->samplers().sk_vectors(l, b);
+        if (lmn) std::memcpy(lmn, l.data(), sizeof(int32_t) * l.size());
+        if (bin) std::memcpy(bin, b.data(), sizeof(int32_t) * b.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_sk_amplitudes(aztot_md* md, double* rho, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nk = 0, nb = 0, np = 0;
+        long long sm = 0;
+        md->eng->samplers().sk_shape(nk, nb, np, sm);
+        int ns = 0;
+        while (ns * (ns + 1) / 2 < np) ns++;                // (n_pairs = n_species (n_species + 1) / 2)
+        const long long want = 2LL * nk * ns;
+        if (want > 0x7fffffffLL) throw ArgError("sk: 2 x vectors x species does not fit the int this call returns");
+        need = (int)want;
+        if (rho && cap < need) throw ArgError("sk: cap < n_vectors * n_species * 2");
+        std::vector<double> v;
+        md->eng->samplers().sk_amplitudes(v);               // (refuses before a sample)
+        if (rho) std::memcpy(rho, v.data(), sizeof(double) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_sk_sums(aztot_md* md, int64_t* samples, double* acc, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nk = 0, nb = 0, np = 0;
+        long long sm = 0;
+        md->eng->samplers().sk_shape(nk, nb, np, sm);
+        const long long want = (long long)nk * np;
+        if (want > 0x7fffffffLL) throw ArgError("sk: vectors x pairs does not fit the int this call returns");
+        need = (int)want;
+        if (acc && cap < need) throw ArgError("sk: cap < n_vectors * n_pairs");
+        if (samples) *samples = sm;
+        if (!acc) return;
+        std::vector<double> v;
+        md->eng->samplers().sk_sums(v);
+        std::memcpy(acc, v.data(), sizeof(double) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_sk_values(aztot_md* md, double* k, int32_t* n_in_bin, double* s_total, double* s_pair, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int nk = 0, nb = 0, np = 0;
+        long long sm = 0;
+        md->eng->samplers().sk_shape(nk, nb, np, sm);
+        need = nb * np;
+        const bool any = k || n_in_bin || s_total || s_pair;
+        if (any && cap < need) throw ArgError("sk: cap < n_bins * n_pairs");
+        if (!any) return;
+        std::vector<double> kv, tv, pv;
+        std::vector<int32_t> nv;
+        md->eng->samplers().sk_values(kv, nv, tv, pv);
+        if (k) std::memcpy(k, kv.data(), sizeof(double) * kv.size());
+        if (n_in_bin) std::memcpy(n_in_bin, nv.data(), sizeof(int32_t) * nv.size());
+        if (s_total) std::memcpy(s_total, tv.data(), sizeof(double) * tv.size());
+        if (s_pair) std::memcpy(s_pair, pv.data(), sizeof(double) * pv.size());
     });
     return rc < 0 ? rc : need;
 }

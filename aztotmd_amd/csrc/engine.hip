@@ -20,6 +20,7 @@
 #include "rdf.hip.h"
 #include "cn.hip.h"
 #include "adf.hip.h"
+#include "sk.hip.h"
 #include "tcf.hip.h"
 #include "slab.hip.h"
 

@@ -21,6 +21,11 @@
 //                   probability density per degree of each column.  Sampled after every completed step c > nequil with c % every == 0; with every == 0, or when
 //                   the run ended before the first sample, once on the final configuration.  Without the block: no sampler, no file
 //   adf_n.dat       the same layout with the raw counts
+//   sk.dat          OUR EXTENSION, with 'strfac <kmax> <dk> <every> <max_per_bin>': the static structure factors of aztot_sk_*, header "k\tn\tS" + "\t<nameA>-<nameB>"
+//                   per species pair in pair-index order, a row per bin that holds at least one k-vector: the bin centre in 1/A, the number of k-vectors averaged,
+//                   the total S(k) and the Ashcroft-Langreth partials.  The schedule of adf.dat: sampled after every completed step c > nequil with
+//                   c % every == 0; with every == 0, or when the run ended before the first sample, once on the final configuration.  A kmax the box cannot
+//                   serve (past 48 harmonics on an axis, or no vector at all) gives a WARNING and no file.  Without the line: no sampler, no file
 // Both displ.dat and vaf.dat are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
 // MSD / VAF schedule: ONE sampler (aztot_tcf_*) with a single origin, n_origins = 1 and origin_every = the number of samples the run takes.  Sample 0 is the
 // initial state (x0s, sys_init.cpp:545); a step c < nequil that writes a stat row samples and writes a displ.dat row; at c == nequil (> 0) the sampler is
@@ -32,7 +37,7 @@
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
 // stat row (c % stat == 0, and the last step), an RDF sample (which only reads the state: its place against the stat row of the same step does not matter),
-// the end of the equilibration, a vaf.dat row, a stress.dat row or a sample of the bond-angle distributions.
+// the end of the equilibration, a vaf.dat row, a stress.dat row, a sample of the bond-angle distributions or one of the structure factors.
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -131,6 +136,30 @@ static void write_adf(aztot_md* md, const std::vector<aztot_adf_column>& cols, c
         }
         std::fclose(f);
     }
+}
+
+// sk.dat: header "k\tn\tS\t<nameA>-<nameB>...", rows "%f" k, "\t%d" vectors in the bin, "\t%f" S and "\t%f" per pair; bins without a vector have no row
+static void write_sk(aztot_md* md, const std::vector<std::string>& names, const std::string& path)
+{
+    int nb = 0, np = 0;
+    if (aztot_sk_shape(md, nullptr, &nb, &np, nullptr) != AZTOT_OK) die("sk shape");
+    std::vector<double> k(std::max(nb, 1)), tot(std::max(nb, 1)), part((size_t)std::max(nb * np, 1));
+    std::vector<int32_t> cnt(std::max(nb, 1));
+    if (aztot_sk_values(md, k.data(), cnt.data(), tot.data(), part.data(), nb * np) < 0) die("sk values");
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) { std::perror(path.c_str()); std::exit(1); }
+    std::fprintf(f, "k\tn\tS");
+    for (size_t a = 0; a < names.size(); a++)
+        for (size_t b = a; b < names.size(); b++) std::fprintf(f, "\t%s-%s", names[a].c_str(), names[b].c_str());
+    std::fprintf(f, "\n");
+    for (int b = 0; b < nb; b++)
+    {
+        if (cnt[b] == 0) continue;
+        std::fprintf(f, "%f\t%d\t%f", k[b], (int)cnt[b], tot[b]);
+        for (int p = 0; p < np; p++) std::fprintf(f, "\t%f", part[(size_t)b * np + p]);
+        std::fprintf(f, "\n");
+    }
+    std::fclose(f);
 }
 
 // "<time>\t<step>" + "\t%f" per species: the row layout of out_msd's MSD columns and of vaf_info
@@ -283,6 +312,18 @@ int main(int argc, char** argv)
     }
     auto adf_due = [&](int c) { return adfOn && adfEvery > 0 && c > nEq && c % adfEvery == 0; };
     int adfTaken = 0;
+    // static structure factors ('strfac', our extension): the schedule of the bond-angle distributions, the file at the end
+    double skq[4] = {0, 0, 0, 0};
+    if (aztot_model_query(model, "sk", skq, 4) < 4) die("sk");
+    const int skEvery = (int)skq[2];
+    bool skOn = skq[0] > 0.0;
+    if (skOn && aztot_sk_setup(md, skq[0], skq[1], (int)skq[3]) < 0)
+    {
+        std::fprintf(stderr, "WARNING: strfac directive not usable (%s): no sk.dat\n", aztot_last_error());
+        skOn = false;
+    }
+    auto sk_due = [&](int c) { return skOn && skEvery > 0 && c > nEq && c % skEvery == 0; };
+    int skTaken = 0;
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
@@ -299,8 +340,14 @@ int main(int argc, char** argv)
         }
         if (stressOn) n = std::min(n, (done / stressEvery + 1) * stressEvery - done);
         if (adfOn && adfEvery > 0) n = std::min(n, (std::max(done, nEq) / adfEvery + 1) * adfEvery - done);
+        if (skOn && skEvery > 0) n = std::min(n, (std::max(done, nEq) / skEvery + 1) * skEvery - done);
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
+        if (sk_due(done))
+        {
+            if (aztot_sk_sample(md) != AZTOT_OK) die("sk sample");
+            skTaken++;
+        }
         if (adf_due(done))
         {
             if (aztot_adf_sample(md) != AZTOT_OK) die("adf sample");
@@ -366,6 +413,11 @@ int main(int argc, char** argv)
     {
         if (adfTaken == 0 && aztot_adf_sample(md) != AZTOT_OK) die("adf sample");
         write_adf(md, adfCols, names, out + "/adf.dat", out + "/adf_n.dat");
+    }
+    if (skOn)
+    {
+        if (skTaken == 0 && aztot_sk_sample(md) != AZTOT_OK) die("sk sample");
+        write_sk(md, names, out + "/sk.dat");
     }
     // coordination numbers: one snapshot of the final configuration (main.cu:446-448)
     auto query_all = [&](const char* key) {

@@ -122,6 +122,10 @@ struct Model
     // equilibration (0: one sample of the final configuration); adf_bins == 0: off
     int adf_bins = 0, adf_every = 0;
     std::vector<aztot_adf_column> adf_cols;
+    // 'strfac <kmax> <dk> <every> <max_per_bin>' (ours): static structure factors (aztot_sk_setup), a sample every `every` steps after the equilibration
+    // (0: one sample of the final configuration); sk_kmax == 0: off
+    double sk_kmax = 0, sk_dk = 0;
+    int sk_every = 0, sk_max_per_bin = 0;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

@@ -1,5 +1,6 @@
 // The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h), the
-// pressure tensor (stress.hip.h) and bond-angle distributions (adf.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* / aztot_adf_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
+// pressure tensor (stress.hip.h), bond-angle distributions (adf.hip.h) and static structure factors (sk.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* /
+// aztot_stress_* / aztot_adf_* / aztot_sk_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
 // is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
 //
 // The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
@@ -81,6 +82,16 @@ public:
     void adf_values(std::vector<double>& theta, std::vector<double>& p);   // bin centres in degrees, density per degree [bin][column]
     void adf_neighbours(std::vector<int32_t>& n);                      // [atom id] at the last sample (a refused one included), -1: not a central atom
 
+    // static structure factors (include/aztot.h states the vector set, the order of the sums and the values): fp64 sums over the samples
+    int sk_setup(double kmax, double dk, int maxPerBin);               // (re)allocates and zeroes; returns the number of k-vectors
+    void sk_sample();
+    void sk_reset();
+    void sk_shape(int& nVectors, int& nBins, int& nPairs, long long& samples);
+    void sk_vectors(std::vector<int32_t>& lmn, std::vector<int32_t>& bin);     // [vector][l, m, n] and the bin of each
+    void sk_amplitudes(std::vector<double>& rho);                      // [vector][species][re, im] of the last sample
+    void sk_sums(std::vector<double>& acc);                            // [vector][pair]
+    void sk_values(std::vector<double>& k, std::vector<int32_t>& nInBin, std::vector<double>& sTotal, std::vector<double>& sPair);   // [bin], [bin], [bin], [bin][pair]
+
 private:
     // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
     // each coordination-number set-up has one (different cell edges)
@@ -159,6 +170,23 @@ private:
         double* dEdges = nullptr;
     };
 
+    // the kept k-vectors in lexicographic order with their bins, positions and species by atom id, row sums of a batch of vectors, amplitudes of the last
+    // sample, sums over the samples
+    struct SkState
+    {
+        double kmax = 0, dk = 0;
+        int maxPerBin = 0, nBins = 0;   // nBins == 0: not set up
+        int nK = 0, nSpec = 0, nPairs = 0;
+        long long samples = 0;
+        bool sampled = false;           // the amplitudes of a sample are there
+        std::vector<int32_t> lmn, bin, nInBin;
+        int h[3] = {1, 1, 1};           // entries of the per-axis harmonic tables: the largest |harmonic| of the set + 1
+        int tile = 0, nRows = 0, nIdTiles = 0, batch = 0;      // atoms per LDS tile, rows and 64-id tiles of the summation order, vectors per launch
+        DeviceArena mem;
+        double *x = nullptr, *y = nullptr, *z = nullptr, *partial = nullptr, *rho = nullptr, *acc = nullptr;
+        int32_t *type = nullptr, *dLmn = nullptr;
+    };
+
     // the protocol every sampler follows, once (samplers.hip.h)
     void need_one_gpu(const char* what) const;
     static void need_setup(bool isSetUp, const char* name, const char* tail = "");
@@ -174,6 +202,7 @@ private:
     TcfState& tcf_state();
     StressState& stress_state(bool needSample);
     AdfState& adf_state();
+    SkState& sk_state();
 
     Host& host_;
     const Model& model_;            // the engine's (outlives the samplers)
@@ -186,6 +215,7 @@ private:
     TcfState tcf_;
     StressState stress_;
     AdfState adf_;
+    SkState sk_;
 };
 
 }  // namespace aztot

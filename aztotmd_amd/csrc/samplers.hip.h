@@ -769,4 +769,221 @@ void Samplers::adf_neighbours(std::vector<int32_t>& out)
     for (int s = 0; s < N; s++) out[ids[s]] = cnt[s];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Static structure factors (sk.hip.h; the vector set, the order of the sums and the values are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+Samplers::SkState& Samplers::sk_state() { need_setup(sk_.nBins != 0, "sk"); return sk_; }
+
+int Samplers::sk_setup(double kmax, double dk, int maxPerBin)
+{
+    need_one_gpu("static structure factors");
+    if (!(kmax > 0.0) || !(dk > 0.0) || !std::isfinite(kmax) || !std::isfinite(dk)) throw ArgError("sk: kmax and dk must be positive");
+    if (maxPerBin < 0) throw ArgError("sk: max_per_bin must not be negative (0: keep every vector)");
+    const double idk = 1.0 / dk, nb = kmax * idk;
+    if (!(nb >= 1.0) || !(nb < (double)AZTOT_SK_MAX_BINS + 1.0)) throw ArgError("sk: n_bins = kmax / dk must be in [1, AZTOT_SK_MAX_BINS]");
+    SkState T;
+    T.kmax = kmax; T.dk = dk; T.maxPerBin = maxPerBin; T.nBins = (int)nb;
+    T.nSpec = model_.nSpec(); T.nPairs = T.nSpec * (T.nSpec + 1) / 2;
+    // g = 2 pi / L with the correctly rounded double of 2 pi; sq[a][h] = (h g_a) * (h g_a)
+    const double twoPi = 6.283185307179586, kmax2 = kmax * kmax;
+    std::vector<double> sq[3];
+    int hmax[3];
+    for (int a = 0; a < 3; a++)
+    {
+        const double g = twoPi / box_.L[a];
+        for (int h = 0; h <= AZTOT_SK_MAX_HARMONIC + 1; h++) { const double k = (double)h * g; sq[a].push_back(k * k); }
+        if (sq[a][AZTOT_SK_MAX_HARMONIC + 1] <= kmax2)
+            throw ArgError(std::string("sk: kmax needs harmonic ") + std::to_string(AZTOT_SK_MAX_HARMONIC + 1) + " on axis " + "xyz"[a] + ", more than AZTOT_SK_MAX_HARMONIC = " +
+                           std::to_string(AZTOT_SK_MAX_HARMONIC) + ": this box admits kmax < " + std::to_string((double)(AZTOT_SK_MAX_HARMONIC + 1) * twoPi /
+                           std::max(box_.L[0], std::max(box_.L[1], box_.L[2]))) + " (49 * 2 pi / its longest edge); nothing is truncated");
+        hmax[a] = 0;
+        while (hmax[a] < AZTOT_SK_MAX_HARMONIC && sq[a][hmax[a] + 1] <= kmax2) hmax[a]++;
+    }
+    // the half space in ascending lexicographic order of (l, m, n): l > 0, or l == 0 and m > 0, or l == m == 0 and n > 0
+    std::vector<int32_t> lmn, bin;
+    std::vector<int64_t> inBin((size_t)T.nBins, 0);
+    for (int l = 0; l <= hmax[0]; l++)
+        for (int m = (l > 0 ? -hmax[1] : 0); m <= hmax[1]; m++)
+            for (int n = ((l > 0 || m > 0) ? -hmax[2] : 1); n <= hmax[2]; n++)
+            {
+                const double kk = (sq[0][l] + sq[1][std::abs(m)]) + sq[2][std::abs(n)];
+                if (!(kk <= kmax2)) continue;
+                const int b = (int)(std::sqrt(kk) * idk);
+                if (b >= T.nBins) continue;
+                lmn.push_back(l); lmn.push_back(m); lmn.push_back(n);
+                bin.push_back(b);
+                inBin[b]++;
+            }
+    // thinning: a bin with c > M vectors keeps j of 0 ... c - 1 iff (j + 1) M / c > j M / c (exactly M of them)
+    std::vector<int64_t> seen((size_t)T.nBins, 0);
+    T.nInBin.assign((size_t)T.nBins, 0);
+    for (size_t v = 0; v < bin.size(); v++)
+    {
+        const int b = bin[v];
+        const int64_t c = inBin[b], j = seen[b]++, M = maxPerBin;
+        if (M > 0 && c > M && !((j + 1) * M / c > j * M / c)) continue;
+        T.lmn.push_back(lmn[3 * v]); T.lmn.push_back(lmn[3 * v + 1]); T.lmn.push_back(lmn[3 * v + 2]);
+        T.bin.push_back(b);
+        T.nInBin[b]++;
+        for (int a = 0; a < 3; a++) T.h[a] = std::max(T.h[a], std::abs(lmn[3 * v + a]) + 1);
+    }
+    T.nK = (int)T.bin.size();
+    if (T.nK == 0) throw ArgError("sk: no k-vector (kmax is below the smallest 2 pi / L of the box, or its bin is past the last one)");
+    const int N = model_.nAt, nH = T.h[0] + T.h[1] + T.h[2];
+    T.tile = kSkIdTile;
+    while (T.tile > 16 && (size_t)T.tile * nH * sizeof(cplx) > (size_t)kSkLdsBudget) T.tile >>= 1;
+    T.nIdTiles = std::max(1, div_up(N, kSkIdTile));
+    T.nRows = std::min(kSkRows, T.nIdTiles);
+    // vectors per launch: `partial` stays inside its budget however large the set is
+    const size_t perVector = (size_t)T.nRows * T.nSpec * 2 * sizeof(double);
+    const size_t cap = std::max<size_t>(1, kSkPartialBudget / perVector / kSkChunk) * kSkChunk;
+    T.batch = (int)std::min<size_t>(cap, (size_t)T.nK);
+    set_up(sk_, T, [&] {
+        const size_t nPad = (size_t)T.nIdTiles * kSkIdTile;
+        T.x = T.mem.alloc<double>(nPad, true, stream_); T.y = T.mem.alloc<double>(nPad, true, stream_); T.z = T.mem.alloc<double>(nPad, true, stream_);
+        T.type = T.mem.alloc<int32_t>(nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.type, 0xff, sizeof(int32_t) * nPad, stream_));
+        T.dLmn = T.mem.alloc<int32_t>(T.lmn.size(), false, stream_);
+        HIP_CHECK(hipMemcpy(T.dLmn, T.lmn.data(), T.lmn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        T.partial = T.mem.alloc<double>((size_t)T.nRows * T.batch * T.nSpec * 2, false, stream_);
+        T.rho = T.mem.alloc<double>((size_t)T.nK * T.nSpec * 2, true, stream_);
+        T.acc = T.mem.alloc<double>((size_t)T.nK * T.nPairs, true, stream_);
+    });
+    return sk_.nK;
+}
+
+void Samplers::sk_reset()
+{
+    SkState& S = sk_state();
+    HIP_CHECK(hipMemsetAsync(S.acc, 0, (size_t)S.nK * S.nPairs * sizeof(double), stream_));
+    S.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Samplers::sk_sample()
+{
+    SkState& S = sk_state();
+    sample("sk kernels", [&](const AtomArrays& A) {
+        const int N = model_.nAt;
+        S.sampled = false;
+        TcfBox B;
+        SkGeom G;
+        for (int k = 0; k < 3; k++) { B.L[k] = box_.L[k]; B.invL[k] = box_.invL[k]; B.half[k] = box_.half[k]; G.L[k] = box_.L[k]; G.h[k] = S.h[k]; }
+        const int nH = S.h[0] + S.h[1] + S.h[2];
+        // AZTOT_SK_TILE = 16 / 32 / 64 and AZTOT_SK_BATCH = vectors per launch: measurement switches (tools/sk_cost.py, tests) that replace the two rules
+        // (within the room in LDS and in `partial`); the results do not depend on them
+        int tile = S.tile, batch = S.batch;
+        if (const char* e = std::getenv("AZTOT_SK_TILE"))
+        {
+            const int t = std::atoi(e);
+            if ((t == 16 || t == 32 || t == 64) && (size_t)t * nH * sizeof(cplx) <= (size_t)kSkLdsBudget) tile = t;
+        }
+        if (const char* e = std::getenv("AZTOT_SK_BATCH"))
+        {
+            const int b = std::atoi(e);
+            if (b >= 1 && b <= S.batch) batch = b;
+        }
+        if (N > 0)
+            timed("k_sk_gather", [&] { hipLaunchKernelGGL(k_sk_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, B, A, N, S.x, S.y, S.z, S.type); });
+        const size_t rowStride = (size_t)S.batch * S.nSpec * 2, lds = (size_t)tile * nH * sizeof(cplx);
+        for (int v0 = 0; v0 < S.nK; v0 += batch)
+        {
+            const int nvb = std::min(batch, S.nK - v0);
+            timed("k_sk_amplitudes", [&] {
+                hipLaunchKernelGGL(k_sk_amplitudes, dim3(div_up(nvb, kSkChunk), S.nRows), dim3(kBlock), lds, stream_, G, S.nSpec, tile, S.nIdTiles, nvb, rowStride,
+                                   S.dLmn + 3 * (size_t)v0, S.x, S.y, S.z, S.type, S.partial);
+            });
+            const size_t nEnt = (size_t)nvb * S.nSpec * 2;
+            timed("k_sk_fold", [&] {
+                hipLaunchKernelGGL(k_sk_fold, dim3((unsigned)((nEnt + kWave - 1) / kWave)), dim3(kWave * kSkFoldWaves), 0, stream_, S.nRows, nEnt, rowStride, S.partial,
+                                   S.rho + (size_t)v0 * S.nSpec * 2);
+            });
+        }
+        const size_t nAcc = (size_t)S.nK * S.nPairs;
+        timed("k_sk_accumulate", [&] {
+            hipLaunchKernelGGL(k_sk_accumulate, dim3((unsigned)((nAcc + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream_, S.nK, S.nSpec, S.nPairs, S.rho, S.acc);
+        });
+    });
+    S.samples++;
+    S.sampled = true;
+}
+
+void Samplers::sk_shape(int& nVectors, int& nBins, int& nPairs, long long& samples)
+{
+    const SkState& S = sk_state();
+    nVectors = S.nK; nBins = S.nBins; nPairs = S.nPairs; samples = S.samples;
+}
+
+void Samplers::sk_vectors(std::vector<int32_t>& lmn, std::vector<int32_t>& bin)
+{
+    const SkState& S = sk_state();
+    lmn = S.lmn; bin = S.bin;
+}
+
+void Samplers::sk_amplitudes(std::vector<double>& rho)
+{
+    const SkState& S = sk_state();
+    if (!S.sampled) throw ArgError("sk: aztot_sk_sample has not been called since the set-up");
+    rho.resize((size_t)S.nK * S.nSpec * 2);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(rho.data(), S.rho, rho.size() * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+void Samplers::sk_sums(std::vector<double>& acc)
+{
+    const SkState& S = sk_state();
+    acc.resize((size_t)S.nK * S.nPairs);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(acc.data(), S.acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+// Ashcroft-Langreth partials per vector, S_ab = acc / (samples * sqrt(n_a n_b)), and the total S = sum_{a <= b} w_ab sqrt(n_a n_b) S_ab / N (pair order, from
+// 0.0), each averaged over the kept vectors of its bin (summed in set order, from 0.0).  Every operation is rounded on its own: tests/sk_model.py values()
+void Samplers::sk_values(std::vector<double>& k, std::vector<int32_t>& nInBin, std::vector<double>& sTotal, std::vector<double>& sPair)
+{
+#pragma clang fp contract(off)
+    std::vector<double> acc;
+    sk_sums(acc);
+    const SkState& S = sk_;
+    const int nP = S.nPairs, nS = S.nSpec;
+    k.resize(S.nBins);
+    for (int b = 0; b < S.nBins; b++) k[b] = (b + 0.5) * S.dk;
+    nInBin = S.nInBin;
+    sTotal.assign((size_t)S.nBins, 0.0);
+    sPair.assign((size_t)S.nBins * nP, 0.0);
+    std::vector<double> root(nP), weight(nP);
+    {
+        int p = 0;
+        for (int a = 0; a < nS; a++)
+            for (int b = a; b < nS; b++, p++)
+            {
+                root[p] = std::sqrt((double)model_.species[a].number * (double)model_.species[b].number);
+                weight[p] = (a == b ? 1.0 : 2.0) * root[p];
+            }
+    }
+    const double nAt = (double)model_.nAt;
+    for (int v = 0; v < S.nK; v++)
+    {
+        const int b = S.bin[v];
+        double tot = 0.0;
+        for (int p = 0; p < nP; p++)
+        {
+            const double d = (double)S.samples * root[p];
+            const double sab = d != 0.0 ? acc[(size_t)v * nP + p] / d : 0.0;
+            sPair[(size_t)b * nP + p] = sPair[(size_t)b * nP + p] + sab;
+            const double term = weight[p] * sab;
+            tot = tot + term;
+        }
+        const double sv = nAt > 0.0 ? tot / nAt : 0.0;
+        sTotal[b] = sTotal[b] + sv;
+    }
+    for (int b = 0; b < S.nBins; b++)
+    {
+        if (!S.nInBin[b]) continue;
+        const double c = (double)S.nInBin[b];
+        sTotal[b] = sTotal[b] / c;
+        for (int p = 0; p < nP; p++) sPair[(size_t)b * nP + p] = sPair[(size_t)b * nP + p] / c;
+    }
+}
+
 }  // namespace aztot

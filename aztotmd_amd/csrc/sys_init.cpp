@@ -409,6 +409,25 @@ void read_sim(const std::string& dir, Model& m)
         }
         m.adf_bins = (int)nb; m.adf_every = every;
     }
+    // static structure factors: 'strfac <kmax> <dk> <every> <max_per_bin>' (our extension, the arguments of aztot_sk_setup and the period of the samples); no
+    // line: off.  A whole word: the scanner tries the template at the start of every whitespace-delimited token and the template asks for white space behind
+    // the word, so it fires neither inside nor at the head of another token.  The first value is read as a word and converted whole: something that only
+    // starts like a number is malformed, not half-read
+    m.sk_kmax = m.sk_dk = 0.0; m.sk_every = m.sk_max_per_bin = 0;
+    char skWord[64] = {0};
+    if (seek_value(f, " strfac%*[ \t\r\n]%63s", skWord))
+    {
+        const char* form = "ERROR[418] malformed 'strfac' directive in control.txt: strfac <kmax> <dk> <every> <max_per_bin>";
+        char* end = nullptr;
+        const double kmax = std::strtod(skWord, &end);
+        double dk = 0.0;
+        int every = 0, cap = 0;
+        if (end == skWord || *end != '\0' || std::fscanf(f, " %lf %d %d", &dk, &every, &cap) != 3) fail(form);
+        if (!(kmax > 0.0) || !(dk > 0.0) || !std::isfinite(kmax) || !std::isfinite(dk)) fail("ERROR[418] kmax and dk of the 'strfac' directive must be positive");
+        if (every < 0) fail("ERROR[418] negative period in 'strfac' directive of control.txt");
+        if (cap < 0) fail("ERROR[418] negative max_per_bin in 'strfac' directive of control.txt");
+        m.sk_kmax = kmax; m.sk_dk = dk; m.sk_every = every; m.sk_max_per_bin = cap;
+    }
     // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
     m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
     if (seek_value(f, " rdf %lf ", &m.rdf_rmax))

@@ -233,6 +233,9 @@ def write_input_files(case, directory, stat=200):
             nb, every, cols = case["adf"]
             f.write("adf\t%d\t%d\t%d\n" % (int(nb), int(every), len(cols)))
             f.writelines("%s %s %s %r %r\n" % (c, a, b, float(ra), float(rb)) for c, a, b, ra, rb in cols)
+        if case.get("strfac"):          # static structure factors (our directive, aztot_sk_*): (kmax, dk, every, max_per_bin)
+            kmax, dk, every, cap = case["strfac"]
+            f.write("strfac\t%r\t%r\t%d\t%d\n" % (float(kmax), float(dk), int(every), int(cap)))
         f.write("stat\t%d\n" % stat)
     if case.get("bonds") is not None and len(case["bonds"]):
         with open(os.path.join(directory, "bonds.txt"), "w") as f:       # read_bondlist, bonds.cpp:25-110

@@ -489,6 +489,72 @@ int aztot_adf_values(aztot_md *md, double *theta, double *p, int cap);
 /* neighbours of each atom (by id) at the last sample, -1: not a central atom; returns n_atoms */
 int aztot_adf_neighbours(aztot_md *md, int32_t *n, int cap);
 
+/* ---- static structure factors: per-species amplitudes over a set of k-vectors chosen by |k|, partial S_ab(k) summed over the samples ------------------
+   The reference computes no structure factor: like the pressure tensor and the bond-angle distributions, this sampler is ours.
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.
+
+   VECTORS.  k = (l g_x, m g_y, n g_z) with integers l, m, n and g_a = 2 pi / L_a, 2 pi being the correctly rounded double of 2 pi
+   (6.283185307179586), not the model's truncated 3.14159265359: the phase has to be periodic in the box.  Only the half space, each pair +-k once:
+   l > 0, or l == 0 and m > 0, or l == m == 0 and n > 0.  For every vector kk = ((l g_x)*(l g_x) + (m g_y)*(m g_y)) + (n g_z)*(n g_z) in double, each
+   operation rounded on its own ((l g_x) is the rounded product of the integer and g_x).  A vector belongs to the set iff kk <= kmax*kmax and
+   bin = (int)(sqrt(kk) * (1.0 / dk)) < n_bins, n_bins = (int)(kmax * (1.0 / dk)): the RDF's rule transposed.  Every step is a correctly rounded
+   operation: numpy reproduces the set exactly (tests/sk_model.py).
+
+   ORDER AND THINNING.  The vectors are in ascending lexicographic order of (l, m, n).  With max_per_bin = M > 0, a bin that holds c > M vectors,
+   numbered j = 0 ... c - 1 in that order, keeps j iff (j + 1) * M / c > j * M / c in 64-bit integer division: exactly M of them.  Bins with c <= M, and
+   every bin when M == 0, keep everything.  The kept vectors, still in lexicographic order, are the set; n_k is its size.
+
+   The set-up rejects with AZTOT_ERR_ARG: a null handle, kmax <= 0, dk <= 0, n_bins outside [1, AZTOT_SK_MAX_BINS], M < 0, an empty set, and a kmax
+   that needs a harmonic above AZTOT_SK_MAX_HARMONIC on any axis, i.e. (49 g_a)*(49 g_a) <= kmax*kmax (the message names the axis and the bound on kmax
+   this box admits; nothing is truncated silently).  48 is the range over which the harmonic recurrence is held to its tolerance
+   (tests/test_gpu_ewald.py) and what the on-chip tables are sized for.  A refused set-up leaves the earlier one.
+
+   A SAMPLE reads the state aztot_md_to_host would return: wrapped positions and species, by atom id.  For species s and vector k the amplitude is
+   rho_s(k) = sum_{j of species s} exp(i k r_j) as (re, im), the phase being 2 pi (l x / L_x + m y / L_y + n z / L_z) with the true pi.  Per atom and
+   axis exp(2 pi i x / L_a) is evaluated once; higher harmonics come by complex multiplication, negative m or n by conjugation.  Against the exact
+   sum, |rho_s - exact| <= 1e-13 n_s per component (tests/test_gpu_sk.py, 50 digits).
+
+   ORDER OF THE SUM.  No floating-point atomics anywhere.  The ids are cut into tiles of 64 consecutive ids; there are nB = min(256, ceil(N / 64)) rows.
+   Row r adds the atoms of tiles r, r + nB, r + 2 nB, ... in that order, ascending id inside a tile, one atom at a time from +0.0; atoms of other
+   species add nothing.  The nB row sums are zero-padded to 256 and folded by halving (a[j] = a[j] + a[j + h] for h = 128 ... 1).  The order is a function
+   of N alone: it does not depend on the slot order the cell sort left, on the launch shape, on how many atoms an on-chip tile holds or on how the
+   vectors are batched.  Two handles holding the same state return the same bits.
+
+   ACCUMULATION.  Species pair (a, b), a <= b, has the RDF's pair index mn * (n_species - 1) + mn * (1 - mn) / 2 + mx.  Each sample adds, once, in
+   sample order, acc[k][pair] = acc[k][pair] + t with t = (re_a*re_b) + (im_a*im_b) = Re rho_a rho_b*, each operation rounded on its own; the sample
+   count goes up by one.  A reset or a set-up clears the accumulators; nothing else does.
+
+   VALUES, Ashcroft-Langreth.  Per vector S_ab(k) = acc / (samples * sqrt(n_a n_b)), 0 where n_a n_b == 0 or before the first sample.  Per bin: the
+   plain mean over the bin's kept vectors, summed in set order.  The total per vector is S(k) = sum_{a <= b} w_ab sqrt(n_a n_b) S_ab(k) / N with
+   w_aa = 1, w_ab = 2 for a < b (summed in pair order), binned the same way.  The bin centre is k = (b + 0.5) dk.  n_in_bin is the number of kept
+   vectors of each bin; the per-bin mean is defined as 0 where it is 0, and callers mask such rows by it.
+
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.  A run that
+   samples is bit-identical in state and statistics to one that calls aztot_get_stats at the same points.
+   Out of scope: slab ranks, nuclei groups, charge-charge or scattering-length-weighted combinations (a caller forms them from the partials), the
+   imaginary part of the cross terms, the intermediate scattering function F(k, t) (a caller can build it from aztot_sk_amplitudes), vectors past 48
+   harmonics, a matrix-core (MFMA) formulation.
+   Errors: sampling or reading before the set-up, aztot_sk_amplitudes before a sample, a cap too small for a non-null buffer -> AZTOT_ERR_ARG; a handle
+   that failed earlier refuses to sample but can still be read. */
+#define AZTOT_SK_MAX_HARMONIC 48
+#define AZTOT_SK_MAX_BINS 4096
+/* (re)allocates and zeroes; returns n_k */
+int aztot_sk_setup(aztot_md *md, double kmax, double dk, int max_per_bin);
+/* the amplitudes of the current configuration; adds Re rho_a rho_b* to the sums */
+int aztot_sk_sample(aztot_md *md);
+/* zero sums and sample count */
+int aztot_sk_reset(aztot_md *md);
+int aztot_sk_shape(aztot_md *md, int *n_vectors, int *n_bins, int *n_pairs, int64_t *samples);
+/* lmn[3 * vector + axis] and bin[vector]; returns n_k (both optional; cap counts vectors) */
+int aztot_sk_vectors(aztot_md *md, int32_t *lmn, int32_t *bin, int cap);
+/* rho[(vector * n_species + species) * 2 + (0 re, 1 im)] of the last sample; returns n_k * n_species * 2 (rho null and cap 0: the size alone) */
+int aztot_sk_amplitudes(aztot_md *md, double *rho, int cap);
+/* acc[vector * n_pairs + pair]; returns n_k * n_pairs (samples and acc are each optional) */
+int aztot_sk_sums(aztot_md *md, int64_t *samples, double *acc, int cap);
+/* bin centres, kept vectors per bin and the total (n_bins of each), s_pair[bin * n_pairs + pair]; returns n_bins * n_pairs (every output optional; cap counts
+   s_pair's entries) */
+int aztot_sk_values(aztot_md *md, double *k, int32_t *n_in_bin, double *s_total, double *s_pair, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
