@@ -88,6 +88,11 @@ class _AdfColumn(C.Structure):
     _fields_ = [("central", C.c_int32), ("ligand_a", C.c_int32), ("ligand_b", C.c_int32), ("reserved", C.c_int32), ("radius_a", C.c_double), ("radius_b", C.c_double)]
 
 
+class _BooParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("central_mask", C.c_int32), ("ligand_mask", C.c_int32), ("n_orders", C.c_int32), ("orders", C.c_int32 * 4),
+                ("n_bins", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _Stress(C.Structure):
     _fields_ = [("step", C.c_int64), ("time", C.c_double), ("volume", C.c_double), ("kinetic", C.c_double * 6), ("virial", C.c_double * 6),
                 ("pressure", C.c_double * 6), ("pressure_iso", C.c_double), ("eng_vdw", C.c_double), ("eng_coul", C.c_double),
@@ -115,6 +120,7 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_adf_setup", "aztot_adf_sample", "aztot_adf_reset", "aztot_adf_shape", "aztot_adf_edges", "aztot_adf_counts", "aztot_adf_values",
            "aztot_adf_neighbours",
            "aztot_sk_setup", "aztot_sk_sample", "aztot_sk_reset", "aztot_sk_shape", "aztot_sk_vectors", "aztot_sk_amplitudes", "aztot_sk_sums", "aztot_sk_values",
+           "aztot_boo_setup", "aztot_boo_sample", "aztot_boo_reset", "aztot_boo_shape", "aztot_boo_per_atom", "aztot_boo_qlm", "aztot_boo_counts", "aztot_boo_values",
            "aztot_last_error", "aztot_version")
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
@@ -260,6 +266,14 @@ def lib():
         L.aztot_sk_amplitudes.argtypes = [C.c_void_p, _dp, C.c_int]
         L.aztot_sk_sums.argtypes = [C.c_void_p, C.POINTER(C.c_int64), _dp, C.c_int]
         L.aztot_sk_values.argtypes = [C.c_void_p, _dp, _ip, _dp, _dp, C.c_int]
+        L.aztot_boo_setup.argtypes = [C.c_void_p, C.POINTER(_BooParams)]
+        L.aztot_boo_sample.argtypes = [C.c_void_p]
+        L.aztot_boo_reset.argtypes = [C.c_void_p]
+        L.aztot_boo_shape.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip, C.POINTER(C.c_int64)]
+        L.aztot_boo_per_atom.argtypes = [C.c_void_p, _ip, _dp, C.c_int]
+        L.aztot_boo_qlm.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.aztot_boo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint64), C.c_int]
+        L.aztot_boo_values.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -782,6 +796,64 @@ class Engine:
         k, cnt, tot, part = np.zeros(nb), np.zeros(nb, dtype=np.int32), np.zeros(nb), np.zeros(nb * npair)
         _check(lib().aztot_sk_values(self.h, k.ctypes.data_as(_dp), cnt.ctypes.data_as(_ip), tot.ctypes.data_as(_dp), part.ctypes.data_as(_dp), part.size))
         return k, cnt, tot, part.reshape(nb, npair)
+
+    # ---- bond-orientational order (aztot_boo_*; bonds, values, the order of the sums and the totals are stated in include/aztot.h) ----
+    def boo_setup(self, radius, orders, n_bins, central_mask, ligand_mask, reserved=0):
+        """Steinhardt q_l and the neighbour-averaged form for the given orders l; the masks have bit s for species s; (re)allocates and zeroes, returns n_bins"""
+        p = _BooParams()
+        p.radius, p.central_mask, p.ligand_mask, p.n_orders, p.n_bins, p.reserved = float(radius), int(central_mask), int(ligand_mask), len(orders), int(n_bins), int(reserved)
+        for o, l in enumerate(list(orders)[:4]):
+            p.orders[o] = int(l)
+        return _check(lib().aztot_boo_setup(self.h, C.byref(p)))
+
+    def boo_sample(self):
+        """the per-atom values of the current configuration; adds them to the totals"""
+        _check(lib().aztot_boo_sample(self.h))
+
+    def boo_reset(self):
+        _check(lib().aztot_boo_reset(self.h))
+
+    def boo_shape(self):
+        """(orders, n_bins, n_species, samples)"""
+        no, nb, ns, sm = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        orders = np.zeros(4, dtype=np.int32)
+        _check(lib().aztot_boo_shape(self.h, C.byref(no), orders.ctypes.data_as(_ip), C.byref(nb), C.byref(ns), C.byref(sm)))
+        return tuple(int(l) for l in orders[:no.value]), nb.value, ns.value, sm.value
+
+    def boo_per_atom(self):
+        """(n[n_atoms] int32, q[n_atoms, n_orders, 2]) of the last sample in ORIGINAL atom order: neighbours (-1: not central), q_l (kind 0) and q-bar_l (kind 1)"""
+        no = len(self.boo_shape()[0])
+        n = _check(lib().aztot_boo_per_atom(self.h, None, None, 0))
+        cnt, q = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1) * no * 2)
+        _check(lib().aztot_boo_per_atom(self.h, cnt.ctypes.data_as(_ip), q.ctypes.data_as(_dp), n))
+        return cnt[:n], q[:n * no * 2].reshape(n, no, 2)
+
+    def boo_qlm(self):
+        """complex q_lm[n_atoms, n_orders, 13] of the last sample in ORIGINAL atom order, m = 0 ... 12 (zeros past m = l)"""
+        no = len(self.boo_shape()[0])
+        n = _check(lib().aztot_boo_qlm(self.h, None, 0))
+        out = np.zeros(max(n, 1))
+        _check(lib().aztot_boo_qlm(self.h, out.ctypes.data_as(_dp), n))
+        out = out[:n].reshape(-1, no, 13, 2)
+        return out[..., 0] + 1j * out[..., 1]
+
+    def boo_counts(self):
+        """(samples, hist[2, n_orders, n_species, n_bins] uint64, sums[2, n_orders, n_species], entered[n_species] uint64)"""
+        orders, nb, ns, _ = self.boo_shape()
+        no = len(orders)
+        hist, sums, entered = np.zeros(2 * no * ns * nb, dtype=np.uint64), np.zeros(2 * no * ns), np.zeros(ns, dtype=np.uint64)
+        samples = C.c_int64()
+        u64 = C.POINTER(C.c_uint64)
+        _check(lib().aztot_boo_counts(self.h, C.byref(samples), hist.ctypes.data_as(u64), sums.ctypes.data_as(_dp), entered.ctypes.data_as(u64), hist.size))
+        return samples.value, hist.reshape(2, no, ns, nb), sums.reshape(2, no, ns), entered
+
+    def boo_values(self):
+        """(centre[n_bins], density[2, n_orders, n_species, n_bins] per unit q, mean[2, n_orders, n_species])"""
+        orders, nb, ns, _ = self.boo_shape()
+        no = len(orders)
+        centre, dens, mean = np.zeros(nb), np.zeros(2 * no * ns * nb), np.zeros(2 * no * ns)
+        _check(lib().aztot_boo_values(self.h, centre.ctypes.data_as(_dp), dens.ctypes.data_as(_dp), mean.ctypes.data_as(_dp), dens.size))
+        return centre, dens.reshape(2, no, ns, nb), mean.reshape(2, no, ns)
 
     def close(self):
         if getattr(self, "h", None):

@@ -124,6 +124,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  vaf (steps between two rows of vaf.dat: the 'vaf' line of control.txt; 0 without one)
 //  stress (steps between two rows of stress.dat: the 'stress' line of control.txt, our extension; 0 without one)
 //  adf (n_bins, every, n, then per line: central, ligand_a, ligand_b species ids, R_a, R_b: the 'adf' block of control.txt, our extension; 0, 0, 0 without one)
+//  boo (R, n_bins, every, central_mask, ligand_mask, n_orders, then the orders: the 'boo' line of control.txt, our extension; n_bins = 0 without one)
 //  sk (kmax, dk, every, max_per_bin: the 'strfac' line of control.txt, our extension; kmax = 0 without one)
 //  types x y z vx vy vz   (per atom)    photons uvx uvy uvz (radiative thermostat tables; seed = first element of `out` on entry for photons)
 int aztot_model_query(const aztot_model* h, const char* key, double* out, int cap)
@@ -205,6 +206,11 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             for (const auto& c : m.adf_cols) { v.push_back(c.central); v.push_back(c.ligand_a); v.push_back(c.ligand_b); v.push_back(c.radius_a); v.push_back(c.radius_b); }
         }
         else if (k == "sk") v = {m.sk_kmax, m.sk_dk, (double)m.sk_every, (double)m.sk_max_per_bin};
+        else if (k == "boo")
+        {
+            v = {m.boo.radius, (double)m.boo.n_bins, (double)m.boo_every, (double)m.boo.central_mask, (double)m.boo.ligand_mask, (double)m.boo.n_orders};
+            for (int o = 0; o < m.boo.n_orders; o++) v.push_back(m.boo.orders[o]);
+        }
         else if (k == "nuclei") { for (int j : nuclei_of(m).of) v.push_back(j); }
         else if (k == "n_nuclei") v = {(double)nuclei_of(m).names.size()};
         else if (k == "types") { v.resize(m.nAt); for (int i = 0; i < m.nAt; i++) v[i] = m.types[i]; }
@@ -862,6 +868,122 @@ int aztot_sk_values(aztot_md* md, double* k, int32_t* n_in_bin, double* s_total,
         if (n_in_bin) std::memcpy(n_in_bin, nv.data(), sizeof(int32_t) * nv.size());
         if (s_total) std::memcpy(s_total, tv.data(), sizeof(double) * tv.size());
         if (s_pair) std::memcpy(s_pair, pv.data(), sizeof(double) * pv.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_boo_setup(aztot_md* md, const aztot_boo_params* params)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    if (!params) return fail(AZTOT_ERR_ARG, "boo: null params");
+    int nb = 0;
+    const int rc = guarded([&] { nb = md->eng->samplers().boo_setup(*params); });
+    return rc < 0 ? rc : nb;
+}
+
+int aztot_boo_sample(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().boo_sample(); });
+}
+
+int aztot_boo_reset(aztot_md* md)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] { md->eng->samplers().boo_reset(); });
+}
+
+int aztot_boo_shape(aztot_md* md, int* n_orders, int32_t* orders, int* n_bins, int* n_species, int64_t* samples)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    return guarded([&] {
+        int no = 0, nb = 0, ns = 0, ord[AZTOT_BOO_MAX_ORDERS];
+        long long sm = 0;
+        md->eng->samplers().boo_shape(no, nb, ns, sm, ord);
+        if (n_orders) *n_orders = no;
+        if (orders) for (int o = 0; o < AZTOT_BOO_MAX_ORDERS; o++) orders[o] = ord[o];
+        if (n_bins) *n_bins = nb;
+        if (n_species) *n_species = ns;
+        if (samples) *samples = sm;
+    });
+}
+
+int aztot_boo_per_atom(aztot_md* md, int32_t* n, double* q, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int no = 0, nb = 0, ns = 0;
+        long long sm = 0;
+        md->eng->samplers().boo_shape(no, nb, ns, sm);          // (refuses before the set-up)
+        need = md->eng->n_atoms_global();
+        if ((n || q) && cap < need) throw ArgError("boo: cap < n_atoms");
+        std::vector<int32_t> nv;
+        std::vector<double> qv;
+        md->eng->samplers().boo_per_atom(nv, qv);               // (refuses before a sample)
+        if (n) std::memcpy(n, nv.data(), sizeof(int32_t) * nv.size());
+        if (q) std::memcpy(q, qv.data(), sizeof(double) * qv.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_boo_qlm(aztot_md* md, double* qlm, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int no = 0, nb = 0, ns = 0;
+        long long sm = 0;
+        md->eng->samplers().boo_shape(no, nb, ns, sm);
+        const long long want = (long long)md->eng->n_atoms_global() * no * 2 * (AZTOT_BOO_MAX_L + 1);
+        if (want > 0x7fffffffLL) throw ArgError("boo: n_atoms * n_orders * 26 does not fit an int");
+        need = (int)want;
+        if (qlm && cap < need) throw ArgError("boo: cap < n_atoms * n_orders * 26");
+        std::vector<double> v;
+        md->eng->samplers().boo_qlm(v);                         // (refuses before a sample)
+        if (qlm) std::memcpy(qlm, v.data(), sizeof(double) * v.size());
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_boo_counts(aztot_md* md, int64_t* samples, uint64_t* hist, double* sums, uint64_t* entered, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int no = 0, nb = 0, ns = 0;
+        long long sm = 0;
+        md->eng->samplers().boo_shape(no, nb, ns, sm);
+        need = 2 * no * ns * nb;
+        if (hist && cap < need) throw ArgError("boo: cap < 2 * n_orders * n_species * n_bins");
+        if (samples) *samples = sm;
+        if (!hist && !sums && !entered) return;
+        std::vector<unsigned long long> h, e;
+        std::vector<double> s;
+        md->eng->samplers().boo_counts(h, s, e);
+        if (hist) for (size_t k = 0; k < h.size(); k++) hist[k] = h[k];
+        if (sums) std::memcpy(sums, s.data(), sizeof(double) * s.size());
+        if (entered) for (size_t k = 0; k < e.size(); k++) entered[k] = e[k];
+    });
+    return rc < 0 ? rc : need;
+}
+
+int aztot_boo_values(aztot_md* md, double* centre, double* density, double* mean, int cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    int need = 0;
+    const int rc = guarded([&] {
+        int no = 0, nb = 0, ns = 0;
+        long long sm = 0;
+        md->eng->samplers().boo_shape(no, nb, ns, sm);
+        need = 2 * no * ns * nb;
+        if (density && cap < need) throw ArgError("boo: cap < 2 * n_orders * n_species * n_bins");
+        if (!centre && !density && !mean) return;
+        std::vector<double> c, d, mn;
+        md->eng->samplers().boo_values(c, d, mn);
+        if (centre) std::memcpy(centre, c.data(), sizeof(double) * c.size());
+        if (density) std::memcpy(density, d.data(), sizeof(double) * d.size());
+        if (mean) std::memcpy(mean, mn.data(), sizeof(double) * mn.size());
     });
     return rc < 0 ? rc : need;
 }

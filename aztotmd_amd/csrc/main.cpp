@@ -26,6 +26,11 @@
 //                   the total S(k) and the Ashcroft-Langreth partials.  The schedule of adf.dat: sampled after every completed step c > nequil with
 //                   c % every == 0; with every == 0, or when the run ended before the first sample, once on the final configuration.  A kmax the box cannot
 //                   serve (past 48 harmonics on an axis, or no vector at all) gives a WARNING and no file.  Without the line: no sampler, no file
+//   boo.dat         OUR EXTENSION, with 'boo <R> <n_bins> <every> <n_orders> <l...> <nCentral> <names...> <nLigand> <names...>': the bond-orientational order
+//                   parameters of aztot_boo_*, header "q" + "\tq<l>_<species>\tqbar<l>_<species>" per order and central species, a row per bin: the bin centre
+//                   and the density per unit q of each column; then a comment line per column, "# <column> mean <mean> entered <atoms>".  The schedule of
+//                   adf.dat.  Without the line: no sampler, no file
+//   boo_n.dat       the same layout with the raw counts
 // Both displ.dat and vaf.dat are switched on by the 'vaf n' line (n > 0): a control.txt without it runs and writes exactly what it did before the sampler existed.
 // MSD / VAF schedule: ONE sampler (aztot_tcf_*) with a single origin, n_origins = 1 and origin_every = the number of samples the run takes.  Sample 0 is the
 // initial state (x0s, sys_init.cpp:545); a step c < nequil that writes a stat row samples and writes a displ.dat row; at c == nequil (> 0) the sampler is
@@ -37,7 +42,8 @@
 // RDF schedule: the reference counts iStep from 0 and samples at the end of the loop body (main.cu:392-395), i.e. after completed step c whenever
 // (c - 1) % every == 0: after steps 1, 1 + every, ...  Call boundaries: aztot_step is called with n = the distance to the next event, an event being a
 // stat row (c % stat == 0, and the last step), an RDF sample (which only reads the state: its place against the stat row of the same step does not matter),
-// the end of the equilibration, a vaf.dat row, a stress.dat row, a sample of the bond-angle distributions or one of the structure factors.
+// the end of the equilibration, a vaf.dat row, a stress.dat row, a sample of the bond-angle distributions, one of the structure factors or one of the
+// bond-orientational order.
 // Unlike the reference, atoms are written in their ORIGINAL order (the reference writes them cell-sorted, SURVEY C-20).
 // Everything goes through the C ABI of include/aztot.h.
 #include <cmath>
@@ -160,6 +166,48 @@ static void write_sk(aztot_md* md, const std::vector<std::string>& names, const 
         std::fprintf(f, "\n");
     }
     std::fclose(f);
+}
+
+// boo.dat: header "q\tq<l>_<species>\tqbar<l>_<species>...", rows "%f" centre then "\t%f" per column, then "# <column> mean %f entered %llu" per column;
+// boo_n.dat: the same with the raw counts as "%llu"
+static void write_boo(aztot_md* md, int centralMask, const std::vector<std::string>& names, const std::string& path, const std::string& pathN)
+{
+    int no = 0, nb = 0, ns = 0;
+    int32_t orders[AZTOT_BOO_MAX_ORDERS];
+    if (aztot_boo_shape(md, &no, orders, &nb, &ns, nullptr) != AZTOT_OK) die("boo shape");
+    const int nh = 2 * no * ns * nb;
+    std::vector<double> centre(std::max(nb, 1)), dens((size_t)std::max(nh, 1)), mean((size_t)std::max(2 * no * ns, 1));
+    std::vector<uint64_t> cnt(dens.size()), entered((size_t)std::max(ns, 1));
+    if (aztot_boo_values(md, centre.data(), dens.data(), mean.data(), nh) < 0) die("boo values");
+    if (aztot_boo_counts(md, nullptr, cnt.data(), nullptr, entered.data(), nh) < 0) die("boo counts");
+    struct Col { std::string name; int at, species; };       // at: (kind * n_orders + order) * n_species + species
+    std::vector<Col> cols;
+    for (int o = 0; o < no; o++)
+        for (int s = 0; s < ns; s++)
+        {
+            if (!((centralMask >> s) & 1)) continue;
+            for (int kind = 0; kind < 2; kind++)
+                cols.push_back({std::string(kind ? "qbar" : "q") + std::to_string(orders[o]) + "_" + names[s], (kind * no + o) * ns + s, s});
+        }
+    for (int raw = 0; raw < 2; raw++)
+    {
+        const std::string& file = raw ? pathN : path;
+        FILE* f = std::fopen(file.c_str(), "w");
+        if (!f) { std::perror(file.c_str()); std::exit(1); }
+        std::fprintf(f, "q");
+        for (const auto& c : cols) std::fprintf(f, "\t%s", c.name.c_str());
+        std::fprintf(f, "\n");
+        for (int b = 0; b < nb; b++)
+        {
+            std::fprintf(f, "%f", centre[b]);
+            for (const auto& c : cols)
+                if (raw) std::fprintf(f, "\t%llu", (unsigned long long)cnt[(size_t)c.at * nb + b]);
+                else std::fprintf(f, "\t%f", dens[(size_t)c.at * nb + b]);
+            std::fprintf(f, "\n");
+        }
+        for (const auto& c : cols) std::fprintf(f, "# %s mean %f entered %llu\n", c.name.c_str(), mean[c.at], (unsigned long long)entered[c.species]);
+        std::fclose(f);
+    }
 }
 
 // "<time>\t<step>" + "\t%f" per species: the row layout of out_msd's MSD columns and of vaf_info
@@ -324,6 +372,22 @@ int main(int argc, char** argv)
     }
     auto sk_due = [&](int c) { return skOn && skEvery > 0 && c > nEq && c % skEvery == 0; };
     int skTaken = 0;
+    // bond-orientational order ('boo', our extension): the schedule of the bond-angle distributions, the files at the end
+    double booq[6 + AZTOT_BOO_MAX_ORDERS] = {0};
+    if (aztot_model_query(model, "boo", booq, 6 + AZTOT_BOO_MAX_ORDERS) < 6) die("boo");
+    const int booEvery = (int)booq[2];
+    bool booOn = booq[1] > 0.0;
+    aztot_boo_params booPar = {};
+    booPar.radius = booq[0]; booPar.n_bins = (int32_t)booq[1]; booPar.central_mask = (int32_t)booq[3]; booPar.ligand_mask = (int32_t)booq[4];
+    booPar.n_orders = (int32_t)booq[5];
+    for (int o = 0; o < booPar.n_orders && o < AZTOT_BOO_MAX_ORDERS; o++) booPar.orders[o] = (int32_t)booq[6 + o];
+    if (booOn && aztot_boo_setup(md, &booPar) < 0)
+    {
+        std::fprintf(stderr, "WARNING: boo directive not usable (%s): no boo.dat\n", aztot_last_error());
+        booOn = false;
+    }
+    auto boo_due = [&](int c) { return booOn && booEvery > 0 && c > nEq && c % booEvery == 0; };
+    int booTaken = 0;
     aztot_stats st;
     for (int done = 0; done < nStep;)
     {
@@ -341,8 +405,14 @@ int main(int argc, char** argv)
         if (stressOn) n = std::min(n, (done / stressEvery + 1) * stressEvery - done);
         if (adfOn && adfEvery > 0) n = std::min(n, (std::max(done, nEq) / adfEvery + 1) * adfEvery - done);
         if (skOn && skEvery > 0) n = std::min(n, (std::max(done, nEq) / skEvery + 1) * skEvery - done);
+        if (booOn && booEvery > 0) n = std::min(n, (std::max(done, nEq) / booEvery + 1) * booEvery - done);
         if (aztot_step(md, n) != AZTOT_OK) die("step");
         done += n;
+        if (boo_due(done))
+        {
+            if (aztot_boo_sample(md) != AZTOT_OK) die("boo sample");
+            booTaken++;
+        }
         if (sk_due(done))
         {
             if (aztot_sk_sample(md) != AZTOT_OK) die("sk sample");
@@ -413,6 +483,11 @@ int main(int argc, char** argv)
     {
         if (adfTaken == 0 && aztot_adf_sample(md) != AZTOT_OK) die("adf sample");
         write_adf(md, adfCols, names, out + "/adf.dat", out + "/adf_n.dat");
+    }
+    if (booOn)
+    {
+        if (booTaken == 0 && aztot_boo_sample(md) != AZTOT_OK) die("boo sample");
+        write_boo(md, booPar.central_mask, names, out + "/boo.dat", out + "/boo_n.dat");
     }
     if (skOn)
     {

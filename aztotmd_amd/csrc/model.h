@@ -126,6 +126,10 @@ struct Model
     // (0: one sample of the final configuration); sk_kmax == 0: off
     double sk_kmax = 0, sk_dk = 0;
     int sk_every = 0, sk_max_per_bin = 0;
+    // 'boo <R> <n_bins> <every> <n_orders> <l...> <nCentral> <names...> <nLigand> <names...>' (ours): bond-orientational order (aztot_boo_setup), a sample
+    // every `every` steps after the equilibration (0: one sample of the final configuration); boo.n_bins == 0: off
+    aztot_boo_params boo{};
+    int boo_every = 0;
     // Elec (dataStruct.h:349-366)
     int elec_type = AZTOT_ELEC_NONE;
     double rReal = 0, r2Real = 0, alpha = 0, eps = 1.0;

@@ -1,6 +1,6 @@
 // The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h), the
-// pressure tensor (stress.hip.h), bond-angle distributions (adf.hip.h) and static structure factors (sk.hip.h) behind aztot_rdf_* / aztot_cn_* / aztot_tcf_* /
-// aztot_stress_* / aztot_adf_* / aztot_sk_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
+// pressure tensor (stress.hip.h), bond-angle distributions (adf.hip.h), static structure factors (sk.hip.h) and bond-orientational order (boo.hip.h) behind
+// aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* / aztot_adf_* / aztot_sk_* / aztot_boo_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
 // is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
 //
 // The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
@@ -91,6 +91,17 @@ public:
     void sk_amplitudes(std::vector<double>& rho);                      // [vector][species][re, im] of the last sample
     void sk_sums(std::vector<double>& acc);                            // [vector][pair]
     void sk_values(std::vector<double>& k, std::vector<int32_t>& nInBin, std::vector<double>& sTotal, std::vector<double>& sPair);   // [bin], [bin], [bin], [bin][pair]
+
+    // bond-orientational order (include/aztot.h states the bonds, the values, the order of the sums and the totals)
+    int boo_setup(const aztot_boo_params& p);                          // (re)allocates and zeroes; returns the number of bins
+    void boo_sample();
+    void boo_reset();
+    void boo_shape(int& nOrders, int& nBins, int& nSpec, long long& samples, int* orders = nullptr);
+    void boo_per_atom(std::vector<int32_t>& n, std::vector<double>& q);    // by atom id: n[atom], q[(atom * n_orders + order) * 2 + kind]
+    void boo_qlm(std::vector<double>& qlm);                            // [atom id][order][m 0 ... 12][re, im] of kind 0
+    // hist [kind][order][species][bin], sums [kind][order][species], entered [species]
+    void boo_counts(std::vector<unsigned long long>& hist, std::vector<double>& sums, std::vector<unsigned long long>& entered);
+    void boo_values(std::vector<double>& centre, std::vector<double>& density, std::vector<double>& mean);     // [bin], hist's layout, sums' layout
 
 private:
     // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
@@ -187,6 +198,20 @@ private:
         int32_t *type = nullptr, *dLmn = nullptr;
     };
 
+    // the set-up with its host-made tables, q_lm and n in canonical slot order, per-atom values by atom id, their chunk sums, totals over the samples
+    struct BooState : GridSort
+    {
+        int nBins = 0;                  // 0: not set up
+        aztot_boo_params par{};
+        long long samples = 0;
+        bool sampled = false;           // the per-atom values of a sample are there
+        int nSpec = 0, stride = 0, sliceShift = 0, nChunk = 0, nChunkPad = 0, useLds = 0;
+        size_t nPad = 0, nHist = 0;     // ids padded to a multiple of 256; histogram cells (the entered counts follow them)
+        int32_t *arrivalId = nullptr, *canonRank = nullptr, *slotId = nullptr, *nSlot = nullptr, *nById = nullptr, *typeById = nullptr;
+        double *qlm = nullptr, *qCols = nullptr, *partials = nullptr, *sums = nullptr;
+        unsigned long long* totals = nullptr;
+    };
+
     // the protocol every sampler follows, once (samplers.hip.h)
     void need_one_gpu(const char* what) const;
     static void need_setup(bool isSetUp, const char* name, const char* tail = "");
@@ -203,6 +228,7 @@ private:
     StressState& stress_state(bool needSample);
     AdfState& adf_state();
     SkState& sk_state();
+    BooState& boo_state(bool needSample);
 
     Host& host_;
     const Model& model_;            // the engine's (outlives the samplers)
@@ -216,6 +242,7 @@ private:
     StressState stress_;
     AdfState adf_;
     SkState sk_;
+    BooState boo_;
 };
 
 }  // namespace aztot

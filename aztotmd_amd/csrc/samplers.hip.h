@@ -2,6 +2,7 @@
 #pragma once
 #include "samplers.h"
 #include "stress.hip.h"
+#include "boo.hip.h"
 
 namespace aztot {
 
@@ -983,6 +984,240 @@ void Samplers::sk_values(std::vector<double>& k, std::vector<int32_t>& nInBin, s
         const double c = (double)S.nInBin[b];
         sTotal[b] = sTotal[b] / c;
         for (int p = 0; p < nP; p++) sPair[(size_t)b * nP + p] = sPair[(size_t)b * nP + p] / c;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Bond-orientational order (boo.hip.h; bonds, values, the order of the sums and the totals are stated in include/aztot.h)
+// ---------------------------------------------------------------------------------------------------
+Samplers::BooState& Samplers::boo_state(bool needSample)
+{
+    need_setup(boo_.nBins != 0, "boo");
+    if (needSample && !boo_.sampled) throw ArgError("boo: aztot_boo_sample has not been called since the set-up");
+    return boo_;
+}
+
+// N_lm = sqrt((2l + 1) / (4 pi) * (l - m)! / (l + m)!) and 4 pi / (2l + 1), made in long double and rounded once
+static BooOrder boo_order_table(int l, int at, int stride)
+{
+    const long double pi = 3.141592653589793238462643383279502884L;
+    BooOrder O{};
+    for (int m = 0; m <= l; m++)
+    {
+        long double ratio = 1.0L;                       // (l - m)! / (l + m)!
+        for (int k = l - m + 1; k <= l + m; k++) ratio /= (long double)k;
+        O.norm[m] = (double)sqrtl((long double)(2 * l + 1) / (4.0L * pi) * ratio);
+    }
+    O.scale = (double)(4.0L * pi / (long double)(2 * l + 1));
+    O.at = at; O.stride = stride;
+    return O;
+}
+
+int Samplers::boo_setup(const aztot_boo_params& p)
+{
+    need_one_gpu("bond-orientational order parameters");
+    const int nSpec = model_.nSpec();
+    if (!(p.radius > 0.0) || !std::isfinite(p.radius)) throw ArgError("boo: the radius must be positive");
+    if (p.reserved != 0) throw ArgError("boo: the reserved field must be 0");
+    const unsigned all = nSpec >= 32 ? 0xffffffffu : ((1u << nSpec) - 1u);
+    if (p.central_mask == 0 || p.ligand_mask == 0) throw ArgError("boo: central_mask and ligand_mask must not be empty");
+    if (((unsigned)p.central_mask & ~all) || ((unsigned)p.ligand_mask & ~all)) throw ArgError("boo: a mask names a species at or above n_species");
+    if (p.n_orders < 1 || p.n_orders > AZTOT_BOO_MAX_ORDERS) throw ArgError("boo: n_orders must be in [1, AZTOT_BOO_MAX_ORDERS]");
+    for (int o = 0; o < p.n_orders; o++)
+    {
+        if (p.orders[o] < 1 || p.orders[o] > AZTOT_BOO_MAX_L) throw ArgError("boo: an order must be in [1, AZTOT_BOO_MAX_L]");
+        for (int k = 0; k < o; k++)
+            if (p.orders[k] == p.orders[o]) throw ArgError("boo: the same order is given twice");
+    }
+    if (p.n_bins < 1 || p.n_bins > AZTOT_BOO_MAX_BINS) throw ArgError("boo: n_bins must be in [1, AZTOT_BOO_MAX_BINS]");
+    BooState T;
+    T.par = p;
+    for (int o = p.n_orders; o < AZTOT_BOO_MAX_ORDERS; o++) T.par.orders[o] = 0;
+    T.nBins = p.n_bins; T.nSpec = nSpec;
+    for (int o = 0; o < p.n_orders; o++) T.stride += 2 * (p.orders[o] + 1);
+    const int N = model_.nAt;
+    // lanes per atom: a function of N alone (the rule of the coordination numbers), so that the order of every per-atom sum is one too
+    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    T.nChunk = std::max(1, div_up(N, kBooChunk));
+    T.nChunkPad = 1;
+    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
+    T.nPad = (size_t)T.nChunk * kBooChunk;
+    T.nHist = (size_t)2 * p.n_orders * nSpec * p.n_bins;
+    T.useLds = (T.nHist + nSpec) * sizeof(uint32_t) <= (size_t)kBooHistBudget ? 1 : 0;
+    set_up(boo_, T, [&] {
+        grid_setup(T, p.radius);
+        const size_t n = (size_t)std::max(N, 1), nCols = (size_t)2 * p.n_orders;
+        T.arrivalId = T.mem.alloc<int32_t>(n, false, stream_); T.canonRank = T.mem.alloc<int32_t>(n, false, stream_);
+        T.slotId = T.mem.alloc<int32_t>(n, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.slotId, 0xff, sizeof(int32_t) * n, stream_));
+        T.nSlot = T.mem.alloc<int32_t>(n, true, stream_);
+        T.qlm = T.mem.alloc<double>(n * (size_t)T.stride, true, stream_);
+        T.nById = T.mem.alloc<int32_t>(T.nPad, true, stream_); T.typeById = T.mem.alloc<int32_t>(T.nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.typeById, 0xff, sizeof(int32_t) * T.nPad, stream_));
+        T.qCols = T.mem.alloc<double>(nCols * T.nPad, true, stream_);
+        T.partials = T.mem.alloc<double>(nCols * nSpec * (size_t)T.nChunkPad, true, stream_);
+        T.sums = T.mem.alloc<double>(nCols * nSpec, true, stream_);
+        T.totals = T.mem.alloc<unsigned long long>(T.nHist + nSpec, true, stream_);
+    });
+    return boo_.nBins;
+}
+
+void Samplers::boo_reset()
+{
+    BooState& S = boo_state(false);
+    HIP_CHECK(hipMemsetAsync(S.totals, 0, (S.nHist + S.nSpec) * 8, stream_));
+    HIP_CHECK(hipMemsetAsync(S.sums, 0, (size_t)2 * S.par.n_orders * S.nSpec * 8, stream_));
+    S.samples = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// one kernel per order L = 1 ... 12: the accumulators are indexed at compile time only
+template <typename F> static void boo_dispatch(int l, F&& go)
+{
+    switch (l)
+    {
+    case 1: go(std::integral_constant<int, 1>()); break;
+    case 2: go(std::integral_constant<int, 2>()); break;
+    case 3: go(std::integral_constant<int, 3>()); break;
+    case 4: go(std::integral_constant<int, 4>()); break;
+    case 5: go(std::integral_constant<int, 5>()); break;
+    case 6: go(std::integral_constant<int, 6>()); break;
+    case 7: go(std::integral_constant<int, 7>()); break;
+    case 8: go(std::integral_constant<int, 8>()); break;
+    case 9: go(std::integral_constant<int, 9>()); break;
+    case 10: go(std::integral_constant<int, 10>()); break;
+    case 11: go(std::integral_constant<int, 11>()); break;
+    case 12: go(std::integral_constant<int, 12>()); break;
+    default: throw std::logic_error("boo: order outside [1, 12]");
+    }
+}
+
+void Samplers::boo_sample()
+{
+    BooState& S = boo_state(false);
+    sample("boo kernels", [&](const AtomArrays& A) {
+        const int N = model_.nAt, nO = S.par.n_orders, nCols = 2 * nO;
+        S.sampled = false;
+        if (N == 0) return;
+        static const char* const names[2] = {"k_boo_bin", "k_boo_scan"};
+        grid_count(S, A, names);
+        const int nb = div_up(N, kBlock);
+        // arrival order -> ids ascending inside every cell; the slot -> id map of that order
+        timed("k_boo_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.arrivalId); });
+        timed("k_boo_rank", [&] { hipLaunchKernelGGL(k_stress_rank, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.cellStart, S.arrivalId, S.canonRank); });
+        timed("k_boo_place", [&] {
+            hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.canonRank, S.cellStart, S.x, S.y, S.z, S.kind);
+            hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.canonRank, S.cellStart, S.slotId);
+        });
+        BooParams P;
+        P.r2 = S.par.radius * S.par.radius; P.centralMask = S.par.central_mask; P.ligandMask = S.par.ligand_mask;
+        const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
+        BooOrder tab[AZTOT_BOO_MAX_ORDERS];
+        for (int o = 0, at = 0; o < nO; at += 2 * (S.par.orders[o] + 1), o++) tab[o] = boo_order_table(S.par.orders[o], at, S.stride);
+        timed("k_boo_qlm", [&] {
+            for (int o = 0; o < nO; o++)
+                boo_dispatch(S.par.orders[o], [&](auto l) {
+                    hipLaunchKernelGGL(k_boo_qlm<decltype(l)::value>, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, P, tab[o], N, S.sliceShift, S.cellStart, S.x, S.y,
+                                       S.z, S.kind, S.nSlot, S.qlm);
+                });
+        });
+        timed("k_boo_average", [&] {
+            for (int o = 0; o < nO; o++)
+                boo_dispatch(S.par.orders[o], [&](auto l) {
+                    hipLaunchKernelGGL(k_boo_average<decltype(l)::value>, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, P, tab[o], N, S.sliceShift, o, nO, S.nPad,
+                                       S.cellStart, S.x, S.y, S.z, S.kind, S.slotId, S.nSlot, S.qlm, S.qCols, S.nById, S.typeById);
+                });
+        });
+        const int gs = std::max(1, std::min(kBooMaxBlocks, nb));
+        timed("k_boo_hist", [&] {
+            hipLaunchKernelGGL(k_boo_hist, dim3(gs), dim3(kBlock), S.useLds ? (S.nHist + S.nSpec) * sizeof(uint32_t) : 0, stream_, N, nO, S.nSpec, S.nBins, S.nPad,
+                               S.useLds, S.qCols, S.nById, S.typeById, S.totals);
+        });
+        timed("k_boo_chunks", [&] {
+            hipLaunchKernelGGL(k_boo_chunks, dim3(S.nChunk), dim3(kBlock), 0, stream_, nCols, S.nSpec, S.nPad, S.nChunkPad, S.qCols, S.typeById, S.partials);
+        });
+        timed("k_boo_fold", [&] { hipLaunchKernelGGL(k_boo_fold, dim3(nCols * S.nSpec), dim3(kBlock), 0, stream_, S.nChunkPad, S.partials, S.sums); });
+    });
+    S.sampled = true;
+    S.samples++;
+}
+
+void Samplers::boo_shape(int& nOrders, int& nBins, int& nSpec, long long& samples, int* orders)
+{
+    const BooState& S = boo_state(false);
+    nOrders = S.par.n_orders; nBins = S.nBins; nSpec = S.nSpec; samples = S.samples;
+    if (orders) for (int o = 0; o < AZTOT_BOO_MAX_ORDERS; o++) orders[o] = S.par.orders[o];
+}
+
+void Samplers::boo_per_atom(std::vector<int32_t>& n, std::vector<double>& q)
+{
+    const BooState& S = boo_state(true);
+    const int N = model_.nAt, nO = S.par.n_orders;
+    n.assign((size_t)N, -1);
+    q.assign((size_t)N * nO * 2, 0.0);
+    if (N == 0) return;
+    std::vector<double> col((size_t)N);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(n.data(), S.nById, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    for (int kind = 0; kind < 2; kind++)
+        for (int o = 0; o < nO; o++)
+        {
+            HIP_CHECK(hipMemcpy(col.data(), S.qCols + (size_t)(kind * nO + o) * S.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+            for (int i = 0; i < N; i++) q[((size_t)i * nO + o) * 2 + kind] = col[i];
+        }
+}
+
+void Samplers::boo_qlm(std::vector<double>& out)
+{
+    const BooState& S = boo_state(true);
+    const int N = model_.nAt, nO = S.par.n_orders, M = 2 * (AZTOT_BOO_MAX_L + 1);
+    out.assign((size_t)N * nO * M, 0.0);
+    if (N == 0) return;
+    std::vector<int32_t> ids(N);
+    std::vector<double> q((size_t)N * S.stride);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(ids.data(), S.slotId, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(q.data(), S.qlm, sizeof(double) * q.size(), hipMemcpyDeviceToHost));
+    for (int s = 0; s < N; s++)
+    {
+        if ((unsigned)ids[s] >= (unsigned)N) continue;
+        for (int o = 0, at = 0; o < nO; at += 2 * (S.par.orders[o] + 1), o++)
+            for (int k = 0; k < 2 * (S.par.orders[o] + 1); k++) out[((size_t)ids[s] * nO + o) * M + k] = q[(size_t)s * S.stride + at + k];
+    }
+}
+
+void Samplers::boo_counts(std::vector<unsigned long long>& hist, std::vector<double>& sums, std::vector<unsigned long long>& entered)
+{
+    const BooState& S = boo_state(false);
+    std::vector<unsigned long long> all(S.nHist + S.nSpec);
+    sums.resize((size_t)2 * S.par.n_orders * S.nSpec);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(all.data(), S.totals, all.size() * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(sums.data(), S.sums, sums.size() * 8, hipMemcpyDeviceToHost));
+    hist.assign(all.begin(), all.begin() + S.nHist);
+    entered.assign(all.begin() + S.nHist, all.end());
+}
+
+// density[column][bin] = count / (column total * width), width = 1 / n_bins, 0 where the column is empty; mean = sum / entered, 0 where nothing entered
+void Samplers::boo_values(std::vector<double>& centre, std::vector<double>& density, std::vector<double>& mean)
+{
+    std::vector<unsigned long long> hist, entered;
+    std::vector<double> sums;
+    boo_counts(hist, sums, entered);
+    const int nBins = boo_.nBins, nSpec = boo_.nSpec, nCols = 2 * boo_.par.n_orders * nSpec;
+    const double width = 1.0 / (double)nBins;
+    centre.resize(nBins);
+    for (int b = 0; b < nBins; b++) centre[b] = (b + 0.5) / (double)nBins;
+    density.assign(hist.size(), 0.0);
+    mean.assign(sums.size(), 0.0);
+    for (int c = 0; c < nCols; c++)
+    {
+        unsigned long long tot = 0;
+        for (int b = 0; b < nBins; b++) tot += hist[(size_t)c * nBins + b];
+        if (tot)
+            for (int b = 0; b < nBins; b++) density[(size_t)c * nBins + b] = (double)hist[(size_t)c * nBins + b] / ((double)tot * width);
+        const unsigned long long e = entered[c % nSpec];
+        if (e) mean[c] = sums[c] / (double)e;
     }
 }
 

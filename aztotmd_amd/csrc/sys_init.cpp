@@ -428,6 +428,51 @@ void read_sim(const std::string& dir, Model& m)
         if (cap < 0) fail("ERROR[418] negative max_per_bin in 'strfac' directive of control.txt");
         m.sk_kmax = kmax; m.sk_dk = dk; m.sk_every = every; m.sk_max_per_bin = cap;
     }
+    // bond-orientational order: 'boo <R> <n_bins> <every> <n_orders> <l...> <nCentral> <names...> <nLigand> <names...>' (our extension, the arguments of
+    // aztot_boo_setup and the period of the samples), free format like outCN; no line: off.  A whole word, the first value converted whole, as 'strfac'.
+    // ERROR[419]: the shape and the numbers, ERROR[420]: the species names
+    m.boo = aztot_boo_params{}; m.boo_every = 0;
+    char booWord[64] = {0};
+    if (seek_value(f, " boo%*[ \t\r\n]%63s", booWord))
+    {
+        const char* form = "ERROR[419] malformed 'boo' directive in control.txt: boo <R> <n_bins> <every> <n_orders> <l...> <nCentral> <names...> <nLigand> <names...>";
+        char* end = nullptr;
+        const double R = std::strtod(booWord, &end);
+        int nb = 0, every = 0, no = 0;
+        if (end == booWord || *end != '\0' || std::fscanf(f, " %d %d %d", &nb, &every, &no) != 3) fail(form);
+        if (!(R > 0.0) || !std::isfinite(R)) fail("ERROR[419] the radius of the 'boo' directive must be positive");
+        if (nb < 1 || nb > AZTOT_BOO_MAX_BINS) fail("ERROR[419] n_bins of the 'boo' directive must be between 1 and " + std::to_string(AZTOT_BOO_MAX_BINS));
+        if (every < 0) fail("ERROR[419] negative period in 'boo' directive of control.txt");
+        if (no < 1 || no > AZTOT_BOO_MAX_ORDERS) fail("ERROR[419] the 'boo' directive takes between 1 and " + std::to_string(AZTOT_BOO_MAX_ORDERS) + " orders");
+        aztot_boo_params p{};
+        p.radius = R; p.n_bins = nb; p.n_orders = no;
+        for (int o = 0; o < no; o++)
+        {
+            int l = 0;
+            if (std::fscanf(f, " %d", &l) != 1) fail(form);
+            if (l < 1 || l > AZTOT_BOO_MAX_L) fail("ERROR[419] an order of the 'boo' directive must be between 1 and " + std::to_string(AZTOT_BOO_MAX_L));
+            for (int k = 0; k < o; k++)
+                if (p.orders[k] == l) fail("ERROR[419] the order " + std::to_string(l) + " is given twice in the 'boo' directive");
+            p.orders[o] = l;
+        }
+        for (int list = 0; list < 2; list++)
+        {
+            int n = 0, mask = 0;
+            if (std::fscanf(f, " %d", &n) != 1) fail(form);
+            if (n < 1 || n > m.nSpec()) fail(std::string("ERROR[419] the 'boo' directive needs between 1 and n_species ") + (list ? "ligand" : "central") + " species");
+            for (int i = 0; i < n; i++)
+            {
+                char name[64] = {0};
+                if (std::fscanf(f, " %63s", name) != 1) fail(form);
+                const int sp = species_by_name(m, name);
+                if (sp < 0) fail(std::string("ERROR[420] unknown species name (") + name + ") in the 'boo' directive of control.txt");
+                if ((mask >> sp) & 1) fail(std::string("ERROR[420] the species ") + name + " is given twice in a list of the 'boo' directive");
+                mask |= 1 << sp;
+            }
+            (list ? p.ligand_mask : p.central_mask) = mask;
+        }
+        m.boo = p; m.boo_every = every;
+    }
     // read_rdf (rdf.cpp:14-37): only the exact word 'nucl' turns the nuclei RDFs on.  The reference fails without the line (ERROR[408]); here it means "no RDF"
     m.rdf_present = 0; m.rdf_rmax = m.rdf_dr = 0.0; m.rdf_every = m.rdf_out_every = m.rdf_nucl = 0;
     if (seek_value(f, " rdf %lf ", &m.rdf_rmax))

@@ -233,6 +233,10 @@ def write_input_files(case, directory, stat=200):
             nb, every, cols = case["adf"]
             f.write("adf\t%d\t%d\t%d\n" % (int(nb), int(every), len(cols)))
             f.writelines("%s %s %s %r %r\n" % (c, a, b, float(ra), float(rb)) for c, a, b, ra, rb in cols)
+        if case.get("boo"):             # bond-orientational order (our directive, aztot_boo_*): (R, n_bins, every, [orders], [central names], [ligand names])
+            R, nb, every, orders, central, ligand = case["boo"]
+            f.write("boo\t%r\t%d\t%d\t%d %s\t%d %s\t%d %s\n" % (float(R), int(nb), int(every), len(orders), " ".join(str(int(l)) for l in orders), len(central),
+                                                                " ".join(central), len(ligand), " ".join(ligand)))
         if case.get("strfac"):          # static structure factors (our directive, aztot_sk_*): (kmax, dk, every, max_per_bin)
             kmax, dk, every, cap = case["strfac"]
             f.write("strfac\t%r\t%r\t%d\t%d\n" % (float(kmax), float(dk), int(every), int(cap)))

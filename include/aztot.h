@@ -555,6 +555,81 @@ int aztot_sk_sums(aztot_md *md, int64_t *samples, double *acc, int cap);
    s_pair's entries) */
 int aztot_sk_values(aztot_md *md, double *k, int32_t *n_in_bin, double *s_total, double *s_pair, int cap);
 
+/* ---- bond-orientational order: Steinhardt q_l per atom and the neighbour-averaged q-bar_l of Lechner and Dellago ---------------------------------------
+   The reference has no such output: like the pressure tensor and the bond-angle distributions, this sampler is ours.
+   One GPU only: a slab handle (nranks > 1, loopback included) is refused with AZTOT_ERR_INPUT.
+
+   SET-UP.  radius R; central_mask and ligand_mask, bit s for species s; n_orders in [1, AZTOT_BOO_MAX_ORDERS] distinct orders l in [1, AZTOT_BOO_MAX_L];
+   n_bins in [1, AZTOT_BOO_MAX_BINS]; reserved = 0.  Returns n_bins.  Rejected with AZTOT_ERR_ARG: a null handle or params, R <= 0 (or not finite), an
+   empty mask, a mask bit at or above n_species, an order out of range or repeated, n_orders or n_bins out of range, a non-zero `reserved`.  A refused
+   set-up leaves the earlier one in place.  A species without atoms is fine.
+
+   BONDS.  Atom i is central iff its species is in central_mask.  Its neighbours N(i) are the atoms j != i whose species is in ligand_mask and whose
+   separation satisfies 0 < r2 < R * R, strict on both sides.  The separation is that of aztot_cn_sample and aztot_adf_sample on the positions
+   aztot_md_to_host returns: u = r_j - r_i per axis, one shift by L where |d| > L / 2, r2 = (ux*ux + uy*uy) + uz*uz in fp64 with every operation rounded
+   on its own.  R may exceed L / 2: each partner is seen once, through its nearest image.  n_i = |N(i)|; there is no neighbour cap (nothing per
+   neighbour is held on chip).
+
+   VALUES.  Bond direction (x, y, z) = u * (1 / sqrt(r2)).  For m = 0 ... l
+       q_lm(i) = (1 / n_i) sum_{j in N(i)} Y_lm(direction of the bond i -> j)
+   with the orthonormal complex spherical harmonics and the Condon-Shortley phase; m < 0 follows by symmetry and is neither stored nor summed.
+       q_l(i) = sqrt( 4 pi / (2l + 1) * ( |q_l0|^2 + 2 sum_{m > 0} |q_lm|^2 ) )
+   Averaged form, C(i) the central atoms among N(i):
+       qbar_lm(i) = ( q_lm(i) + sum_{k in C(i)} q_lm(k) ) / (1 + |C(i)|),      qbar_l(i) from qbar_lm(i) by the same expression.
+   n_i = 0: q_lm = 0 and q_l = qbar_l = 0; a central neighbour with n_k = 0 enters with zeros and is counted in |C(i)|.  An atom that is not central
+   has n = -1 and all values 0.
+
+   ROUTE.  No sin, cos, acos or atan2: (x + i y)^m by complex multiplication, T_l^m(z) = P_l^m(z) / sin^m(theta) by the three-term recurrence in l from
+   T_m^m = (-1)^m (2m - 1)!!, the normalisation sqrt((2l + 1) / (4 pi) (l - m)! / (l + m)!) from a host table made in extended precision and applied
+   once per atom to the sums.  Nothing divides by sin(theta): a bond along +-z is an ordinary bond.  One correctly rounded sqrt and one division per
+   bond.  No floating-point atomics.  The harmonic arithmetic may contract to fused multiply-adds: q_lm is held to a stated tolerance, not to the bit
+   (tests/boo_model.py: QLM_TOL per component, four times the measured worst error of the same route in plain fp64).
+
+   ORDER OF THE SUMS.  A sample's per-atom values are a function of the sampled state alone (wrapped positions, ids, types, N, box, set-up): neighbour
+   cells in a fixed order, ids ascending inside a cell, dealt to a number of lanes that depends on N only, folded by lane exchange in a fixed order.  Two
+   handles that hold the same state return the same bits, whatever slot order their engines' sorts left.
+
+   TOTALS over the samples.  Only central atoms with n_i > 0 enter.  uint64 hist[kind][order][species][bin], kind 0 = q, 1 = qbar, with
+   bin = min(n_bins - 1, (int) fl(q * n_bins)); fp64 sum[kind][order][species]: the summation tree of aztot_tcf_sample (runs of 64 ids, the four runs of
+   256, the chunks padded to a power of two and halved) over the per-atom values in id order, the term of an atom of another species +0.0, added to
+   the running sum once per sample in sample order; uint64 entered[species]; the number of samples.  A reset or a set-up clears them; nothing else does.
+   Values: centre (b + 0.5) / n_bins; density per unit q = count / (column total * width), width = 1 / n_bins, 0 where the column total is 0 (a
+   column is one (kind, order, species)); mean = sum / entered, 0 where entered is 0.
+
+   Timing as aztot_rdf_sample: completes the deferred end of the last aztot_step call, only READS the state, returns with the device idle.
+   Out of scope: the w_l invariants (a caller forms them from aztot_boo_qlm), k-nearest or Voronoi neighbourhoods, solid-like bond counts (ten Wolde),
+   nuclei groups, slab ranks, several set-ups side by side.
+   Errors: sampling or reading before the set-up, aztot_boo_per_atom / aztot_boo_qlm before a sample, a cap too small for a non-null buffer ->
+   AZTOT_ERR_ARG; a handle that failed earlier refuses to sample but can still be read. */
+#define AZTOT_BOO_MAX_ORDERS 4
+#define AZTOT_BOO_MAX_L 12
+#define AZTOT_BOO_MAX_BINS 4096
+typedef struct aztot_boo_params
+{
+    double radius;
+    int32_t central_mask, ligand_mask;                 /* bit s: species s */
+    int32_t n_orders, orders[AZTOT_BOO_MAX_ORDERS];
+    int32_t n_bins, reserved;                          /* reserved must be 0 */
+} aztot_boo_params;                                    /* 48 bytes */
+/* (re)allocates and zeroes; returns n_bins */
+int aztot_boo_setup(aztot_md *md, const aztot_boo_params *params);
+/* the per-atom values of the current configuration; adds them to the totals */
+int aztot_boo_sample(aztot_md *md);
+/* zero totals and sample count */
+int aztot_boo_reset(aztot_md *md);
+/* orders: room for AZTOT_BOO_MAX_ORDERS entries (each output optional) */
+int aztot_boo_shape(aztot_md *md, int *n_orders, int32_t *orders, int *n_bins, int *n_species, int64_t *samples);
+/* last sample by atom id: n[atom] (-1: not central), q[(atom * n_orders + order) * 2 + kind]; returns n_atoms (both null and cap 0: the size alone;
+   cap counts atoms) */
+int aztot_boo_per_atom(aztot_md *md, int32_t *n, double *q, int cap);
+/* q_lm of the last sample, qlm[((atom * n_orders + order) * 13 + m) * 2 + (0 re, 1 im)], zeros past m = l; returns n_atoms * n_orders * 26 */
+int aztot_boo_qlm(aztot_md *md, double *qlm, int cap);
+/* hist[((kind * n_orders + order) * n_species + species) * n_bins + bin], sums[(kind * n_orders + order) * n_species + species], entered[species];
+   returns the size of hist (every output optional; cap counts hist's entries, sums and entered need room for their full size) */
+int aztot_boo_counts(aztot_md *md, int64_t *samples, uint64_t *hist, double *sums, uint64_t *entered, int cap);
+/* bin centres (n_bins), density in hist's layout, mean in sums' layout; returns the size of density (each optional; cap counts density's entries) */
+int aztot_boo_values(aztot_md *md, double *centre, double *density, double *mean, int cap);
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
    names: NUL-separated list written into `names` (cap bytes); ms / calls: arrays of length >= returned count */
