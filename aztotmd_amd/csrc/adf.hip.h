@@ -1,8 +1,8 @@
 // Bond-angle distributions (aztot_adf_*, include/aztot.h) on the samplers' kind of private cell grid.  The reference has no such output: the directive is ours.
 //
-//  k_rdf_bin + k_scan_* + k_rdf_place (rdf.hip.h)   counting sort of the current positions into cells with an edge >= the largest radius
-//  k_cn_slot_ids (cn.hip.h)                          the slot -> atom id map of that sort
-//  k_adf_neigh                                       neighbours of every central atom (lanes = (atom, slice of the candidates), as k_cn_pairs) and the
+//  k_grid_bin + k_scan_* + k_grid_place (grid.hip.h) counting sort of the current positions into cells with an edge >= the largest radius
+//  k_grid_slot_ids                                   the slot -> atom id map of that sort
+//  k_adf_neigh                                       neighbours of every central atom (lanes = (atom, slice of the candidates), grid_walk) and the
 //                                                    largest count with its atom id: the host sizes the tile from it and refuses a sample over the cap
 //  k_adf_triplets                                    per central atom: its neighbours gathered into an LDS tile (u, r2, species, fp64), the pairs of the tile
 //                                                    dealt to the atom's lanes, the bin by binary search over the edge table, uint32 sub-histogram in LDS
@@ -13,7 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cn.hip.h"
+#include "grid.hip.h"
 
 namespace aztot {
 
@@ -43,36 +43,8 @@ __device__ __forceinline__ void adf_stage_tables(AdfTables& T, const AdfTables* 
     for (int e = threadIdx.x; e < (int)(sizeof(AdfTables) / sizeof(int32_t)); e += kBlock) dst[e] = src[e];
 }
 
-// u = r_j - r_i after delta_periodic, and r2 = (ux*ux + uy*uy) + uz*uz with every operation rounded on its own: the rule of aztot_cn_sample
-__device__ __forceinline__ double adf_sep(const RdfGrid& G, double xi, double yi, double zi, double xj, double yj, double zj, double& ux, double& uy, double& uz)
-{
-    ux = xj - xi; uy = yj - yi; uz = zj - zi;
-    min_image(ux, G.L[0], G.half[0]);
-    min_image(uy, G.L[1], G.half[1]);
-    min_image(uz, G.L[2], G.half[2]);
-    return __dadd_rn(__dadd_rn(__dmul_rn(ux, ux), __dmul_rn(uy, uy)), __dmul_rn(uz, uz));
-}
-
-// the neighbour cells of cell (cx, cy, cz): 27, or each distinct one where an axis has fewer than 3; f(first slot, one past the last slot) per cell
-template <typename F> __device__ __forceinline__ void adf_cells(const RdfGrid& G, const int32_t* __restrict__ cellStart, int cx, int cy, int cz, F&& f)
-{
-    const int lo[3] = {G.nc[0] >= 3 ? -1 : 0, G.nc[1] >= 3 ? -1 : 0, G.nc[2] >= 3 ? -1 : 0};
-    const int hi[3] = {G.nc[0] >= 2 ? 1 : 0, G.nc[1] >= 2 ? 1 : 0, G.nc[2] >= 2 ? 1 : 0};
-    for (int dx = lo[0]; dx <= hi[0]; dx++)
-        for (int dy = lo[1]; dy <= hi[1]; dy++)
-            for (int dz = lo[2]; dz <= hi[2]; dz++)
-            {
-                int ex = cx + dx, ey = cy + dy, ez = cz + dz;
-                ex += ex < 0 ? G.nc[0] : (ex >= G.nc[0] ? -G.nc[0] : 0);
-                ey += ey < 0 ? G.nc[1] : (ey >= G.nc[1] ? -G.nc[1] : 0);
-                ez += ez < 0 ? G.nc[2] : (ez >= G.nc[2] ? -G.nc[2] : 0);
-                const int c = (ex * G.nc[1] + ey) * G.nc[2] + ez;
-                f(cellStart[c], cellStart[c + 1]);
-            }
-}
-
-// Neighbour count.  Lane t of the launch is (atom t >> sliceShift in slot order, slice t & (S - 1)), as in k_cn_pairs.  A neighbour of atom i (species g) is
-// an atom j != i with 0 < r2 < rowMax2[g] whose species is in ligMask[g].  neigh[slot] = the count, -1 where g is central to nothing.
+// Neighbour count: the lanes of SliceLane, the candidates of grid_walk.  A neighbour of atom i (species g) is an atom j != i with 0 < r2 < rowMax2[g]
+// (grid_sep's r2) whose species is in ligMask[g].  neigh[slot] = the count, -1 where g is central to nothing.
 // *summary = max over the central atoms of (count << 32 | atom id)
 __global__ __launch_bounds__(kBlock) void k_adf_neigh(RdfGrid G, const AdfTables* __restrict__ tab, int n, int sliceShift, const int32_t* __restrict__ cellStart,
                                                       const double* __restrict__ sx, const double* __restrict__ sy, const double* __restrict__ sz,
@@ -82,27 +54,20 @@ __global__ __launch_bounds__(kBlock) void k_adf_neigh(RdfGrid G, const AdfTables
     __shared__ AdfTables T;
     adf_stage_tables(T, tab);
     __syncthreads();
-    const int S = 1 << sliceShift;
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int i = (int)(t >> sliceShift), slice = (int)(t & (S - 1));
+    const SliceLane lane(sliceShift);
+    const int i = lane.i;
     const int gi = i < n ? sKind[i] & 255 : 0;
     const double rmx = i < n ? T.rowMax2[gi] : -1.0;
     int cnt = 0;
     if (rmx >= 0.0)
     {
-        const double xi = sx[i], yi = sy[i], zi = sz[i];
         const int mask = T.ligMask[gi];
-        adf_cells(G, cellStart, cell_coord(xi, G.icsz[0], G.nc[0]), cell_coord(yi, G.icsz[1], G.nc[1]), cell_coord(zi, G.icsz[2], G.nc[2]), [&](int s0, int s1) {
-            for (int j = s0 + slice; j < s1; j += S)
-            {
-                double ux, uy, uz;
-                const double r2 = adf_sep(G, xi, yi, zi, sx[j], sy[j], sz[j], ux, uy, uz);
-                cnt += (j != i && r2 > 0.0 && r2 < rmx && ((mask >> (sKind[j] & 255)) & 1)) ? 1 : 0;
-            }
-        });
+        grid_walk(G, cellStart, lane, sx[i], sy[i], sz[i], sx, sy, sz, [&](int j, double, double, double, double r2, int& acc) {
+            acc += (j != i && r2 > 0.0 && r2 < rmx && ((mask >> (sKind[j] & 255)) & 1)) ? 1 : 0;
+        }, cnt);
     }
-    for (int m = 1; m < S; m <<= 1) cnt += __shfl_xor(cnt, m);
-    const bool writer = i < n && slice == 0;
+    cnt = slice_fold(cnt, lane.S);
+    const bool writer = i < n && lane.slice == 0;
     if (writer) neigh[i] = rmx >= 0.0 ? cnt : -1;
     // one max per wave
     unsigned long long top = writer && rmx >= 0.0 ? ((unsigned long long)cnt << 32) | (unsigned int)slotId[i] : 0ull;
@@ -167,11 +132,11 @@ __global__ __launch_bounds__(kBlock) void k_adf_triplets(RdfGrid G, const AdfTab
         {
             const double xi = sx[i], yi = sy[i], zi = sz[i];
             const int mask = T.ligMask[gi];
-            adf_cells(G, cellStart, cell_coord(xi, G.icsz[0], G.nc[0]), cell_coord(yi, G.icsz[1], G.nc[1]), cell_coord(zi, G.icsz[2], G.nc[2]), [&](int s0, int s1) {
+            grid_cells(G, cellStart, cell_coord(xi, G.icsz[0], G.nc[0]), cell_coord(yi, G.icsz[1], G.nc[1]), cell_coord(zi, G.icsz[2], G.nc[2]), [&](int s0, int s1) {
                 for (int j = s0 + lane; j < s1; j += Gl)
                 {
                     double ux, uy, uz;
-                    const double r2 = adf_sep(G, xi, yi, zi, sx[j], sy[j], sz[j], ux, uy, uz);
+                    const double r2 = grid_sep(G, xi, yi, zi, sx[j], sy[j], sz[j], ux, uy, uz);
                     const int gj = sKind[j] & 255;
                     if (j != i && r2 > 0.0 && r2 < rmx && ((mask >> gj) & 1))
                     {

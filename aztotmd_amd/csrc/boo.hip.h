@@ -1,14 +1,13 @@
 // Bond-orientational order (Steinhardt q_l and the neighbour-averaged q-bar_l of Lechner and Dellago; aztot_boo_*, include/aztot.h) on the samplers' kind of
 // private cell grid.  The reference has no such output: the directive is ours.
 //
-//  k_rdf_bin + k_scan_* (rdf.hip.h)      cell and arrival rank of every atom, cells with an edge >= R
-//  k_cn_slot_ids + k_stress_rank         the arrival rank replaced by the rank of the atom's id among its cell-mates: slot order is a function of the state
-//  k_rdf_place + k_cn_slot_ids           positions and species in that order, and its slot -> id map
-//  k_boo_qlm<L>                          lanes = (atom, slice of the candidates) as k_adf_neigh; per bond one sqrt and one division, then the 2 (L + 1) sums
+//  k_boo_bin ... k_boo_place (grid.hip.h) the counting sort in its canonical order (Samplers::grid_fill_canonical), cells with an edge >= R: slot order is a
+//                                        function of the state; positions, species and the slot -> id map in that order
+//  k_boo_qlm<L>                          lanes = (atom, slice of the candidates), grid_walk; per bond one sqrt and one division, then the 2 (L + 1) sums
 //                                        of T_L^m(z) (x + i y)^m in registers; slices folded with lane exchanges; q_lm and n_i by slot
 //  k_boo_average<L>                      the same walk over the neighbours' q_lm by slot; q_l and q-bar_l by atom id
 //  k_boo_hist                            bins of the per-atom values: a uint32 sub-histogram in LDS flushed into the uint64 totals
-//  k_boo_chunks / k_boo_fold             the summation tree of the time correlation functions over the per-atom values in id order, per species
+//  k_boo_chunks / k_boo_fold             the summation tree over atom ids (kernels.hip.h) over the per-atom values, per species
 //
 // Harmonics without an angle.  With the unit vector (x, y, z) of a bond, sin^m(theta) e^(i m phi) = (x + i y)^m, and T_l^m(z) = P_l^m(z) / sin^m(theta) is a
 // polynomial in z: T_m^m = (-1)^m (2m - 1)!!, T_(m+1)^m = (2m + 1) z T_m^m, (l - m) T_l^m = (2l - 1) z T_(l-1)^m - (l + m - 1) T_(l-2)^m.  Nothing divides by
@@ -17,15 +16,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "adf.hip.h"
-#include "stress.hip.h"
+#include "grid.hip.h"
 
 namespace aztot {
 
 constexpr int kBooMaxL = 12, kBooMaxOrders = 4, kBooMaxBins = 4096;     // AZTOT_BOO_MAX_* of include/aztot.h
 constexpr int kBooMaxBlocks = 1024;         // k_boo_hist walks the ids grid-stride: at most this many LDS histograms are flushed per sample
 constexpr int kBooHistBudget = 32768;       // bytes of LDS k_boo_hist may take for its uint32 sub-histogram; beyond it: 64-bit global atomics
-constexpr int kBooChunk = kBlock;
 
 // what the kernels need of the set-up; norm and the rest are indexed at compile time only (kernel arguments: scalar registers)
 struct BooParams
@@ -80,48 +77,33 @@ template <int L> __device__ __forceinline__ double boo_invariant(const double (&
     return sqrt(scale * (s0 + 2.0 * sm));
 }
 
-// Bond sums.  Lane t of the launch is (atom t >> sliceShift in slot order, slice t & (S - 1)); every slice visits the neighbour cells in the order of
-// adf_cells and takes the candidates start + slice, + S, ... of each.  Slot order is canonical and S depends on N alone: the order of every sum is a
-// function of the sampled state.  A neighbour of a central atom i: j != i, species in ligandMask, 0 < r2 < R * R (adf_sep's r2).
+// Bond sums: the lanes of SliceLane, the candidates of grid_walk in its order.  Slot order is canonical and S depends on N alone: the order of every sum is
+// a function of the sampled state.  A neighbour of a central atom i: j != i, species in ligandMask, 0 < r2 < R * R (grid_sep's r2).
 //   nSlot[slot] = n_i (-1: not central);  qlm[slot * stride + at + 2 m + c] = N_lm * sum / n_i (0 where n_i <= 0)
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_boo_qlm(RdfGrid G, BooParams P, BooOrder O, int n, int sliceShift, const int32_t* __restrict__ cellStart,
                                                     const double* __restrict__ sx, const double* __restrict__ sy, const double* __restrict__ sz,
                                                     const int32_t* __restrict__ sKind, int32_t* __restrict__ nSlot, double* __restrict__ qlm)
 {
-    const int S = 1 << sliceShift;
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int i = (int)(t >> sliceShift), slice = (int)(t & (S - 1));
+    const SliceLane lane(sliceShift);
+    const int i = lane.i;
     const bool central = i < n && ((P.centralMask >> (sKind[i] & 255)) & 1);
     double acc[2 * (L + 1)];
 #pragma unroll
     for (int k = 0; k < 2 * (L + 1); k++) acc[k] = 0.0;
     int cnt = 0;
     if (central)
-    {
-        const double xi = sx[i], yi = sy[i], zi = sz[i];
-        adf_cells(G, cellStart, cell_coord(xi, G.icsz[0], G.nc[0]), cell_coord(yi, G.icsz[1], G.nc[1]), cell_coord(zi, G.icsz[2], G.nc[2]), [&](int s0, int s1) {
-            for (int j = s0 + slice; j < s1; j += S)
+        grid_walk(G, cellStart, lane, sx[i], sy[i], sz[i], sx, sy, sz, [&](int j, double ux, double uy, double uz, double r2) {
+            if (j != i && r2 > 0.0 && r2 < P.r2 && ((P.ligandMask >> (sKind[j] & 255)) & 1))
             {
-                double ux, uy, uz;
-                const double r2 = adf_sep(G, xi, yi, zi, sx[j], sy[j], sz[j], ux, uy, uz);
-                if (j != i && r2 > 0.0 && r2 < P.r2 && ((P.ligandMask >> (sKind[j] & 255)) & 1))
-                {
-                    const double inv = 1.0 / sqrt(r2);
-                    boo_add_bond<L>(acc, ux * inv, uy * inv, uz * inv);
-                    cnt++;
-                }
+                const double inv = 1.0 / sqrt(r2);
+                boo_add_bond<L>(acc, ux * inv, uy * inv, uz * inv);
+                cnt++;
             }
         });
-    }
-    // fold the slices of an atom (neighbouring lanes of one wave) in the fixed order 1, 2, 4, ...; lanes past the last atom take part with zeros
-    for (int m = 1; m < S; m <<= 1)
-    {
-#pragma unroll
-        for (int k = 0; k < 2 * (L + 1); k++) acc[k] += __shfl_xor(acc[k], m);
-        cnt += __shfl_xor(cnt, m);
-    }
-    if (i < n && slice == 0)
+    slice_fold(acc, lane.S);
+    cnt = slice_fold(cnt, lane.S);
+    if (i < n && lane.slice == 0)
     {
         nSlot[i] = central ? cnt : -1;
         double* q = qlm + (size_t)i * O.stride + O.at;
@@ -144,40 +126,27 @@ __global__ __launch_bounds__(kBlock) void k_boo_average(RdfGrid G, BooParams P, 
                                                         const int32_t* __restrict__ nSlot, const double* __restrict__ qlm, double* __restrict__ qCols,
                                                         int32_t* __restrict__ nById, int32_t* __restrict__ typeById)
 {
-    const int S = 1 << sliceShift;
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int i = (int)(t >> sliceShift), slice = (int)(t & (S - 1));
+    const SliceLane lane(sliceShift);
+    const int i = lane.i;
     const bool central = i < n && ((P.centralMask >> (sKind[i] & 255)) & 1);
     double acc[2 * (L + 1)];
 #pragma unroll
     for (int k = 0; k < 2 * (L + 1); k++) acc[k] = 0.0;
     int cnt = 0;
     if (central)
-    {
-        const double xi = sx[i], yi = sy[i], zi = sz[i];
-        adf_cells(G, cellStart, cell_coord(xi, G.icsz[0], G.nc[0]), cell_coord(yi, G.icsz[1], G.nc[1]), cell_coord(zi, G.icsz[2], G.nc[2]), [&](int s0, int s1) {
-            for (int j = s0 + slice; j < s1; j += S)
+        grid_walk(G, cellStart, lane, sx[i], sy[i], sz[i], sx, sy, sz, [&](int j, double, double, double, double r2) {
+            const int gj = sKind[j] & 255;
+            if (j != i && r2 > 0.0 && r2 < P.r2 && ((P.ligandMask >> gj) & 1) && ((P.centralMask >> gj) & 1))
             {
-                double ux, uy, uz;
-                const double r2 = adf_sep(G, xi, yi, zi, sx[j], sy[j], sz[j], ux, uy, uz);
-                const int gj = sKind[j] & 255;
-                if (j != i && r2 > 0.0 && r2 < P.r2 && ((P.ligandMask >> gj) & 1) && ((P.centralMask >> gj) & 1))
-                {
-                    const double* q = qlm + (size_t)j * O.stride + O.at;
+                const double* q = qlm + (size_t)j * O.stride + O.at;
 #pragma unroll
-                    for (int k = 0; k < 2 * (L + 1); k++) acc[k] += q[k];
-                    cnt++;
-                }
+                for (int k = 0; k < 2 * (L + 1); k++) acc[k] += q[k];
+                cnt++;
             }
         });
-    }
-    for (int m = 1; m < S; m <<= 1)
-    {
-#pragma unroll
-        for (int k = 0; k < 2 * (L + 1); k++) acc[k] += __shfl_xor(acc[k], m);
-        cnt += __shfl_xor(cnt, m);
-    }
-    if (i < n && slice == 0)
+    slice_fold(acc, lane.S);
+    cnt = slice_fold(cnt, lane.S);
+    if (i < n && lane.slice == 0)
     {
         const int id = slotId[i];
         if ((unsigned)id >= (unsigned)n) return;
@@ -232,13 +201,14 @@ __global__ __launch_bounds__(kBlock) void k_boo_hist(int n, int nOrders, int nSp
 }
 
 // Steps 1 and 2 of the tree for workgroup b (ids [256 b, 256 b + 256)), every column and species: the term of an id is its value where its species is s,
-// +0.0 elsewhere (the padding has species -1).  partials[(c * nSpec + s) * nChunkPad + b]
+// +0.0 elsewhere (the padding has species -1).  Step 3 is k_tree_fold's (kernels.hip.h), added to the running sums.
+//   partials[(c * nSpec + s) * nChunkPad + b]
 __global__ __launch_bounds__(kBlock) void k_boo_chunks(int nCols, int nSpec, size_t nPad, int nChunkPad, const double* __restrict__ qCols,
                                                        const int32_t* __restrict__ typeById, double* __restrict__ partials)
 {
     __shared__ double red[2 * kBooMaxOrders * kSpecCap][kBlock / kWave];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const size_t id = (size_t)blockIdx.x * kBooChunk + t;
+    const size_t id = (size_t)blockIdx.x * kTreeChunk + t;
     const int ty = typeById[id];
     for (int c = 0; c < nCols; c++)
     {
@@ -250,20 +220,7 @@ __global__ __launch_bounds__(kBlock) void k_boo_chunks(int nCols, int nSpec, siz
         }
     }
     __syncthreads();
-    if (t < nCols * nSpec) partials[(size_t)t * nChunkPad + blockIdx.x] = __dadd_rn(__dadd_rn(red[t][0], red[t][2]), __dadd_rn(red[t][1], red[t][3]));
-}
-
-// Step 3 of the tree for (column, species) blockIdx.x: the chunk sums (padded with +0.0 to nChunkPad, a power of two) folded by halving in place, then
-// added to the running sum
-__global__ __launch_bounds__(kBlock) void k_boo_fold(int nChunkPad, double* partials, double* __restrict__ sums)
-{
-    double* a = partials + (size_t)blockIdx.x * nChunkPad;
-    for (int h = nChunkPad >> 1; h > 0; h >>= 1)
-    {
-        for (int j = threadIdx.x; j < h; j += kBlock) a[j] = __dadd_rn(a[j], a[j + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = __dadd_rn(sums[blockIdx.x], a[0]);
+    if (t < nCols * nSpec) partials[(size_t)t * nChunkPad + blockIdx.x] = tree_wave4(red[t]);
 }
 
 }  // namespace aztot

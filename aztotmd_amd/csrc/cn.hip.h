@@ -2,10 +2,10 @@
 //
 //  reference                                   ours
 //  ------------------------------------------  -------------------------------------------------------------------------------
-//  out_cn / out_ncn: all N^2 (N^2 / 2) pairs    k_rdf_bin + k_scan_* + k_rdf_place (rdf.hip.h): counting sort of the current positions into cells with an
-//  on one host core after md_to_host            edge >= the largest radius; k_cn_slot_ids: the slot -> atom id map of that sort;
-//                                               k_cn_pairs: full-neighbour walk, lanes = (atom, slice of the candidates), counters in registers, slices
-//                                               folded with lane exchanges, one store per (atom, column), no atomics;
+//  out_cn / out_ncn: all N^2 (N^2 / 2) pairs    k_grid_bin + k_scan_* + k_grid_place (grid.hip.h): counting sort of the current positions into cells with an
+//  on one host core after md_to_host            edge >= the largest radius; k_grid_slot_ids: the slot -> atom id map of that sort;
+//                                               k_cn_pairs: full-neighbour walk (grid_walk), lanes = (atom, slice of the candidates), counters in registers,
+//                                               slices folded with lane exchanges, one store per (atom, column), no atomics;
 //                                               k_cn_range + k_cn_table: per-atom counts -> min / max and the uint64 table [cn][column] (integer atomics)
 //
 // A column is (central group, ligand group, R): groups are species (outCN) or nuclei (ncn).  Within one set-up a (central, ligand) pair names at most
@@ -14,25 +14,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "rdf.hip.h"
+#include "grid.hip.h"
 
 namespace aztot {
 
 constexpr int kCnMaxBlocks = 1024;          // k_cn_range / k_cn_table walk the atoms grid-stride
 constexpr int kCnLdsBudget = 32768;         // bytes of LDS k_cn_table may take for its uint32 sub-table
 
-// slot of every atom in the sorted order (the inverse is what a reader needs: atom id of each slot)
-__global__ __launch_bounds__(kBlock) void k_cn_slot_ids(AtomArrays A, int n, const int32_t* __restrict__ cellOf, const int32_t* __restrict__ rankOf,
-                                                        const int32_t* __restrict__ cellStart, int32_t* __restrict__ slotId)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    slotId[cellStart[cellOf[i]] + rankOf[i]] = A.id[i];
-}
-
-// Pair walk.  Lane t of the launch is (atom t >> sliceShift in slot order, slice t & (S - 1)), S = 1 << sliceShift <= 64 lanes of one wave per atom: every
-// slice visits all the neighbour cells (27, or each distinct one where an axis has fewer than 3) and takes the candidates start + slice, + S, ... of each,
-// so S = 1 is the one-thread-per-atom walk and S = 64 reads a cell's atoms as one coalesced row.  NL: counters kept (>= C.maxLive).
+// Pair walk: the lanes of SliceLane, the candidates of grid_walk (j == i among them: counted where C.countSelf).  NL: counters kept (>= C.maxLive).
 //   slotOf[g * kSpecCap + h]: counter of an atom of group g for a partner of group h, -1: no such column;  r2Of: R * R of that column;
 //   rowMax[g]: the largest R * R of g's columns (a cheap first test before the table is read), < 0: g is central to nothing
 template <int NL>
@@ -47,9 +36,8 @@ __global__ __launch_bounds__(kBlock) void k_cn_pairs(RdfGrid G, CnParams C, int 
     for (int e = threadIdx.x; e < kSpecCap * kSpecCap; e += kBlock) { sSlot[e] = slotOf[e]; sR2[e] = r2Of[e]; }
     if (threadIdx.x < kSpecCap) sRowMax[threadIdx.x] = rowMax[threadIdx.x];
     __syncthreads();
-    const int S = 1 << sliceShift;
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int i = (int)(t >> sliceShift), slice = (int)(t & (S - 1));
+    const SliceLane lane(sliceShift);
+    const int i = lane.i;
     int cnt[NL];
 #pragma unroll
     for (int k = 0; k < NL; k++) cnt[k] = 0;
@@ -57,50 +45,22 @@ __global__ __launch_bounds__(kBlock) void k_cn_pairs(RdfGrid G, CnParams C, int 
     const double rmx = i < n ? sRowMax[gi] : -1.0;
     if (rmx >= 0.0)
     {
-        const int lo[3] = {G.nc[0] >= 3 ? -1 : 0, G.nc[1] >= 3 ? -1 : 0, G.nc[2] >= 3 ? -1 : 0};
-        const int hi[3] = {G.nc[0] >= 2 ? 1 : 0, G.nc[1] >= 2 ? 1 : 0, G.nc[2] >= 2 ? 1 : 0};
-        const double xi = sx[i], yi = sy[i], zi = sz[i];
-        const int cx = cell_coord(xi, G.icsz[0], G.nc[0]), cy = cell_coord(yi, G.icsz[1], G.nc[1]), cz = cell_coord(zi, G.icsz[2], G.nc[2]);
         const int32_t* rowSlot = sSlot + gi * kSpecCap;
         const double* rowR2 = sR2 + gi * kSpecCap;
-        for (int dx = lo[0]; dx <= hi[0]; dx++)
-            for (int dy = lo[1]; dy <= hi[1]; dy++)
-                for (int dz = lo[2]; dz <= hi[2]; dz++)
-                {
-                    int ex = cx + dx, ey = cy + dy, ez = cz + dz;
-                    ex += ex < 0 ? G.nc[0] : (ex >= G.nc[0] ? -G.nc[0] : 0);
-                    ey += ey < 0 ? G.nc[1] : (ey >= G.nc[1] ? -G.nc[1] : 0);
-                    ez += ez < 0 ? G.nc[2] : (ez >= G.nc[2] ? -G.nc[2] : 0);
-                    const int c = (ex * G.nc[1] + ey) * G.nc[2] + ez;
-                    const int s1 = cellStart[c + 1];
-                    for (int j = cellStart[c] + slice; j < s1; j += S)
-                    {
-                        if (j == i && !C.countSelf) continue;
-                        // fp64 without contraction: the same rounding as the host's (dx*dx + dy*dy) + dz*dz on the delta_periodic differences (box.cpp:297-305)
-                        double ddx = xi - sx[j], ddy = yi - sy[j], ddz = zi - sz[j];
-                        min_image(ddx, G.L[0], G.half[0]);
-                        min_image(ddy, G.L[1], G.half[1]);
-                        min_image(ddz, G.L[2], G.half[2]);
-                        const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)), __dmul_rn(ddz, ddz));
-                        if (r2 <= rmx)
-                        {
-                            const int gj = (sKind[j] >> C.shift) & 255;
-                            const int k = rowSlot[gj];
-                            const double R2 = rowR2[gj];
-                            const bool hit = k >= 0 && (C.inclusive ? R2 >= r2 : r2 < R2);
+        grid_walk(G, cellStart, lane, sx[i], sy[i], sz[i], sx, sy, sz, [&](int j, double, double, double, double r2, int (&acc)[NL]) {
+            if (r2 <= rmx && (j != i || C.countSelf))
+            {
+                const int gj = (sKind[j] >> C.shift) & 255;
+                const int k = rowSlot[gj];
+                const double R2 = rowR2[gj];
+                const bool hit = k >= 0 && (C.inclusive ? R2 >= r2 : r2 < R2);
 #pragma unroll
-                            for (int q = 0; q < NL; q++) cnt[q] += (hit && q == k) ? 1 : 0;
-                        }
-                    }
-                }
+                for (int q = 0; q < NL; q++) acc[q] += (hit && q == k) ? 1 : 0;
+            }
+        }, cnt);
     }
-    // fold the slices of an atom (neighbouring lanes of one wave) in a fixed order; lanes past the last atom take part with zeros
-    for (int m = 1; m < S; m <<= 1)
-    {
-#pragma unroll
-        for (int q = 0; q < NL; q++) cnt[q] += __shfl_xor(cnt[q], m);
-    }
-    if (i < n && slice == 0)
+    slice_fold(cnt, lane.S);
+    if (i < n && lane.slice == 0)
     {
 #pragma unroll
         for (int q = 0; q < NL; q++)

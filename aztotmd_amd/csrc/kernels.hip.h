@@ -36,6 +36,27 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// The tree-ordered sum over atom ids of the samplers (include/aztot.h): a workgroup holds kTreeChunk consecutive ids, lane l of wave w the id 64 w + l of
+// them.  Step 1 is wave_sum over a run of 64 ids (strides 32 ... 1), step 2 tree_wave4 over the four runs, step 3 tree_fold over the chunk sums.
+constexpr int kTreeChunk = kBlock;
+__device__ __forceinline__ double tree_wave4(const double r[4]) { return __dadd_rn(__dadd_rn(r[0], r[2]), __dadd_rn(r[1], r[3])); }
+// a[0 ... nChunkPad): the chunk sums padded with +0.0 to a power of two, folded by halving in place by the whole workgroup; result valid in thread 0
+__device__ __forceinline__ double tree_fold(double* a, int nChunkPad)
+{
+    for (int h = nChunkPad >> 1; h > 0; h >>= 1)
+    {
+        for (int j = threadIdx.x; j < h; j += kBlock) a[j] = __dadd_rn(a[j], a[j + h]);
+        __syncthreads();
+    }
+    return threadIdx.x == 0 ? a[0] : 0.0;
+}
+// step 3 for column blockIdx.x of partials[column * nChunkPad + chunk]: stored (accumulate == 0) or added to the running sum out[column]
+__global__ __launch_bounds__(kBlock) void k_tree_fold(int nChunkPad, int accumulate, double* partials, double* __restrict__ out)
+{
+    const double sum = tree_fold(partials + (size_t)blockIdx.x * nChunkPad, nChunkPad);
+    if (threadIdx.x == 0) out[blockIdx.x] = accumulate ? __dadd_rn(out[blockIdx.x], sum) : sum;
+}
+
 // sum over the workgroup; result valid in thread 0. `scratch` holds blockDim/64 doubles.
 __device__ __forceinline__ double block_sum(double v, double* scratch)
 {

@@ -2,7 +2,7 @@
 //
 //  reference                                   ours
 //  ------------------------------------------  -------------------------------------------------------------------------------
-//  brute_rdf / brute_nrdf: all N^2/2 pairs,     k_rdf_bin + k_scan_* + k_rdf_place: counting sort of the current positions into a
+//  brute_rdf / brute_nrdf: all N^2/2 pairs,     k_grid_bin + k_scan_* + k_grid_place (grid.hip.h): counting sort of the current positions into a
 //  float atomics into a float histogram         grid of cells with edge >= rmax (its own, not the engine's: those are stale by up
 //                                               to the skin and sized for the force cut-off);
 //                                               k_rdf_pairs: half-shell walk over that grid, fp64 distances, uint32 sub-histograms
@@ -13,54 +13,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels.hip.h"
+#include "grid.hip.h"
 
 namespace aztot {
 
 constexpr int kRdfMaxBlocks = 1024;         // k_rdf_pairs walks the atoms grid-stride: at most this many LDS histograms are flushed per sample
 constexpr int kRdfLdsBudget = 65536;        // bytes of LDS k_rdf_pairs may take for its sub-histograms (one per wave where they fit, else one per workgroup)
-
-__device__ __forceinline__ int rdf_cell(const RdfGrid& G, double x, double y, double z)
-{
-    return (cell_coord(x, G.icsz[0], G.nc[0]) * G.nc[1] + cell_coord(y, G.icsz[1], G.nc[1])) * G.nc[2] + cell_coord(z, G.icsz[2], G.nc[2]);
-}
-
-// position as aztot_md_to_host hands it out: a lazy run keeps coordinates unwrapped between two sorts (put_periodic, box.cpp:230-295)
-__device__ __forceinline__ void rdf_wrapped(const RdfGrid& G, const AtomArrays& A, int i, double& x, double& y, double& z)
-{
-    x = A.x[i]; y = A.y[i]; z = A.z[i];
-    wrap_coord(x, G.L[0], G.invL[0]);
-    wrap_coord(y, G.L[1], G.invL[1]);
-    wrap_coord(z, G.L[2], G.invL[2]);
-}
-
-// pass 1 of the counting sort: cell of every atom and its arrival rank inside the cell
-__global__ __launch_bounds__(kBlock) void k_rdf_bin(RdfGrid G, AtomArrays A, int n, int32_t* __restrict__ cellOf, int32_t* __restrict__ rankOf,
-                                                    int32_t* __restrict__ cellCount)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    double x, y, z;
-    rdf_wrapped(G, A, i, x, y, z);
-    const int c = rdf_cell(G, x, y, z);
-    cellOf[i] = c;
-    rankOf[i] = atomicAdd(&cellCount[c], 1);
-}
-
-// pass 2: wrapped position and (species | nucleus << 8) of every atom at its slot of the grid
-__global__ __launch_bounds__(kBlock) void k_rdf_place(RdfGrid G, AtomArrays A, int n, const int32_t* __restrict__ cellOf, const int32_t* __restrict__ rankOf,
-                                                      const int32_t* __restrict__ cellStart, double* __restrict__ sx, double* __restrict__ sy,
-                                                      double* __restrict__ sz, int32_t* __restrict__ sKind)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    double x, y, z;
-    rdf_wrapped(G, A, i, x, y, z);
-    const int s = cellStart[cellOf[i]] + rankOf[i];
-    const int t = A.type[i];
-    sx[s] = x; sy[s] = y; sz[s] = z;
-    sKind[s] = t | (G.nucl[t] << 8);
-}
 
 __device__ __forceinline__ int rdf_pair(int a, int b, int n)
 {   // iPair = mn * (n - 1) + mn * (1 - mn) / 2 + mx (cuStat.cu:479-486)

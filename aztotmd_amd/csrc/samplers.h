@@ -1,7 +1,15 @@
-// The samplers of one rank: radial distribution functions (rdf.hip.h), coordination numbers (cn.hip.h), time correlation functions (tcf.hip.h), the
-// pressure tensor (stress.hip.h), bond-angle distributions (adf.hip.h), static structure factors (sk.hip.h) and bond-orientational order (boo.hip.h) behind
-// aztot_rdf_* / aztot_cn_* / aztot_tcf_* / aztot_stress_* / aztot_adf_* / aztot_sk_* / aztot_boo_* of include/aztot.h.  Each owns its device buffers and its running totals; none of it is scheduling, so none of it
-// is Engine's.  Host-only; the bodies are in samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
+// The samplers of one rank, behind the aztot_<name>_* calls of include/aztot.h:
+//   rdf     radial distribution functions     rdf.hip.h
+//   cn      coordination numbers              cn.hip.h
+//   tcf     time correlation functions        tcf.hip.h
+//   stress  pressure tensor                   stress.hip.h
+//   adf     bond-angle distributions          adf.hip.h
+//   sk      static structure factors          sk.hip.h
+//   boo     bond-orientational order          boo.hip.h
+// What several of them share - the private cell grid, its canonical order and the sliced neighbour walk - is in grid.hip.h; the tree-ordered sum over
+// atom ids is next to wave_sum in kernels.hip.h.
+// Each sampler owns its device buffers and its running totals; none of it is scheduling, so none of it is Engine's.  Host-only; the bodies are in
+// samplers.hip.h, included by engine.hip, the one translation unit that sees the kernels.
 //
 // The contract.  A sample is launched on the engine's stream between two aztot_step calls, never inside a captured step.  It reads the current per-atom
 // arrays - the configuration as aztot_md_to_host would return it: the deferred end of the last aztot_step call has happened - and writes only the samplers'
@@ -104,8 +112,8 @@ public:
     void boo_values(std::vector<double>& centre, std::vector<double>& density, std::vector<double>& mean);     // [bin], hist's layout, sums' layout
 
 private:
-    // a private cell grid over the current positions and the buffers of its counting sort (k_rdf_bin / k_scan_* / k_rdf_place): the RDF sampler has one,
-    // each coordination-number set-up has one (different cell edges)
+    // a private cell grid over the current positions and the buffers of its counting sort (k_grid_bin / k_scan_* / k_grid_place): every sampler that looks
+    // at pairs has its own, each coordination-number set-up has one (different cell edges)
     struct GridSort
     {
         DeviceArena mem;
@@ -114,6 +122,21 @@ private:
         Counts* scanCounts = nullptr;   // what k_scan_apply / k_scan_single write besides the offsets goes here, not into the engine's Counts / DevStats
         DevStats* scanStats = nullptr;
         RdfGrid grid{};
+    };
+    // ... filled in the canonical order (cells by position, ids ascending inside a cell): the slot order is a function of the sampled state alone
+    struct CanonGrid : GridSort
+    {
+        int32_t *arrivalId = nullptr, *canonRank = nullptr;     // slot -> id map of the arrival order, rank of every atom's id among its cell-mates
+        int32_t* slotId = nullptr;                              // slot -> id map of the canonical order, -1 until a sample writes it
+    };
+    // the sizes of the tree-ordered sum over the atom ids (kernels.hip.h): chunks of kTreeChunk ids, their number padded to a power of two, the ids padded
+    // to whole chunks
+    struct IdTree
+    {
+        int nChunk = 0, nChunkPad = 0;
+        size_t nPad = 0;
+        IdTree() = default;
+        explicit IdTree(int N);
     };
     struct RdfState : GridSort
     {
@@ -144,8 +167,8 @@ private:
     {
         int M = 0, E = 0;               // origins in the ring and samples between two of them; M == 0: not set up
         long long samples = 0;          // since the set-up or the last reset
-        int nSpec = 0, nChunk = 0, nChunkPad = 0;
-        size_t nPad = 0;                // ids padded to a multiple of kTcfChunk
+        int nSpec = 0;
+        IdTree tree;
         DeviceArena mem;
         double *cur = nullptr, *ring = nullptr, *partials = nullptr, *msdSum = nullptr, *vafSum = nullptr;
         int32_t* type = nullptr;        // species by atom id, -1 in the padding
@@ -154,12 +177,12 @@ private:
     };
 
     // per-atom columns by atom id (StressCol), their chunk sums and totals; the grid carries the canonical in-cell order
-    struct StressState : GridSort
+    struct StressState : CanonGrid
     {
         bool isSetUp = false, sampled = false;
-        int sliceShift = 0, nChunk = 0, nChunkPad = 0;
-        size_t nPad = 0;
-        int32_t *arrivalId = nullptr, *canonRank = nullptr, *slotId = nullptr, *visits = nullptr, *drops = nullptr;
+        int sliceShift = 0;
+        IdTree tree;
+        int32_t *visits = nullptr, *drops = nullptr;
         double *rad = nullptr, *cols = nullptr, *partials = nullptr, *totals = nullptr;
         unsigned long long* counters = nullptr;
         long long step = 0;             // of the last sample
@@ -199,15 +222,16 @@ private:
     };
 
     // the set-up with its host-made tables, q_lm and n in canonical slot order, per-atom values by atom id, their chunk sums, totals over the samples
-    struct BooState : GridSort
+    struct BooState : CanonGrid
     {
         int nBins = 0;                  // 0: not set up
         aztot_boo_params par{};
         long long samples = 0;
         bool sampled = false;           // the per-atom values of a sample are there
-        int nSpec = 0, stride = 0, sliceShift = 0, nChunk = 0, nChunkPad = 0, useLds = 0;
-        size_t nPad = 0, nHist = 0;     // ids padded to a multiple of 256; histogram cells (the entered counts follow them)
-        int32_t *arrivalId = nullptr, *canonRank = nullptr, *slotId = nullptr, *nSlot = nullptr, *nById = nullptr, *typeById = nullptr;
+        int nSpec = 0, stride = 0, sliceShift = 0, useLds = 0;
+        IdTree tree;
+        size_t nHist = 0;               // histogram cells (the entered counts follow them)
+        int32_t *nSlot = nullptr, *nById = nullptr, *typeById = nullptr;
         double *qlm = nullptr, *qCols = nullptr, *partials = nullptr, *sums = nullptr;
         unsigned long long* totals = nullptr;
     };
@@ -222,6 +246,11 @@ private:
     void grid_setup(GridSort& S, double edge);                                              // cells with an edge >= `edge`, at most about N of them; allocates the sort's buffers
     void grid_fill(GridSort& S, const AtomArrays& A, const char* const timerNames[3]);      // bin, scan, place the positions of A (timer names of the three stages)
     void grid_count(GridSort& S, const AtomArrays& A, const char* const timerNames[2]);     // ... the first two: cell, arrival rank and cell offsets
+    void canon_setup(CanonGrid& S, double edge);                                            // grid_setup and the buffers of the canonical order
+    // bin, scan, ids, rank, place: grid_fill in the canonical order (timer names of the five stages); slotIds: the place stage also writes S.slotId
+    void grid_fill_canonical(CanonGrid& S, const AtomArrays& A, const char* const timerNames[5], bool slotIds);
+    int lanes_shift() const;                                                                // log2 of the lanes per atom of a sliced walk (SliceLane)
+    int lane_blocks(int shift) const;                                                       // workgroups of a launch with that many lanes per atom
     RdfState& rdf_state();
     CnState& cn_state(int kind, bool needSetup, bool needSample);
     TcfState& tcf_state();

@@ -66,7 +66,7 @@ Samplers::CnState& Samplers::cn_state(int kind, bool needSetup, bool needSample)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The private cell grid of the RDF and coordination-number samplers
+// The private cell grid of the samplers that look at pairs (grid.hip.h), their lanes, and the sizes of the sum tree
 // ---------------------------------------------------------------------------------------------------
 // cells with an edge >= `edge` (a hair more: the cell of a coordinate is floor(x * nc / L) in fp64), at most about N of them (a dilute gas in a large box
 // would otherwise get mostly empty cells); the buffers of the counting sort.  Histogram fields of the grid are the caller's.
@@ -105,7 +105,7 @@ void Samplers::grid_count(GridSort& S, const AtomArrays& A, const char* const ti
     const RdfGrid& G = S.grid;
     const int N = model_.nAt;
     const int nb = div_up(N, kBlock);
-    timed(timerNames[0], [&] { hipLaunchKernelGGL(k_rdf_bin, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellCount); });
+    timed(timerNames[0], [&] { hipLaunchKernelGGL(k_grid_bin, dim3(nb), dim3(kBlock), 0, stream_, G, A, N, S.cellOf, S.rankOf, S.cellCount); });
     if (G.nCell <= kScanSingleMax)
         timed(timerNames[1], [&] { hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, G.nCell, S.cellCount, S.cellStart, S.scanCounts, S.scanStats, 0); });
     else
@@ -122,8 +122,46 @@ void Samplers::grid_fill(GridSort& S, const AtomArrays& A, const char* const tim
     const int N = model_.nAt;
     grid_count(S, A, timerNames);
     timed(timerNames[2], [&] {
-        hipLaunchKernelGGL(k_rdf_place, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.rankOf, S.cellStart, S.x, S.y, S.z, S.kind);
+        hipLaunchKernelGGL(k_grid_place, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.rankOf, S.cellStart, S.x, S.y, S.z, S.kind);
     });
+}
+
+void Samplers::canon_setup(CanonGrid& S, double edge)
+{
+    grid_setup(S, edge);
+    const size_t n = (size_t)std::max(model_.nAt, 1);
+    S.arrivalId = S.mem.alloc<int32_t>(n, false, stream_); S.canonRank = S.mem.alloc<int32_t>(n, false, stream_);
+    S.slotId = S.mem.alloc<int32_t>(n, false, stream_);
+    HIP_CHECK(hipMemsetAsync(S.slotId, 0xff, sizeof(int32_t) * n, stream_));
+}
+
+// the counting sort with the arrival rank k_grid_bin hands out replaced by the rank of the atom's id among its cell-mates
+void Samplers::grid_fill_canonical(CanonGrid& S, const AtomArrays& A, const char* const timerNames[5], bool slotIds)
+{
+    const int N = model_.nAt, nb = div_up(N, kBlock);
+    grid_count(S, A, timerNames);
+    timed(timerNames[2], [&] { hipLaunchKernelGGL(k_grid_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.arrivalId); });
+    timed(timerNames[3], [&] { hipLaunchKernelGGL(k_grid_canon_rank, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.cellStart, S.arrivalId, S.canonRank); });
+    timed(timerNames[4], [&] {
+        hipLaunchKernelGGL(k_grid_place, dim3(nb), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.canonRank, S.cellStart, S.x, S.y, S.z, S.kind);
+        if (slotIds) hipLaunchKernelGGL(k_grid_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.canonRank, S.cellStart, S.slotId);
+    });
+}
+
+// Lanes per atom of a sliced walk: enough of them that a small system still fills the chip (256 CUs x 4 waves of 64 at the least), never more than one wave.
+// A function of N alone, so that the order of every per-atom sum is one too.
+int Samplers::lanes_shift() const
+{
+    int shift = 0;
+    while (shift < 6 && ((long long)std::max(model_.nAt, 1) << shift) < 65536) shift++;
+    return shift;
+}
+
+int Samplers::lane_blocks(int shift) const { return (int)((((long long)model_.nAt << shift) + kBlock - 1) / kBlock); }
+
+Samplers::IdTree::IdTree(int N) : nChunk(std::max(1, div_up(N, kTreeChunk))), nChunkPad(1), nPad((size_t)nChunk * kTreeChunk)
+{
+    while (nChunkPad < nChunk) nChunkPad <<= 1;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -263,9 +301,8 @@ void Samplers::cn_setup(int kind, const aztot_cn_column* cols, int nCols)
     T.par.inclusive = kind == AZTOT_CN_SPECIES ? 1 : 0;
     T.par.countSelf = kind == AZTOT_CN_SPECIES ? 1 : 0;
     T.par.nCols = nCols;
-    // lanes per atom: enough of them that a small system still fills the chip (256 CUs x 4 waves of 64 at the least), never more than one wave
     const int N = model_.nAt;
-    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    T.sliceShift = lanes_shift();
     T.rowsCap = 64;
     set_up(cn_[kind], T, [&] {
         CnState& S = T;
@@ -307,8 +344,8 @@ void Samplers::cn_sample(int kind)
         static const char* const names[3] = {"k_cn_bin", "k_cn_scan", "k_cn_place"};
         grid_fill(S, A, names);
         const int nb = div_up(N, kBlock);
-        timed("k_cn_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId); });
-        const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
+        timed("k_cn_ids", [&] { hipLaunchKernelGGL(k_grid_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId); });
+        const int blocks = lane_blocks(S.sliceShift);
         timed("k_cn_pairs", [&] {
             auto go = [&](auto nl) {
                 launch_cn_pairs<decltype(nl)::value>(stream_, blocks, S.grid, C, N, S.sliceShift, S.cellStart, S.x, S.y, S.z, S.kind, S.dSlotOf, S.dR2Of, S.dRowMax, S.counts);
@@ -389,17 +426,14 @@ int Samplers::tcf_setup(int nOrigins, int originEvery)
     if ((long long)nOrigins * originEvery > AZTOT_TCF_MAX_LAGS) throw ArgError("tcf: too many lags (n_origins x origin_every > 2^24)");
     TcfState T;
     T.M = nOrigins; T.E = originEvery; T.nSpec = model_.nSpec();
-    T.nChunk = std::max(1, div_up(model_.nAt, kTcfChunk));
-    T.nChunkPad = 1;
-    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
-    T.nPad = (size_t)T.nChunk * kTcfChunk;
+    T.tree = IdTree(model_.nAt);
     set_up(tcf_, T, [&] {
-        const size_t nAcc = (size_t)T.n_lags() * T.nSpec;
-        T.cur = T.mem.alloc<double>(6 * T.nPad, true, stream_);
-        T.ring = T.mem.alloc<double>((size_t)T.M * 6 * T.nPad, true, stream_);
-        T.type = T.mem.alloc<int32_t>(T.nPad, false, stream_);
-        HIP_CHECK(hipMemsetAsync(T.type, 0xff, sizeof(int32_t) * T.nPad, stream_));
-        T.partials = T.mem.alloc<double>((size_t)T.M * 2 * T.nSpec * T.nChunkPad, true, stream_);
+        const size_t nAcc = (size_t)T.n_lags() * T.nSpec, nPad = T.tree.nPad;
+        T.cur = T.mem.alloc<double>(6 * nPad, true, stream_);
+        T.ring = T.mem.alloc<double>((size_t)T.M * 6 * nPad, true, stream_);
+        T.type = T.mem.alloc<int32_t>(nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.type, 0xff, sizeof(int32_t) * nPad, stream_));
+        T.partials = T.mem.alloc<double>((size_t)T.M * 2 * T.nSpec * T.tree.nChunkPad, true, stream_);
         T.msdSum = T.mem.alloc<double>(nAcc, true, stream_); T.vafSum = T.mem.alloc<double>(nAcc, true, stream_);
         T.count = T.mem.alloc<long long>((size_t)T.n_lags(), true, stream_);
     });
@@ -423,18 +457,19 @@ void Samplers::tcf_sample()
     sample("tcf kernels", [&](const AtomArrays& A) {
         const int N = model_.nAt;
         const long long c = T.samples;
+        const IdTree& tree = T.tree;
         TcfBox B;
         for (int k = 0; k < 3; k++) { B.L[k] = box_.L[k]; B.invL[k] = box_.invL[k]; B.half[k] = box_.half[k]; }
         const bool isOrigin = c % T.E == 0;
-        double* org = isOrigin ? T.ring + (size_t)((c / T.E) % T.M) * 6 * T.nPad : nullptr;
+        double* org = isOrigin ? T.ring + (size_t)((c / T.E) % T.M) * 6 * tree.nPad : nullptr;
         if (N > 0)
-            timed("k_tcf_gather", [&] { hipLaunchKernelGGL(k_tcf_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, B, A, N, T.nPad, T.cur, org, T.type); });
+            timed("k_tcf_gather", [&] { hipLaunchKernelGGL(k_tcf_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, B, A, N, tree.nPad, T.cur, org, T.type); });
         const int nLive = (int)std::min<long long>(c / T.E + 1, T.M);
         timed("k_tcf_correlate", [&] {
-            hipLaunchKernelGGL(k_tcf_correlate, dim3(T.nChunk), dim3(kBlock), 0, stream_, B, T.nSpec, T.nPad, T.nChunkPad, nLive, T.cur, T.type, T.ring, T.partials);
+            hipLaunchKernelGGL(k_tcf_correlate, dim3(tree.nChunk), dim3(kBlock), 0, stream_, B, T.nSpec, tree.nPad, tree.nChunkPad, nLive, T.cur, T.type, T.ring, T.partials);
         });
         timed("k_tcf_fold", [&] {
-            hipLaunchKernelGGL(k_tcf_fold, dim3(nLive * 2 * T.nSpec), dim3(kBlock), 0, stream_, T.nSpec, T.nChunkPad, c, T.E, T.M, T.partials, T.count, T.msdSum, T.vafSum);
+            hipLaunchKernelGGL(k_tcf_fold, dim3(nLive * 2 * T.nSpec), dim3(kBlock), 0, stream_, T.nSpec, tree.nChunkPad, c, T.E, T.M, T.partials, T.count, T.msdSum, T.vafSum);
         });
     });
     T.samples++;
@@ -489,22 +524,16 @@ void Samplers::stress_setup()
     StressState T;
     const int N = model_.nAt;
     T.isSetUp = true;
-    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
-    T.nChunk = std::max(1, div_up(N, kStressChunk));
-    T.nChunkPad = 1;
-    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
-    T.nPad = (size_t)T.nChunk * kStressChunk;
+    T.sliceShift = lanes_shift();
+    T.tree = IdTree(N);
     set_up(stress_, T, [&] {
         const double biggest = std::max(box_.L[0], std::max(box_.L[1], box_.L[2]));
-        grid_setup(T, model_.rMax > 0.0 ? model_.rMax : biggest);
-        const size_t n = (size_t)std::max(N, 1);
-        T.arrivalId = T.mem.alloc<int32_t>(n, false, stream_); T.canonRank = T.mem.alloc<int32_t>(n, false, stream_);
-        T.slotId = T.mem.alloc<int32_t>(n, false, stream_);
-        HIP_CHECK(hipMemsetAsync(T.slotId, 0xff, sizeof(int32_t) * n, stream_));
+        canon_setup(T, model_.rMax > 0.0 ? model_.rMax : biggest);
+        const size_t n = (size_t)std::max(N, 1), nPad = T.tree.nPad;
         T.rad = T.mem.alloc<double>(n, true, stream_);
-        T.cols = T.mem.alloc<double>((size_t)SC_COUNT * T.nPad, true, stream_);
-        T.visits = T.mem.alloc<int32_t>(T.nPad, true, stream_); T.drops = T.mem.alloc<int32_t>(T.nPad, true, stream_);
-        T.partials = T.mem.alloc<double>((size_t)SC_COUNT * T.nChunkPad, true, stream_);
+        T.cols = T.mem.alloc<double>((size_t)SC_COUNT * nPad, true, stream_);
+        T.visits = T.mem.alloc<int32_t>(nPad, true, stream_); T.drops = T.mem.alloc<int32_t>(nPad, true, stream_);
+        T.partials = T.mem.alloc<double>((size_t)SC_COUNT * T.tree.nChunkPad, true, stream_);
         T.totals = T.mem.alloc<double>(SC_COUNT, true, stream_);
         T.counters = T.mem.alloc<unsigned long long>(2, true, stream_);
     });
@@ -516,34 +545,27 @@ void Samplers::stress_sample()
     sample("stress kernels", [&](const AtomArrays& A) {
         const PairTables E = host_.pair_tables();
         const int N = model_.nAt;
+        const IdTree& tree = T.tree;
         T.sampled = false;
         T.step = E.step;
         HIP_CHECK(hipMemsetAsync(T.counters, 0, 2 * sizeof(unsigned long long), stream_));
         if (N > 0)
         {
-            static const char* const names[2] = {"k_stress_bin", "k_stress_scan"};
-            grid_count(T, A, names);
-            const int nb = div_up(N, kBlock);
-            // arrival order -> ids ascending inside every cell
-            timed("k_stress_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, T.cellOf, T.rankOf, T.cellStart, T.arrivalId); });
-            timed("k_stress_rank", [&] { hipLaunchKernelGGL(k_stress_rank, dim3(nb), dim3(kBlock), 0, stream_, A, N, T.cellOf, T.cellStart, T.arrivalId, T.canonRank); });
-            timed("k_stress_place", [&] {
-                hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, T.grid, A, N, T.cellOf, T.canonRank, T.cellStart, T.x, T.y, T.z, T.kind);
-            });
+            static const char* const names[5] = {"k_stress_bin", "k_stress_scan", "k_stress_ids", "k_stress_rank", "k_stress_place"};
+            grid_fill_canonical(T, A, names, false);     // (the slot -> id map is k_stress_gather's)
             timed("k_stress_gather", [&] {
-                hipLaunchKernelGGL(k_stress_gather, dim3(nb), dim3(kBlock), 0, stream_, E.S, A, N, (int)E.P.use_radii, T.nPad, T.cellOf, T.canonRank, T.cellStart, T.slotId,
-                                   T.rad, T.cols);
+                hipLaunchKernelGGL(k_stress_gather, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream_, E.S, A, N, (int)E.P.use_radii, tree.nPad, T.cellOf, T.canonRank,
+                                   T.cellStart, T.slotId, T.rad, T.cols);
             });
-            const int blocks = (int)((((long long)N << T.sliceShift) + kBlock - 1) / kBlock);
             timed("k_stress_pairs", [&] {
-                hipLaunchKernelGGL(k_stress_pairs, dim3(blocks), dim3(kBlock), 0, stream_, T.grid, E.P, E.S, E.pots, N, T.sliceShift, T.nPad, T.cellStart, T.x, T.y, T.z,
-                                   T.kind, T.rad, T.slotId, T.cols, T.visits, T.drops);
+                hipLaunchKernelGGL(k_stress_pairs, dim3(lane_blocks(T.sliceShift)), dim3(kBlock), 0, stream_, T.grid, E.P, E.S, E.pots, N, T.sliceShift, tree.nPad,
+                                   T.cellStart, T.x, T.y, T.z, T.kind, T.rad, T.slotId, T.cols, T.visits, T.drops);
             });
         }
         timed("k_stress_chunks", [&] {
-            hipLaunchKernelGGL(k_stress_chunks, dim3(T.nChunk), dim3(kBlock), 0, stream_, T.nPad, T.nChunkPad, T.cols, T.visits, T.drops, T.partials, T.counters);
+            hipLaunchKernelGGL(k_stress_chunks, dim3(tree.nChunk), dim3(kBlock), 0, stream_, tree.nPad, tree.nChunkPad, T.cols, T.visits, T.drops, T.partials, T.counters);
         });
-        timed("k_stress_fold", [&] { hipLaunchKernelGGL(k_stress_fold, dim3(SC_COUNT), dim3(kBlock), 0, stream_, T.nChunkPad, T.partials, T.totals); });
+        timed("k_stress_fold", [&] { hipLaunchKernelGGL(k_tree_fold, dim3(SC_COUNT), dim3(kBlock), 0, stream_, tree.nChunkPad, 0, T.partials, T.totals); });
     });
     T.sampled = true;
 }
@@ -581,7 +603,7 @@ void Samplers::stress_per_atom(std::vector<double>& w)
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (int c = 0; c < 6; c++)
     {
-        HIP_CHECK(hipMemcpy(col.data(), T.cols + (size_t)(SC_WXX + c) * T.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(col.data(), T.cols + (size_t)(SC_WXX + c) * T.tree.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
         for (int i = 0; i < N; i++) w[(size_t)i * 6 + c] = col[i];
     }
 }
@@ -639,7 +661,7 @@ int Samplers::adf_setup(int nBins, const aztot_adf_column* cols, int nCols)
     T.edges[0] = 1.0; T.edges[nBins] = -1.0;
     if (nBins % 2 == 0) T.edges[nBins / 2] = 0.0;
     const int N = model_.nAt;
-    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
+    T.sliceShift = lanes_shift();
     const size_t nEnt = (size_t)nBins * nCols;
     T.useLds = nEnt * sizeof(uint32_t) <= (size_t)kAdfHistBudget ? 1 : 0;
     set_up(adf_, T, [&] {
@@ -679,10 +701,9 @@ void Samplers::adf_sample()
         HIP_CHECK(hipMemsetAsync(S.summary, 0, sizeof(summary), stream_));
         S.counted = false;
         timed("adf_neigh", [&] {
-            hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId);
-            const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_adf_neigh, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, S.tables, N, S.sliceShift, S.cellStart, S.x, S.y, S.z, S.kind, S.slotId, S.neigh,
-                               S.summary);
+            hipLaunchKernelGGL(k_grid_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.slotId);
+            hipLaunchKernelGGL(k_adf_neigh, dim3(lane_blocks(S.sliceShift)), dim3(kBlock), 0, stream_, S.grid, S.tables, N, S.sliceShift, S.cellStart, S.x, S.y, S.z, S.kind,
+                               S.slotId, S.neigh, S.summary);
         });
         HIP_CHECK(hipMemcpyAsync(&summary, S.summary, sizeof(summary), hipMemcpyDeviceToHost, stream_));
         host_.end_sample("adf neighbours");     // the tile and the lanes per atom are sized on the host from the counts just read back
@@ -693,7 +714,7 @@ void Samplers::adf_sample()
                                      " neighbours inside the largest radius of its columns, more than AZTOT_ADF_MAX_NEIGHBOURS = " +
                                      std::to_string(AZTOT_ADF_MAX_NEIGHBOURS) + ": nothing was added");
         if (most < 2) return;                    // no atom has a pair of neighbours
-        // lanes per central atom (fitted to the sweep of tools/adf_cost.py): the fewest, from 4, with which the launch has 65536 lanes and the
+        // lanes per central atom (fitted to the sweep of tools/adf_cost.py): the fewest, from 4, with which the launch has 65536 lanes (lanes_shift(), kept in S.sliceShift) and the
         // histogram and the tiles of a workgroup (256 / lanes of them, each `cap` neighbours) stay inside kAdfLdsComfort, so that four workgroups share a CU;
         // more while they do not fit at all.  Every lane of an atom walks all 27 cells, so the gather's cost per atom grows with the lanes; the pairs do not care
         const int cap = (int)most;
@@ -707,7 +728,7 @@ void Samplers::adf_sample()
             while ((1 << laneShift) < forced) laneShift++;
             while (laneShift < 6 && histBytes + (size_t)(kBlock >> laneShift) * cap * kAdfTileBytes > (size_t)kAdfLdsBudget) laneShift++;
         }
-        else while (laneShift < 6 && (((long long)N << laneShift) < 65536 || histBytes + (size_t)(kBlock >> laneShift) * cap * kAdfTileBytes > (size_t)kAdfLdsComfort))
+        else while (laneShift < 6 && (laneShift < S.sliceShift || histBytes + (size_t)(kBlock >> laneShift) * cap * kAdfTileBytes > (size_t)kAdfLdsComfort))
             laneShift++;
         const int groups = kBlock >> laneShift;
         const size_t lds = histBytes + (size_t)groups * cap * kAdfTileBytes;
@@ -1036,26 +1057,19 @@ int Samplers::boo_setup(const aztot_boo_params& p)
     T.nBins = p.n_bins; T.nSpec = nSpec;
     for (int o = 0; o < p.n_orders; o++) T.stride += 2 * (p.orders[o] + 1);
     const int N = model_.nAt;
-    // lanes per atom: a function of N alone (the rule of the coordination numbers), so that the order of every per-atom sum is one too
-    while (T.sliceShift < 6 && ((long long)std::max(N, 1) << T.sliceShift) < 65536) T.sliceShift++;
-    T.nChunk = std::max(1, div_up(N, kBooChunk));
-    T.nChunkPad = 1;
-    while (T.nChunkPad < T.nChunk) T.nChunkPad <<= 1;
-    T.nPad = (size_t)T.nChunk * kBooChunk;
+    T.sliceShift = lanes_shift();
+    T.tree = IdTree(N);
     T.nHist = (size_t)2 * p.n_orders * nSpec * p.n_bins;
     T.useLds = (T.nHist + nSpec) * sizeof(uint32_t) <= (size_t)kBooHistBudget ? 1 : 0;
     set_up(boo_, T, [&] {
-        grid_setup(T, p.radius);
-        const size_t n = (size_t)std::max(N, 1), nCols = (size_t)2 * p.n_orders;
-        T.arrivalId = T.mem.alloc<int32_t>(n, false, stream_); T.canonRank = T.mem.alloc<int32_t>(n, false, stream_);
-        T.slotId = T.mem.alloc<int32_t>(n, false, stream_);
-        HIP_CHECK(hipMemsetAsync(T.slotId, 0xff, sizeof(int32_t) * n, stream_));
+        canon_setup(T, p.radius);
+        const size_t n = (size_t)std::max(N, 1), nCols = (size_t)2 * p.n_orders, nPad = T.tree.nPad;
         T.nSlot = T.mem.alloc<int32_t>(n, true, stream_);
         T.qlm = T.mem.alloc<double>(n * (size_t)T.stride, true, stream_);
-        T.nById = T.mem.alloc<int32_t>(T.nPad, true, stream_); T.typeById = T.mem.alloc<int32_t>(T.nPad, false, stream_);
-        HIP_CHECK(hipMemsetAsync(T.typeById, 0xff, sizeof(int32_t) * T.nPad, stream_));
-        T.qCols = T.mem.alloc<double>(nCols * T.nPad, true, stream_);
-        T.partials = T.mem.alloc<double>(nCols * nSpec * (size_t)T.nChunkPad, true, stream_);
+        T.nById = T.mem.alloc<int32_t>(nPad, true, stream_); T.typeById = T.mem.alloc<int32_t>(nPad, false, stream_);
+        HIP_CHECK(hipMemsetAsync(T.typeById, 0xff, sizeof(int32_t) * nPad, stream_));
+        T.qCols = T.mem.alloc<double>(nCols * nPad, true, stream_);
+        T.partials = T.mem.alloc<double>(nCols * nSpec * (size_t)T.tree.nChunkPad, true, stream_);
         T.sums = T.mem.alloc<double>(nCols * nSpec, true, stream_);
         T.totals = T.mem.alloc<unsigned long long>(T.nHist + nSpec, true, stream_);
     });
@@ -1099,19 +1113,12 @@ void Samplers::boo_sample()
         const int N = model_.nAt, nO = S.par.n_orders, nCols = 2 * nO;
         S.sampled = false;
         if (N == 0) return;
-        static const char* const names[2] = {"k_boo_bin", "k_boo_scan"};
-        grid_count(S, A, names);
-        const int nb = div_up(N, kBlock);
-        // arrival order -> ids ascending inside every cell; the slot -> id map of that order
-        timed("k_boo_ids", [&] { hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.rankOf, S.cellStart, S.arrivalId); });
-        timed("k_boo_rank", [&] { hipLaunchKernelGGL(k_stress_rank, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.cellStart, S.arrivalId, S.canonRank); });
-        timed("k_boo_place", [&] {
-            hipLaunchKernelGGL(k_rdf_place, dim3(nb), dim3(kBlock), 0, stream_, S.grid, A, N, S.cellOf, S.canonRank, S.cellStart, S.x, S.y, S.z, S.kind);
-            hipLaunchKernelGGL(k_cn_slot_ids, dim3(nb), dim3(kBlock), 0, stream_, A, N, S.cellOf, S.canonRank, S.cellStart, S.slotId);
-        });
+        const IdTree& tree = S.tree;
+        static const char* const names[5] = {"k_boo_bin", "k_boo_scan", "k_boo_ids", "k_boo_rank", "k_boo_place"};
+        grid_fill_canonical(S, A, names, true);
         BooParams P;
         P.r2 = S.par.radius * S.par.radius; P.centralMask = S.par.central_mask; P.ligandMask = S.par.ligand_mask;
-        const int blocks = (int)((((long long)N << S.sliceShift) + kBlock - 1) / kBlock);
+        const int blocks = lane_blocks(S.sliceShift);
         BooOrder tab[AZTOT_BOO_MAX_ORDERS];
         for (int o = 0, at = 0; o < nO; at += 2 * (S.par.orders[o] + 1), o++) tab[o] = boo_order_table(S.par.orders[o], at, S.stride);
         timed("k_boo_qlm", [&] {
@@ -1124,19 +1131,19 @@ void Samplers::boo_sample()
         timed("k_boo_average", [&] {
             for (int o = 0; o < nO; o++)
                 boo_dispatch(S.par.orders[o], [&](auto l) {
-                    hipLaunchKernelGGL(k_boo_average<decltype(l)::value>, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, P, tab[o], N, S.sliceShift, o, nO, S.nPad,
+                    hipLaunchKernelGGL(k_boo_average<decltype(l)::value>, dim3(blocks), dim3(kBlock), 0, stream_, S.grid, P, tab[o], N, S.sliceShift, o, nO, tree.nPad,
                                        S.cellStart, S.x, S.y, S.z, S.kind, S.slotId, S.nSlot, S.qlm, S.qCols, S.nById, S.typeById);
                 });
         });
-        const int gs = std::max(1, std::min(kBooMaxBlocks, nb));
+        const int gs = std::max(1, std::min(kBooMaxBlocks, div_up(N, kBlock)));
         timed("k_boo_hist", [&] {
-            hipLaunchKernelGGL(k_boo_hist, dim3(gs), dim3(kBlock), S.useLds ? (S.nHist + S.nSpec) * sizeof(uint32_t) : 0, stream_, N, nO, S.nSpec, S.nBins, S.nPad,
+            hipLaunchKernelGGL(k_boo_hist, dim3(gs), dim3(kBlock), S.useLds ? (S.nHist + S.nSpec) * sizeof(uint32_t) : 0, stream_, N, nO, S.nSpec, S.nBins, tree.nPad,
                                S.useLds, S.qCols, S.nById, S.typeById, S.totals);
         });
         timed("k_boo_chunks", [&] {
-            hipLaunchKernelGGL(k_boo_chunks, dim3(S.nChunk), dim3(kBlock), 0, stream_, nCols, S.nSpec, S.nPad, S.nChunkPad, S.qCols, S.typeById, S.partials);
+            hipLaunchKernelGGL(k_boo_chunks, dim3(tree.nChunk), dim3(kBlock), 0, stream_, nCols, S.nSpec, tree.nPad, tree.nChunkPad, S.qCols, S.typeById, S.partials);
         });
-        timed("k_boo_fold", [&] { hipLaunchKernelGGL(k_boo_fold, dim3(nCols * S.nSpec), dim3(kBlock), 0, stream_, S.nChunkPad, S.partials, S.sums); });
+        timed("k_boo_fold", [&] { hipLaunchKernelGGL(k_tree_fold, dim3(nCols * S.nSpec), dim3(kBlock), 0, stream_, tree.nChunkPad, 1, S.partials, S.sums); });
     });
     S.sampled = true;
     S.samples++;
@@ -1162,7 +1169,7 @@ void Samplers::boo_per_atom(std::vector<int32_t>& n, std::vector<double>& q)
     for (int kind = 0; kind < 2; kind++)
         for (int o = 0; o < nO; o++)
         {
-            HIP_CHECK(hipMemcpy(col.data(), S.qCols + (size_t)(kind * nO + o) * S.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(col.data(), S.qCols + (size_t)(kind * nO + o) * S.tree.nPad, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
             for (int i = 0; i < N; i++) q[((size_t)i * nO + o) * 2 + kind] = col[i];
         }
 }

@@ -19,11 +19,9 @@
 
 namespace aztot {
 
-constexpr int kTcfChunk = kBlock;           // ids per workgroup of k_tcf_correlate: four waves of 64 consecutive ids
-
 struct TcfBox { double L[3], invL[3], half[3]; };
 
-// the six arrays of one stored state: x y z vx vy vz, each nPad long (ids padded to a multiple of kTcfChunk; the padding stays zero)
+// the six arrays of one stored state: x y z vx vy vz, each nPad long (ids padded to a multiple of kTreeChunk; the padding stays zero)
 __device__ __forceinline__ void tcf_store(double* __restrict__ s, size_t nPad, int id, double x, double y, double z, double vx, double vy, double vz)
 {
     s[id] = x; s[nPad + id] = y; s[2 * nPad + id] = z;
@@ -54,10 +52,10 @@ __device__ __forceinline__ TcfOrigin tcf_load(const double* __restrict__ s, size
     return TcfOrigin{s[id], s[nPad + id], s[2 * nPad + id], s[3 * nPad + id], s[4 * nPad + id], s[5 * nPad + id]};
 }
 
-// Workgroup b holds ids [256 b, 256 b + 256): lane l of wave w is id 256 b + 64 w + l, so wave_sum (strides 32 ... 1) is step 1 of the tree and
-// (w0 + w2) + (w1 + w3) is step 2.  The current state stays in registers while the live origins (ring slots 0 ... nLive - 1) stream past; origin k + 1
-// is loaded before origin k is reduced, so that its six loads are in flight across the reduction and the barrier.  Species are found by ballot: only
-// those that occur in the chunk are reduced, the others get their +0.0 written.
+// Workgroup b holds ids [256 b, 256 b + 256): lane l of wave w is id 256 b + 64 w + l, so wave_sum is step 1 of the tree and tree_wave4 is step 2.
+// The current state stays in registers while the live origins (ring slots 0 ... nLive - 1) stream past; origin k + 1 is loaded before origin k is
+// reduced, so that its six loads are in flight across the reduction and the barrier.  Species are found by ballot: only those that occur in the
+// chunk are reduced, the others get their +0.0 written.
 //   partials[((k * 2 + quantity) * nSpec + species) * nChunkPad + b], quantity 0 MSD, 1 VAF
 __global__ __launch_bounds__(kBlock) void k_tcf_correlate(TcfBox B, int nSpec, size_t nPad, int nChunkPad, int nLive, const double* __restrict__ cur,
                                                           const int32_t* __restrict__ typeById, const double* __restrict__ ring,
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_tcf_correlate(TcfBox B, int nSpec, s
     __shared__ double red[2][2][kSpecCap][kBlock / kWave];      // [origin parity][quantity][species][wave]
     __shared__ unsigned sPresent;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const size_t id = (size_t)blockIdx.x * kTcfChunk + t;
+    const size_t id = (size_t)blockIdx.x * kTreeChunk + t;
     const TcfOrigin c = tcf_load(cur, nPad, id);
     const int ty = typeById[id];                                // -1 in the padding
     if (t == 0) sPresent = 0u;
@@ -102,30 +100,25 @@ __global__ __launch_bounds__(kBlock) void k_tcf_correlate(TcfBox B, int nSpec, s
         {
             const int q = t / nSpec, s = t - q * nSpec;
             double v = 0.0;
-            if ((present >> s) & 1u) v = __dadd_rn(__dadd_rn(r[q][s][0], r[q][s][2]), __dadd_rn(r[q][s][1], r[q][s][3]));
+            if ((present >> s) & 1u) v = tree_wave4(r[q][s]);
             partials[(((size_t)k * 2 + q) * nSpec + s) * nChunkPad + blockIdx.x] = v;
         }
     }
 }
 
 // Step 3 of the tree for workgroup (k, quantity, species): the chunk sums (padded with +0.0 to nChunkPad, a power of two; the padding is never
-// written, the fold only touches entries below nChunkPad / 2) folded by halving in place, then acc = acc + S at the lag of the origin in ring slot k.
+// written, the fold only touches entries below nChunkPad / 2) folded by tree_fold, then acc = acc + S at the lag of the origin in ring slot k.
 // Sample c (counted from 0), origins every E samples in slot (c / E) % M: slot k holds origin number j = the largest j <= c / E with j % M == k.
 __global__ __launch_bounds__(kBlock) void k_tcf_fold(int nSpec, int nChunkPad, long long c, int E, int M, double* partials, long long* __restrict__ count,
                                                      double* __restrict__ msdSum, double* __restrict__ vafSum)
 {
-    double* a = partials + (size_t)blockIdx.x * nChunkPad;
-    for (int h = nChunkPad >> 1; h > 0; h >>= 1)
-    {
-        for (int j = threadIdx.x; j < h; j += kBlock) a[j] = __dadd_rn(a[j], a[j + h]);
-        __syncthreads();
-    }
+    const double sum = tree_fold(partials + (size_t)blockIdx.x * nChunkPad, nChunkPad);
     if (threadIdx.x != 0) return;
     const int s = blockIdx.x % nSpec, q = (blockIdx.x / nSpec) & 1, k = blockIdx.x / (2 * nSpec);
     const long long newest = c / E, j = newest - (newest - k) % M;
     const long long lag = c - j * E;
     double* acc = (q ? vafSum : msdSum) + lag * nSpec + s;
-    *acc = __dadd_rn(*acc, a[0]);
+    *acc = __dadd_rn(*acc, sum);
     if (q == 0 && s == 0) count[lag] += 1;
 }
 

@@ -1,5 +1,5 @@
 """Cost of the pressure-tensor sampler (aztot_stress_sample, stress.hip.h) on one GPU, beside two baselines from the same run:
-  k_cn_pairs at R = rMax          the same walk without the force arithmetic (coordination-number sampler, one column);
+  k_cn_pairs at R = rMax          the same grid_walk (grid.hip.h) without the force arithmetic (coordination-number sampler, one column);
   pair_tile of a sort_every = 1   the same arithmetic on the engine's own tiles (every step rebuilds the cells and stages every cell).
   step of the same box
 
