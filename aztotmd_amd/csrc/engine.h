@@ -272,7 +272,8 @@ private:
         bool ekinFromPair = false;      // where the last step left its kinetic-energy partials
         bool lastStepEquil = false;     // the last step launched left its kinetic energy in DevStats::local (k_reduce_kin), not in the partial sums
     } notes_;                           // of the last step EXECUTED (launched one by one, or the last of a replayed cycle)
-    struct GraphSlot { BufState before, after; LaunchNotes notes; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
+    // (entryBytes: the pair-list entry format the cycle's rebuild step records and its steps walk - ListStore::entryBytes once the graph has run)
+    struct GraphSlot { BufState before, after; LaunchNotes notes; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int entryBytes = 2; };
     void adopt_launch_notes(const LaunchNotes& n) { const int ever = std::max(notes_.blocksEver, n.blocksEver); notes_ = n; notes_.blocksEver = ever; }
     std::vector<GraphSlot> graphs_;
     int graphCycle_ = 0;            // steps held by the captured graphs

@@ -605,6 +605,7 @@ void ListStore::allocate(int candCapNew, int iterCapNew)
     report = mem_.alloc<int32_t>(LR_COUNT, true, stream_); rel = mem_.alloc<float4>((size_t)capacity_ + kWave, true, stream_);
     candCap = candCapNew; iterCap = iterCapNew;
     candLds = stageLds = candCapNew; iterLds = iterCapNew;          // (tightened once the builder has reported what the cells really hold: tighten / adapt)
+    entryBytes = entryNext = 2;                                     // (... and 16-bit entries until then: one-byte entries go with a tile of at most 256 records)
     {   // header: -1 = no list ; second word: the cell's coordinates in the local grid (the kernels decode them with shifts)
         std::vector<int32_t> mx(4 * nc, 0);
         const int ncy = P.nc[1], ncz = P.nc[2];
@@ -647,7 +648,8 @@ PairLists ListStore::pair_lists() const
     if (on)
     {
         pl.cand = cand; pl.meta = meta; pl.pairs = pairs; pl.noList = report;
-        pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.stageLds = stageLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.entryScale = pair_list_entry_scale(*P_); pl.waves = waves;
+        pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.stageLds = stageLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.waves = waves;
+        pl.entryBytes = entryBytes; pl.entryScale = entryBytes == 1 ? 1 : pair_list_entry_scale(*P_);      // (one-byte entries are record numbers in every mode)
         pl.rel = rel;
     }
     return pl;
@@ -663,7 +665,11 @@ int ListStore::tile_records_for(int maxT) const
     // (roomy: systems that run without the clean-up launch - a cell that outgrows the tile there costs a window of steps run again, and LDS per wave is not
     //  what bounds a step of a few thousand cells: + 6 %)
     const bool roomy = P_->nranks == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
-    const int need = std::max(4 * kWave, std::min(candCap, roomy ? maxT + maxT / 16 + 4 : maxT + maxT / 100 + 1));
+    int need = std::max(4 * kWave, std::min(candCap, roomy ? maxT + maxT / 16 + 4 : maxT + maxT / 100 + 1));
+    // (one GPU, one wave per cell, every cell's record numbers still in a byte: the margin never takes the tile past the 256 records of the four-group kernel,
+    //  which is the one that walks one-byte entries (narrow_fits) - from 238 kept candidates on a roomy engine's margin shrinks instead, to nothing at 255,
+    //  where the byte is the limit anyway.  Whatever DBG_WIDE_ENTRIES says: the switch changes the entries' width and nothing else)
+    if (maxT <= 255 && P_->nranks == 1 && waves == 1) need = 4 * kWave;
     // (a tile of up to 256 records is served by the kernel that gathers four groups of candidates up front instead of five: never a few records more than
     //  that for the sake of a full LDS block)
     if (need <= 4 * kWave) return need;
@@ -693,14 +699,31 @@ void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& stageLdsNew, i
     candLdsNew = tile_records_for(rep[LR_MAX_TILE]);
     stageLdsNew = stage_records_for(rep[LR_MAX_STAGED]);
     iterLdsNew = std::max(2 * kListMinIter, std::min(iterCap, (rep[LR_MAX_ITERS] + rep[LR_MAX_ITERS] / 8 + 2 + 7) & ~7));
+    // (one-byte entries are read out sixteen iterations at a time: whole chunks where the capacity allows.  A cell's stride in `pairs`, iterCap x 128 B, holds
+    //  2 iterCap one-byte iterations, so any iterCap >= 16 keeps whole chunks of them inside it)
+    if (entryNext == 1 && ((iterLdsNew + 15) & ~15) <= iterCap) iterLdsNew = (iterLdsNew + 15) & ~15;
 }
 
-bool ListStore::tighten(const int32_t* rep)
+bool ListStore::narrow_fits(int maxTile, int candLdsNew, int wavesNew) const
 {
+    return P_->nranks == 1 && !(P_->debugMask & DBG_WIDE_ENTRIES) && !wideForGood_ && wavesNew == 1 && list_preload(candLdsNew) == 4 && maxTile <= 255;
+}
+
+bool ListStore::tighten(const int32_t* rep, bool* formatChanged)
+{
+    if (formatChanged) *formatChanged = false;
     if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_KEPT_FULL] != 0 || rep[LR_MAX_STAGED] <= 0) return false;
     int c, s, i;
     lds_for(rep, c, s, i);
-    if (c >= candLds && s >= stageLds && i >= iterLds) return false;
+    bool changed = false;
+    if (entryNext == 2 && narrow_fits(rep[LR_MAX_TILE], std::min(candLds, c), waves))
+    {   // the lists just recorded hold 16-bit entries: the caller records them again
+        entryNext = 1;
+        lds_for(rep, c, s, i);
+        changed = true;
+        if (formatChanged) *formatChanged = true;
+    }
+    if (c >= candLds && s >= stageLds && i >= iterLds) return changed;
     candLds = std::min(candLds, c); stageLds = std::min(stageLds, s); iterLds = std::min(iterLds, i);
     return true;
 }
@@ -713,9 +736,11 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
     const bool frozen = debug & DBG_SHORT_LISTS;
     if (debug & DBG_LIST_STATS)
     {   // measurement aid: mean list length / tile size / atoms per cell over the cells recorded since the last look
-        std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates staged, %.1f kept, %.2f atoms\n", (double)rep[LR_SUM_ITERS] / rep[LR_RECORDED],
-                     (double)rep[LR_SUM_STAGED] / rep[LR_RECORDED], (double)rep[LR_SUM_CANDS] / rep[LR_RECORDED], (double)rep[LR_SUM_ATOMS] / rep[LR_RECORDED]);
+        std::fprintf(stderr, "aztot: per cell: %.2f list iterations, %.1f candidates staged, %.1f kept, %.2f atoms; %.1f %% of the cells walk more than 16 iterations (%d-byte entries)\n",
+                     (double)rep[LR_SUM_ITERS] / rep[LR_RECORDED], (double)rep[LR_SUM_STAGED] / rep[LR_RECORDED], (double)rep[LR_SUM_CANDS] / rep[LR_RECORDED],
+                     (double)rep[LR_SUM_ATOMS] / rep[LR_RECORDED], 100.0 * (double)rep[LR_OVER_16] / rep[LR_RECORDED], entryBytes);
         HIP_CHECK(hipMemset(&report[LR_SUM_ITERS], 0, sizeof(int32_t) * 4));
+        HIP_CHECK(hipMemset(&report[LR_OVER_16], 0, sizeof(int32_t)));
     }
     // (LR_UNLISTED_NOW stays: it describes the lists in force; the maxima are all-time)
     HIP_CHECK(hipMemsetAsync(&report[LR_UNLISTED], 0, sizeof(int32_t) * 2, stream_));
@@ -735,6 +760,22 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
     // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
     // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
     const int wWant = std::max(waves, waves_wanted((double)rep[LR_MAX_TILE], rep[LR_MAX_ITERS]));
+    const int wavesNew = (wWant > waves && !forcedWaves_ && !frozen) ? wWant : waves;
+    // The entry format.  One-byte entries and a cell they cannot hold (it was recorded without a list, LR_KEPT_FULL, and the clean-up launch has served it), or
+    // a tile or a wave count their kernel is not built for: back to 16 bits from the next step on, which rebuilds - and for good.  16-bit entries where one
+    // byte would do (an engine whose first lists were recorded by a step, not by prepare_next_call): the next rebuild, whenever it comes, records one-byte
+    // entries - the lists in force serve until then, no step's schedule changes
+    if (entryNext == 1 && (rep[LR_MAX_TILE] > 255 || keptFull > 0 || !narrow_fits(rep[LR_MAX_TILE], candLdsNew, wavesNew)))
+    {
+        entryNext = 2; wideForGood_ = true;
+        v.rebuild = v.launchChanged = true;
+    }
+    else if (entryNext == 2 && !frozen && tileFull + keptFull + listFull == 0 && narrow_fits(rep[LR_MAX_TILE], candLdsNew, wavesNew))
+    {
+        entryNext = 1;
+        v.launchChanged = true;
+        lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew);
+    }
     if (wWant > waves && !forcedWaves_ && !frozen)
     {   // (what was recorded describes lists that no longer exist: nothing more to decide now)
         const int itersNew = std::max(2 * kListMinIter, ((int)(rep[LR_MAX_ITERS] * (double)waves / wWant * 1.3) + 8 + 7) & ~7);
@@ -989,6 +1030,8 @@ void Engine::launch_pair()
         // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
         // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
         const bool wantEnergies = stepsLeftInRun_ == 0 || (debug_ & DBG_ENERGIES_EVERY_STEP);
+        // (a step that records the lists records them in the entry format the store has decided on, and walks them in it)
+        if (candMode_ == 1 && lists_.on && !overlapHalo_) lists_.begin_recording();
         const PairLists pl = lists_.pair_lists();
         if (overlapHalo_)
         {   // interior x-layers [2 hw, ncx - 2 hw) first; then, once the neighbours' coordinates have landed, the two runs of boundary layers
@@ -1060,6 +1103,7 @@ void Engine::launch_pair()
                     if (profile_ && !capturing_) timers_.count("fold_drift");
                 }
                 const PairLaunch CL = pair_launch(QL);
+                if (profile_ && !capturing_ && pl.entryBytes == 1) timers_.count("narrow_lists");      // (a count, no time of its own: the launch is timed as pair_list)
                 timed("pair_list", [&] { splitBlocks = launch_pair_list(CL, PairRange(), pl, nx, wantEnergies); });
                 if (!skipCleanup)
                     timed("pair_cleanup", [&] { splitBlocks += launch_pair_cleanup(C, PairRange(), pl, nx); });
@@ -1616,6 +1660,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     g.before = now;
     const int sinceBefore = sinceSort_;
     const LaunchNotes notesBefore = notes_;      // (the capture executes nothing: what the host knows about the last EXECUTED step must survive it)
+    const int entryBytesBefore = lists_.entryBytes;       // (... the format of the lists on the device too: the captured rebuild step may record another)
     HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
     capturing_ = true;
     try
@@ -1634,6 +1679,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
         preIntegrated_ = false;
         kickFolded_ = false;
         sinceSort_ = sinceBefore;
+        lists_.entryBytes = entryBytesBefore;
         set_buf_state(now);
         adopt_launch_notes(notesBefore);
         throw;
@@ -1643,6 +1689,8 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
     g.after = buf_state();
     g.notes = notes_;         // ... of the cycle's last step
+    g.entryBytes = lists_.entryBytes;
+    lists_.entryBytes = entryBytesBefore;
     set_buf_state(now);               // the capture itself executed nothing
     adopt_launch_notes(notesBefore);
     sinceSort_ = sinceBefore;
@@ -1680,6 +1728,7 @@ void Engine::run_steps(int nsteps)
             rebuilds_ += (lazyOn_ && lazyK_ > 1) ? 1 : cycle;       // (a captured cycle: one sort interval, or two every-step steps)
             set_buf_state(slot->after);           // one sort per cycle (K > 1) and the coordinate-array swaps of the fused steps
             adopt_launch_notes(slot->notes);      // where the cycle's last step left its partial sums
+            lists_.entryBytes = slot->entryBytes; // the format its rebuild step recorded
             sinceSort_ = kNoSort;                 // the next cycle (or the eager remainder) starts with a sort
         }
     }
@@ -1698,16 +1747,23 @@ void Engine::prepare_next_call()
     if (lists_.on && lazyK_ > 1 && !listsValid_ && sinceSort_ == 0 && pair_variant() == 2)
     {
         P_.cycleStep = 0;
-        HIP_CHECK(hipMemsetAsync(&lists_.report[LR_UNLISTED_NOW], 0, sizeof(int32_t), stream_));
-        launch_build_lists(pair_launch(P_), PairRange(), lists_.pair_lists());
-        check_launch("list building");
-        sync();
         int32_t rep[LR_COUNT];
-        HIP_CHECK(hipMemcpy(rep, lists_.report, sizeof(rep), hipMemcpyDeviceToHost));
-        unlistedState_ = (rep[LR_UNLISTED_NOW] == 0) ? 1 : 2;
+        auto record = [&] {
+            HIP_CHECK(hipMemsetAsync(&lists_.report[LR_UNLISTED_NOW], 0, sizeof(int32_t), stream_));
+            lists_.begin_recording();
+            launch_build_lists(pair_launch(P_), PairRange(), lists_.pair_lists());
+            check_launch("list building");
+            sync();
+            HIP_CHECK(hipMemcpy(rep, lists_.report, sizeof(rep), hipMemcpyDeviceToHost));
+            unlistedState_ = (rep[LR_UNLISTED_NOW] == 0) ? 1 : 2;
+        };
+        record();
         // the first lists of an engine's life: size the LDS tiles from what the cells really hold right away (adapt_sort_interval does the same at
-        // every look) - the next call then walks them at full occupancy
-        if (!(debug_ & DBG_SHORT_LISTS) && lists_.tighten(rep)) drop_graphs();
+        // every look) - the next call then walks them at full occupancy - and choose the entry format from it: where one byte per entry will do, the
+        // lists are recorded once more, in that format (the cells are as they were: no rebuild, nothing a caller can see)
+        bool formatChanged = false;
+        if (!(debug_ & DBG_SHORT_LISTS) && lists_.tighten(rep, &formatChanged)) drop_graphs();
+        if (formatChanged) record();
         if (nranks_ > 1)
         {   // the plain steps' coordinate exchange needs to know where the boundary layers sit; with interval 1 nobody had asked (k_rank_gather left it ready)
             int32_t h[HI_COUNT];

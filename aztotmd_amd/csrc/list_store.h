@@ -32,6 +32,11 @@ struct ListStore
     int stageLds = 0;               // what the builder's staging area is sized for: the candidates a cell STAGES before the unreachable ones are dropped (<= candCap)
     int waves = 1;                  // waves per cell in k_pair_list (PairLists::waves)
     int growths = 0;
+    // Bytes per pair-list entry (PairLists::entryBytes).  entryBytes: the format of the lists on the device, what k_pair_list is launched with; entryNext: the
+    // format the next recording will leave (begin_recording makes it the one in force).  An engine starts with 2, goes to 1 where narrow_fits says so (tighten:
+    // the caller records again at once ; adapt: from the next rebuild on, whenever that comes - no step's schedule changes), and back to 2 FOR GOOD when a
+    // report shows a cell beyond 255 kept candidates (adapt: Verdict::rebuild).  A launch parameter: every change drops the captured graphs.
+    int entryBytes = 2, entryNext = 2;
 
     // sizes the lists from density, cut-off and skin (listRadius = cut-off + skin) and allocates them; without room for them the run goes on with `on` false
     void create(const StepParams& P, const Model& m, const aztot_options& opt, int capacity, double listRadius, hipStream_t stream, int rank);
@@ -42,8 +47,14 @@ struct ListStore
     PairLists pair_lists() const;   // what the kernels are launched with (all-null when off)
     // LDS sizes that hold the largest cell of a report
     void lds_for(const int32_t* rep, int& candLds, int& stageLds, int& iterLds) const;
-    // the first lists of an engine's life: tighter LDS sizes right away, if every cell fitted.  True when they changed
-    bool tighten(const int32_t* rep);
+    // the first lists of an engine's life: tighter LDS sizes right away, if every cell fitted.  True when launch parameters changed; *formatChanged when
+    // entryNext differs from the format those lists were recorded in (the caller records them again)
+    bool tighten(const int32_t* rep, bool* formatChanged = nullptr);
+    // One-byte entries for an engine whose largest recorded cell keeps maxTile candidates in a tile of candLdsNew records?  One GPU, one wave per cell, the
+    // four-group kernel, every record number in a byte, never gone back before, DBG_WIDE_ENTRIES not set
+    bool narrow_fits(int maxTile, int candLdsNew, int wavesNew) const;
+    // in front of a launch of k_build_lists: the lists it leaves - and every k_pair_list launch from here on - are in the format entryNext
+    void begin_recording() { entryBytes = entryNext; }
     // at a look, for a report with cells recorded: tighten or widen the LDS sizes, more waves per cell, larger arrays, or give up
     Verdict adapt(const int32_t* rep, unsigned debug);
 
@@ -57,6 +68,7 @@ private:
     hipStream_t stream_ = nullptr;
     int capacity_ = 0, rank_ = 0;
     int forcedWaves_ = 0;           // options.waves_per_cell where it names a count k_pair_list has (measurements), else 0
+    bool wideForGood_ = false;      // a report once showed a cell that one-byte entries cannot hold: this engine keeps 16-bit entries (no flipping back and forth)
     size_t ldsMax_ = 0;             // dynamic LDS this device grants a workgroup
 };
 

@@ -151,7 +151,11 @@ __device__ __forceinline__ void fold_drift_finish(const StepParams& P, const Spe
 // TSTAT = true (launches that fuse the next step in a run with the radiative thermostat; never with ENG: the call's last step does not fuse): the epilogue
 // applies the thermostat between closing this step and opening the next, operation for operation what k_boundary_radi does in a launch of its own.
 // PRE: groups of candidates gathered up front (list_preload: 4 for tiles of up to 256 records, else 5).
-template <int MODE, int VDW, bool ENG, bool MULTI, bool TSTAT = false, int PRE = kListPreload>
+// EB: bytes per list entry (PairLists::entryBytes).  2: chunks of 8 iterations, two of them asked for up front.  1 (only !MULTI && PRE == 4, every mode): an
+// entry is the record NUMBER, a chunk holds 16 iterations; chunk 0 is asked for up front and chunk 1 only by a wave whose header says nIter > 16 - one cell
+// in seven of a liquid - so the pair entries of a step are 1.14 KiB per cell instead of 2.14.  The same entries are visited in the same order with the same
+// arithmetic: only the encoding of a record number differs.
+template <int MODE, int VDW, bool ENG, bool MULTI, bool TSTAT = false, int PRE = kListPreload, int EB = 2>
 __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_list(StepParams P, SpecTable S, const DevPot* __restrict__ pots, AtomArrays A,
                                                      const int32_t* __restrict__ cellStart, int firstCell, int nCellsRun,
                                                      double* __restrict__ partials, int maxBlocks, const Counts* __restrict__ counts, int blockBase, PairLists L,
@@ -161,7 +165,9 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     constexpr bool kRadii = pair_mode_reads_radii(MODE);
     constexpr bool kTab = pair_mode_has_table(MODE);
     constexpr int RECB = 24;                                         // record {x, y, z} RELATIVE to the centre of the cell
-    constexpr int ESCALE = (MODE == PM_ONE_LJ) ? 1 : 24;                     // list entry -> byte offset of the record (only the one-species LJ kernel keeps byte offsets)
+    static_assert(EB == 2 || (EB == 1 && !MULTI && PRE == 4), "one-byte list entries: one wave per cell and the four-group tile only");
+    constexpr int ESCALE = (MODE == PM_ONE_LJ && EB == 2) ? 1 : 24;          // list entry -> byte offset of the record (only the one-species LJ kernel's 16-bit entries are byte offsets)
+    constexpr int VPC = 16 / EB;                                     // visits per 1 KiB chunk (16 B per lane)
     constexpr int kTabDoubles = kTab ? kLjSpecMax * kLjSpecMax * kPairTabStride : 0;
     extern __shared__ double ldsList[];
     double* const pairTab = ldsList;
@@ -188,8 +194,10 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
 #pragma unroll
     for (int u = 0; u < PRE; u++) ent[u] = myList[(wave + u * W) * kWave];
     uint4 w = pl[0];
-    uint4 w1 = pl[kWave];                                           // (the second chunk too: 16 iterations cover a liquid's cells, and a chunk asked for only
-                                                                    //  8 iterations ahead arrives late)
+    uint4 w1 = make_uint4(0u, 0u, 0u, 0u);
+    if (EB == 2) w1 = pl[kWave];                                    // (the second chunk too: 16 iterations cover a liquid's cells, and a chunk asked for only
+                                                                    //  8 iterations ahead arrives late.  One-byte entries: chunk 0 IS 16 iterations; chunk 1
+                                                                    //  is asked for below, once the header has said that the cell needs it)
     // {list header, cell coordinates lx | cy << 10 | cz << 20, the cell's first atom, atoms | rcpNS << 12}: one scalar load - no look at cellStart (a second,
     // dependent round trip), no integer divisions (the builder leaves slices per atom and their reciprocal in the header)
     const int4 mx = ((const int4*)L.meta)[cell];
@@ -204,6 +212,13 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     if (meta > 0)
     {
         const int T = meta & 0xFFF, nIter = (meta >> 12) & 0xFF;
+        if (EB == 1)
+        {   // one-byte entries: the second chunk, for the cells that have one (wave-uniform).  Asked for here, in front of the gather, so that it travels with
+            // the coordinates; the barrier keeps the compiler from sinking the load behind the LDS writes (as it once did with a conditional preload of
+            // the fifth candidate group)
+            if (nIter > VPC) w1 = pl[kWave];
+            asm volatile("" ::: "memory");
+        }
         const int ncy = P.nc[1], ncz = P.nc[2];
         const int lx = mx.y & 1023, cy = (mx.y >> 10) & 1023, cz = (mx.y >> 20) & 1023;
         const int ib = mx.z;
@@ -331,7 +346,7 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         double ljDropR2 = P.ljDropR2;
         if (kTab) asm volatile("" : "+v"(ljDropR2));                   // (table-driven modes: a vector register, like the uniforms of PairHot - see there)
         const PairHot hot = kTab ? pair_hot_in_vgprs(P, lj) : (MODE == PM_ONE_LJ ? pair_hot_lj_in_vgprs(P, lj) : pair_hot(P, lj));
-        const int nChunks = (nIter + 7) >> 3;
+        const int nChunks = (nIter + VPC - 1) / VPC;
         // software-pipelined: the candidate of iteration t + 1 is read from LDS before the potential of iteration t is evaluated (entries behind a lane's
         // last one point at the dummy - the builder fills the list buffer with it - so the read ahead is always a valid one)
         double xj, yj, zj, radj = 0.0;
@@ -345,19 +360,23 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             if (kRadii) rd = trad[en];
             if (MODE == PM_GENERIC) ty = ttyp0[en];
         };
-        fetch(nIter > 0 ? (w.x & 0xFFFFu) : dummyOff, xj, yj, zj, tj, radj);
+        // (one-byte entries: whatever a byte holds - a stale entry of an older list, of the other format - is a record of the tile, which has candLds + 1 >= 257
+        //  records: the read ahead stays inside the tile)
+        fetch(nIter > 0 ? (w.x & (EB == 1 ? 0xFFu : 0xFFFFu)) : dummyOff, xj, yj, zj, tj, radj);
         for (int c = 0; c < nChunks; c++)
         {
             uint4 wn = w1;
             if (c + 2 < nChunks) w1 = pl[(c + 2) * kWave];
             const uint32_t ww[5] = {w.x, w.y, w.z, w.w, wn.x};
 #pragma unroll
-            for (int u = 0; u < 8; u++)
+            for (int u = 0; u < VPC; u++)
             {
-                const int t = c * 8 + u;
+                const int t = c * VPC + u;
                 if (t >= nIter) break;                                  // wave-uniform
-                uint32_t kn = ((u + 1) & 1) ? (ww[(u + 1) >> 1] >> 16) : (ww[(u + 1) >> 1] & 0xFFFFu);      // byte offset of the next candidate's record
-                if (u == 7 && c + 1 >= nChunks) kn = dummyOff;           // (behind the list's last chunk there is nothing the builder wrote: stale entries of an older, larger tile)
+                uint32_t kn;                                            // the next candidate's list entry: byte offset of its record, or its number
+                if (EB == 1) kn = (ww[(u + 1) >> 2] >> (8 * ((u + 1) & 3))) & 0xFFu;
+                else kn = ((u + 1) & 1) ? (ww[(u + 1) >> 1] >> 16) : (ww[(u + 1) >> 1] & 0xFFFFu);
+                if (u == VPC - 1 && c + 1 >= nChunks) kn = dummyOff;     // (behind the list's last chunk there is nothing the builder wrote: stale entries of an older, larger tile)
                 double xn, yn, zn, radn = 0.0;
                 int tn = 0;
                 fetch(kn, xn, yn, zn, tn, radn);
@@ -824,7 +843,10 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         for (int q = kept + lane; q < Tpad; q += kWave) myList[q] = (uint32_t)ib | (0x15u << 26);
         __builtin_amdgcn_wave_barrier();
     }
-    const bool keptFull = usable && kept > L.candLds;               // (staged, filtered, and still too many for the walk's tile: served by the clean-up launch until the tile has grown)
+    // (staged, filtered, and still too many for the walk's tile - or, with one-byte entries, for a record number: served by the clean-up launch until the tile
+    //  has grown, or the engine has gone back to 16-bit entries)
+    const bool narrow = L.entryBytes == 1;
+    const bool keptFull = usable && (kept > L.candLds || (narrow && kept > 255));
     if (keptFull) usable = false;
     if (usable)
     {   // every lane of k_pair_list's layout collects ITS entries: lane = slot * NS + slice of wave w walks entries slice, slice + NS, ... of atom w aw + slot;
@@ -837,6 +859,22 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
             if (slot < aw && atom < nthis) { off = entN[atom]; cnt = entC[atom]; }
             const uint16_t* const src = hits + off;
             uint4* const out = (uint4*)(L.pairs + ((size_t)cell * W + w) * L.iterCap * kWave) + lane;
+            if (narrow)
+            {   // record numbers (entryScale is 1: remap holds n + 1 <= 255), sixteen iterations per lane and chunk
+                for (int c = 0; c * 16 < nIter; c++)
+                {
+                    uint32_t v[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int u = 0; u < 16; u++)
+                    {
+                        const int e = (c * 16 + u) * NS + slice;
+                        const uint32_t r = (e < cnt) ? (uint32_t)remap[src[e]] : 0u;
+                        v[u >> 2] |= r << (8 * (u & 3));
+                    }
+                    out[c * kWave] = make_uint4(v[0], v[1], v[2], v[3]);
+                }
+                continue;
+            }
             for (int c = 0; c * 8 < nIter; c++)
             {
                 uint32_t v[8];
@@ -863,6 +901,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         if (P.debugMask & DBG_LIST_STATS)
         {   // measurement aid (slow)
             atomicAdd(&L.noList[LR_SUM_ITERS], nIter); atomicAdd(&L.noList[LR_SUM_CANDS], kept); atomicAdd(&L.noList[LR_SUM_ATOMS], nthis); atomicAdd(&L.noList[LR_SUM_STAGED], T);
+            if (nIter > 16) atomicAdd(&L.noList[LR_OVER_16], 1);
         }
         if (!usable) { atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); atomicAdd(&L.noList[keptFull ? LR_KEPT_FULL : LR_LIST_FULL], 1); }
     }
@@ -887,8 +926,11 @@ inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, N
     // whose energies are wanted (Engine::launch_step_kernels)
     constexpr bool kCanFuseTstat = !pair_mode_reads_radii(MODE);
     const bool four = list_preload(L.candLds) == 4;                 // groups gathered up front: compiled in
-#define AZTOT_LAUNCH_LIST_PRE(E, M, T, G) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T, G>), grid, block, lds, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials, C.maxBlocks, C.cnt, R.blockBase, L, N)
-#define AZTOT_LAUNCH_LIST(E, M, T) do { if (four) AZTOT_LAUNCH_LIST_PRE(E, M, T, 4); else AZTOT_LAUNCH_LIST_PRE(E, M, T, kListPreload); } while (0)
+    // one-byte entries: instantiated for one wave per cell and the four-group tile only (ListStore::narrow_fits holds the engine to that)
+    const bool narrow = L.entryBytes == 1;
+    if (narrow && (!four || L.waves != 1)) throw std::runtime_error("k_pair_list: one-byte list entries need one wave per cell and a tile of at most 256 records");
+#define AZTOT_LAUNCH_LIST_PRE(E, M, T, G, B) hipLaunchKernelGGL((k_pair_list<MODE, VDW, E, M, T, G, B>), grid, block, lds, C.stream, C.P, C.S, C.pots, C.A, C.cellStart, R.first, R.n, C.partials, C.maxBlocks, C.cnt, R.blockBase, L, N)
+#define AZTOT_LAUNCH_LIST(E, M, T) do { if (narrow) AZTOT_LAUNCH_LIST_PRE(E, false, T, 4, 1); else if (four) AZTOT_LAUNCH_LIST_PRE(E, M, T, 4, 2); else AZTOT_LAUNCH_LIST_PRE(E, M, T, kListPreload, 2); } while (0)
     if (N.photons)
     {
         if (energies || !kCanFuseTstat) throw std::runtime_error("k_pair_list: the thermostat cannot be fused into this launch");

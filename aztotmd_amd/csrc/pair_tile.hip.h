@@ -431,6 +431,7 @@ enum ListReport : int
     LR_KEPT_FULL = 7,       // ... whose kept candidates did not fit the tile of k_pair_list (three in a row: cleared together)
     LR_SUM_ITERS = 8, LR_SUM_CANDS = 9, LR_SUM_ATOMS = 10, LR_SUM_STAGED = 11,     // DBG_LIST_STATS: totals over the cells recorded (four in a row: cleared together)
     LR_MAX_STAGED = 12,     // largest number of candidates a cell staged (box-pruned, before the unreachable ones were dropped) ever recorded
+    LR_OVER_16 = 13,        // DBG_LIST_STATS: cells recorded with more than 16 list iterations (a second chunk of one-byte entries); cleared with the totals
     LR_COUNT = 16,
     LR_NONE = -1            // (k_build_lists: a cell without a list that no counter of its own explains - more than 64 atoms per wave)
 };
@@ -443,7 +444,9 @@ struct PairLists
                                    //          first word -1: this cell keeps no list (more candidates than the tile holds, more than 64 atoms, or more
                                    //          iterations than iterCap) - such cells are staged in full on every step by the clean-up launch
     uint16_t* pairs = nullptr;     // [nCell][iterCap * 64]: chunks of 8 iterations x 64 lanes; an entry is the byte offset of the candidate's record in the LDS tile
-                                   //          of k_pair_list: candidate k sits in record k + 1, record 0 is the far-away dummy (entry 0 = "no candidate")
+                                   //          of k_pair_list: candidate k sits in record k + 1, record 0 is the far-away dummy (entry 0 = "no candidate").
+                                   //          entryBytes == 1: the same 1 KiB chunks hold 16 iterations x 64 lanes of one-byte record NUMBERS (byte u of a lane's
+                                   //          16 bytes is iteration 16 c + u); a cell's stride stays iterCap * 128 B, of which such a list fills at most half
     int32_t* noList = nullptr;     // [LR_COUNT]: the builder's report to the host (enum ListReport)
     int32_t candCap = 0;           // candidates per cell in `cand` (multiple of 64)
     int32_t iterCap = 0;           // list iterations per cell in `pairs` (multiple of 8)
@@ -455,7 +458,9 @@ struct PairLists
                                    //      many and the cells few (dense systems, slab ranks), LDS per wave and wave lifetime are what bounds the kernel.
                                    //      `pairs` then holds `waves` lists per cell ([nCell][waves][iterCap * 64])
     int32_t recBytes = 0;          // bytes per LDS record in k_pair_list: 24 {x, y, z}
-    int32_t entryScale = 0;        // list entry of record n: n * entryScale (the record's byte offset, or its number in the table-driven modes)
+    int32_t entryScale = 0;        // list entry of record n: n * entryScale (the record's byte offset, or its number in the table-driven modes and in one-byte entries)
+    int32_t entryBytes = 2;        // bytes per list entry: 2, or 1 where every cell keeps at most 255 candidates (one GPU, one wave per cell, four-group tile:
+                                   //      ListStore::narrow_fits) - the lists are most of what k_pair_list streams from memory
     const float4* rel = nullptr;   // [atoms] written by the sort: position relative to the centre of the atom's own cell (f32) + its cell's z index; what the builder stages
 };
 // does this cell walk its list?  (the same test in k_pair_list and in the clean-up launch: every cell is served by exactly one of them)
