@@ -405,7 +405,8 @@ class Engine:
 
     def __init__(self, model, device=0, initial_forces=1, center_box=0, seed=12345, pair_variant=0, cell_size=0.0, use_graph=1,
                  profile=0, slab=None, debug=0, sort_every=0, split=0, skin=0.0, energies_every_step=0):
-        """slab: None or dict(rank=, nranks=, rccl_id=bytes) or dict(rank=, nranks=, sendrecv=callable, allreduce=callable).
+        """slab: None or dict(rank=, nranks=, rccl_id=bytes) or dict(rank=, nranks=, sendrecv=callable, allreduce=callable) or
+        dict(rank=, nranks=, loopback=True[, replicated=True]) (options.loopback_ranks 1 / 2, include/aztot.h).
         debug: measurement / test switches (DebugBit above, from csrc/device_md.h); they are not part of the ABI - the library reads them from the
         environment variable AZTOT_DEBUG when the device handle is created, so it is set around that call here."""
         L = lib()
@@ -439,8 +440,9 @@ class Engine:
         else:
             idb = slab.get("rccl_id")
             if slab.get("loopback"):
-                # measurement aid: one rank of an N-rank decomposition exchanging with itself (see LoopbackExchanger)
-                o.loopback_ranks = 1
+                # measurement aid: one rank of an N-rank decomposition exchanging with itself (see LoopbackExchanger); "replicated": the model is a box
+                # of nranks exact copies of one period along x (copy k of atom j has id j * nranks + k) and ids follow the copies
+                o.loopback_ranks = 2 if slab.get("replicated") else 1
                 _check(L.aztot_init_device_slab(model.h, C.byref(o), slab["rank"], slab["nranks"], None, SENDRECV_FN(), ALLREDUCE_FN(), None,
                                                 C.byref(self.h)))
             elif idb is not None:

@@ -109,7 +109,7 @@ enum DebugBit : unsigned
     DBG_GENERIC_PAIR = 512,              // the generic (switch-based) pair body instead of a specialised mode
     DBG_KEEP_VDW_CUT_TEST = 1024,        // Lennard-Jones family: keep the per-pair cut-off test although it always passes (family 6, Engine::construct)
     DBG_STAGE_ONLY = 2048,               // NOT result-preserving: the staging pair kernel stages its tile and stops (phase timing)
-    DBG_SLAB_GRAPH = 4096,               // hipGraph replay of a loopback slab rank
+    DBG_SLAB_GRAPH = 4096,               // hipGraph replay of a loopback slab rank that rebuilds its cells every step (options.sort_every = 1; nothing on the lazy schedule)
     DBG_FIXED_INTERVAL = 8192,           // lazy re-sort at the fixed interval options.sort_every whatever the atoms' speed (exercises the wider-stencil fallback)
     DBG_OVERLAP_HALO = 16384,            // slab ranks: coordinate exchange of plain steps on a second stream beside the interior cells' pair forces (measured slower)
     DBG_NO_LISTS = 32768,                // no pair lists: the steps between two rebuilds stage every cell

@@ -328,9 +328,16 @@ void Engine::construct()
     // step into the pair kernel keep the per-atom check there); DBG_CHECK_EVERY_ATOM switches it off
     P_.boundSkip = (lazyOn_ && !fuseNextOk_ && !(debug_ & DBG_CHECK_EVERY_ATOM)) ? 1 : 0;
     if (nranks_ > 1 && !xch_)
-    {   // options.reserved[1]: loopback measurement mode (see LoopbackExchanger)
-        ownedXch_.reset(new LoopbackExchanger((P_.ncxLocal - 2 * P_.hw[0]) * P_.csz[0], P_.L[0], lay_.mig_offset(), lay_.halo_offset(),
-                                              sizeof(MigRec), sizeof(HaloRec)));
+    {   // options.loopback_ranks: loopback measurement mode (see LoopbackExchanger); 2: the model is a box of nranks copies of one period, ids follow the copies
+        int copies = 0;
+        if (opt_.loopback_ranks == 2)
+        {
+            if (model_.nAt % nranks_ != 0 || P_.nc[0] % nranks_ != 0)
+                throw std::runtime_error("slab loopback over a replicated box: atoms and cell layers along x must divide by the number of ranks");
+            copies = nranks_;
+        }
+        ownedXch_.reset(new LoopbackExchanger((P_.ncxLocal - 2 * P_.hw[0]) * P_.csz[0], P_.L[0], rank_ == 0, rank_ == nranks_ - 1, lay_.mig_offset(), lay_.halo_offset(),
+                                              sizeof(MigRec), sizeof(HaloRec), offsetof(MigRec, id), offsetof(HaloRec, id), copies));
         xch_ = ownedXch_.get();
     }
     upload_initial();
@@ -1639,8 +1646,11 @@ int Engine::graph_cycle() const
 
 bool Engine::can_graph() const
 {
-    // slab ranks: only with the loopback transport and only on request (DBG_SLAB_GRAPH) - an experiment, see DESIGN.md section 6
-    const bool slabGraph = nranks_ > 1 && ownedXch_ && (debug_ & DBG_SLAB_GRAPH) && !(P_.nEq > 0 || P_.tstat == AZTOT_TSTAT_NOSE);
+    // slab ranks: only with the loopback transport and only on request (DBG_SLAB_GRAPH) - an experiment, see DESIGN.md section 6.  Only cycles of steps
+    // that all rebuild the cells (options.sort_every = 1): a plain step's coordinate exchange takes its ranges from the host's copy of the halo block
+    // (take_halo_info waits for the read-back the sort posted, adopt_halo_info checks it), which a capture can neither wait for nor bake in - the ranges
+    // change with every sort.  On the lazy schedule the switch does nothing and the steps are launched one by one.
+    const bool slabGraph = nranks_ > 1 && ownedXch_ && (debug_ & DBG_SLAB_GRAPH) && !(P_.nEq > 0 || P_.tstat == AZTOT_TSTAT_NOSE) && !lazyOn_;
     // Replaying captured cycles pays where a step is a handful of microsecond kernels.  On 1 M atoms the kernels are long enough for plain asynchronous
     // launches to keep the GPU busy, and each hipGraphLaunch costs a 40 us bubble in front of its first kernel (rocprofv3 kernel trace): 0.1594 ms/step
     // replayed, 0.1575 launched one by one; 40 000 atoms: 0.0184 replayed, 0.0187 one by one.  (DBG_GRAPH_ALWAYS: replay whatever the size.)

@@ -97,19 +97,37 @@ void CallbackExchanger::allreduce_device(double* dev, int n, hipStream_t stream)
 // ---------------------------------------------------------------------------------------------------
 // loopback transport (measurement aid)
 // ---------------------------------------------------------------------------------------------------
-__global__ void k_loopback_shift(char* msg, size_t migOff, size_t haloOff, size_t migStride, size_t haloStride, double shift, double L)
+// copyShift = -+1 (replicated box, ids j * nCopies + k): the record is the neighbouring copy's atom, copy index k + copyShift modulo nCopies
+__global__ void k_loopback_shift(char* msg, size_t migOff, size_t haloOff, size_t migStride, size_t haloStride, double shift, double L, size_t migIdOff,
+                                 size_t haloIdOff, int copyShift, int nCopies)
 {
     const int32_t* hdr = (const int32_t*)msg;
     const int nMig = hdr[0], nHalo = hdr[1];
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     double* px = nullptr;
-    if (t < nMig) px = (double*)(msg + migOff + (size_t)t * migStride);
-    else if (t - nMig < nHalo) px = (double*)(msg + haloOff + (size_t)(t - nMig) * haloStride);
+    int32_t* pid = nullptr;
+    if (t < nMig)
+    {
+        px = (double*)(msg + migOff + (size_t)t * migStride);
+        pid = (int32_t*)(msg + migOff + (size_t)t * migStride + migIdOff);
+    }
+    else if (t - nMig < nHalo)
+    {
+        px = (double*)(msg + haloOff + (size_t)(t - nMig) * haloStride);
+        pid = (int32_t*)(msg + haloOff + (size_t)(t - nMig) * haloStride + haloIdOff);
+    }
     if (px)
     {
         double x = *px + shift;
         if (x < 0) x += L; else if (x >= L) x -= L;
         *px = x;
+        if (copyShift != 0)
+        {
+            const int id = *pid, k = id % nCopies;
+            int k2 = k + copyShift;
+            if (k2 < 0) k2 += nCopies; else if (k2 >= nCopies) k2 -= nCopies;
+            *pid = id - k + k2;
+        }
     }
 }
 
@@ -119,31 +137,37 @@ void LoopbackExchanger::exchange(int, int, const void* dSendLeft, const void* dS
     HIP_CHECK(hipMemcpyAsync(dFromRight, dSendLeft, bytes, hipMemcpyDeviceToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(dFromLeft, dSendRight, bytes, hipMemcpyDeviceToDevice, stream));
     const int n = (int)((bytes - haloOff_) / haloStride_ + (haloOff_ - migOff_) / migStride_);
-    hipLaunchKernelGGL(k_loopback_shift, dim3((n + 255) / 256), dim3(256), 0, stream, (char*)dFromRight, migOff_, haloOff_, migStride_, haloStride_, w_, L_);
-    hipLaunchKernelGGL(k_loopback_shift, dim3((n + 255) / 256), dim3(256), 0, stream, (char*)dFromLeft, migOff_, haloOff_, migStride_, haloStride_, -w_, L_);
+    hipLaunchKernelGGL(k_loopback_shift, dim3((n + 255) / 256), dim3(256), 0, stream, (char*)dFromRight, migOff_, haloOff_, migStride_, haloStride_, w_, L_,
+                       migIdOff_, haloIdOff_, copies_ ? 1 : 0, copies_);
+    hipLaunchKernelGGL(k_loopback_shift, dim3((n + 255) / 256), dim3(256), 0, stream, (char*)dFromLeft, migOff_, haloOff_, migStride_, haloStride_, -w_, L_,
+                       migIdOff_, haloIdOff_, copies_ ? -1 : 0, copies_);
 }
 
 // one kernel for the whole loopback coordinate exchange (a grouped ncclSend/ncclRecv is one operation too): what goes left comes back from the
 // right, one slab width further along x, and vice versa
 struct LoopArrays { double* a[4]; };
-__global__ void k_loopback_ranges(LoopArrays A, int nArr, int sLb, int sRb, int rLb, int rRb, int nToRight, int nToLeft, double w, double L)
+__global__ void k_loopback_ranges(LoopArrays A, int nArr, int sLb, int sRb, int rLb, int rRb, int nToRight, int nToLeft, double w, double wallRight, double wallLeft)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     for (int k = 0; k < nArr; k++)
     {
         // Between two sorts coordinates stay unwrapped and a ghost moves continuously with its source (the recorded image codes and cell shifts assume
-        // it): the copy is source + slab width + the multiple of L it had at the sort - recovered from the ghost's previous value, which is within an
-        // atom's step of where it belongs.  (Re-wrapping here made a ghost jump by L when its source drifted across the seam: its pairs were missed.)
+        // it): the copy is source + slab width + the multiple of L it was given at the sort.  That multiple is a property of the rank, not of the atom:
+        // the sources are owned atoms, which the sort left inside [xlo, xhi), so k_loopback_shift took every copy that went through the periodic wall -
+        // the right ghosts of the last rank, the left ghosts of rank 0 - back by L and no other (wallRight = -L or 0, wallLeft = +L or 0: the same two
+        // operations in the same order).  (Re-wrapping here made a ghost jump by L when its source drifted across the seam: its pairs were missed.
+        // Recovering the multiple from the ghost's previous value did the same wherever a step's coordinates come from the other set of coordinate
+        // arrays - next-step fusion, the folded drift - whose ghost ranges hold what they held two steps or a sort ago, or nothing yet.)
         if (t < nToRight)
         {   // sent leftward -> arrives as "from the right"
             double v = A.a[k][sLb + t];
-            if (k == 0) { v += w; v += L * nearbyint((A.a[k][rRb + t] - v) / L); }
+            if (k == 0) { v += w; v += wallRight; }
             A.a[k][rRb + t] = v;
         }
         if (t < nToLeft)
         {
             double v = A.a[k][sRb + t];
-            if (k == 0) { v -= w; v += L * nearbyint((A.a[k][rLb + t] - v) / L); }
+            if (k == 0) { v -= w; v += wallLeft; }
             A.a[k][rLb + t] = v;
         }
     }
@@ -156,7 +180,8 @@ void LoopbackExchanger::exchange_ranges(int, int, double* const* arrays, int nAr
     if (nArr > 4) throw std::runtime_error("slab loopback transport: at most 4 arrays per coordinate exchange");
     for (int k = 0; k < nArr; k++) A.a[k] = arrays[k];
     const int nToRight = std::min(sLn, rRn), nToLeft = std::min(sRn, rLn), n = std::max(nToRight, nToLeft);
-    if (n > 0) hipLaunchKernelGGL(k_loopback_ranges, dim3((n + 255) / 256), dim3(256), 0, stream, A, nArr, sLb, sRb, rLb, rRb, nToRight, nToLeft, w_, L_);
+    if (n > 0) hipLaunchKernelGGL(k_loopback_ranges, dim3((n + 255) / 256), dim3(256), 0, stream, A, nArr, sLb, sRb, rLb, rRb, nToRight, nToLeft, w_,
+                                  wallRight_ ? -L_ : 0.0, wallLeft_ ? L_ : 0.0);
 }
 
 void LoopbackExchanger::exchange_counts(int, int, const int32_t* dToLeft, const int32_t* dToRight, int32_t* dFromLeft, int32_t* dFromRight, int n, hipStream_t stream)

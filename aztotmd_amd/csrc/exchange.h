@@ -65,11 +65,20 @@ private:
 // Measurement aid: ONE rank of an N-rank decomposition talks to itself.  What it sends leftward comes back as if the right
 // neighbour had sent it (x shifted by one slab width) and vice versa, so the rank sees the message sizes, ghost counts and
 // kernel shapes of a real N-rank run on a single GPU.  The physics is that of a system made of N copies of this slab.
+// copies > 0 (options.loopback_ranks = 2): the model IS such a system - N exact translates of one period, copy k of atom j having id j * N + k -, so what
+// arrives from the left is the left neighbour's copy (k - 1 modulo N) and what arrives from the right the right neighbour's (k + 1): the rank then holds
+// the ids rank r of a real N-rank run would hold (bond / angle partners across the seam are found, md_to_host fills the atoms that have moved in).  The
+// copy index sits in the low digits on purpose: atoms are sorted by id inside a cell and a plain step's coordinate exchange relies on ghosts and sources
+// being in the same order, which j decides either way (two copies of one atom never share a cell).  copies = 0: ids travel unchanged, an atom that leaves
+// on one side comes back as itself on the other.
 class LoopbackExchanger : public Exchanger
 {
 public:
-    LoopbackExchanger(double slabWidth, double boxLength, size_t migOffset, size_t haloOffset, size_t migStride, size_t haloStride)
-        : w_(slabWidth), L_(boxLength), migOff_(migOffset), haloOff_(haloOffset), migStride_(migStride), haloStride_(haloStride) {}
+    // wallLeft / wallRight: the periodic wall lies between this rank and its left / right neighbour (rank 0 / the last rank)
+    LoopbackExchanger(double slabWidth, double boxLength, bool wallLeft, bool wallRight, size_t migOffset, size_t haloOffset, size_t migStride, size_t haloStride,
+                      size_t migIdOffset = 0, size_t haloIdOffset = 0, int copies = 0)
+        : w_(slabWidth), L_(boxLength), wallLeft_(wallLeft), wallRight_(wallRight), migOff_(migOffset), haloOff_(haloOffset), migStride_(migStride),
+          haloStride_(haloStride), migIdOff_(migIdOffset), haloIdOff_(haloIdOffset), copies_(copies) {}
     void exchange(int left, int right, const void* dSendLeft, const void* dSendRight, void* dFromLeft, void* dFromRight, size_t bytes,
                   hipStream_t stream) override;
     void exchange_ranges(int left, int right, double* const* arrays, int nArr, int sLb, int sLn, int sRb, int sRn, int rLb, int rLn, int rRb, int rRn,
@@ -82,7 +91,9 @@ public:
 
 private:
     double w_, L_;
-    size_t migOff_, haloOff_, migStride_, haloStride_;
+    bool wallLeft_, wallRight_;
+    size_t migOff_, haloOff_, migStride_, haloStride_, migIdOff_, haloIdOff_;
+    int copies_;
 };
 
 class RcclExchanger : public Exchanger

@@ -148,7 +148,20 @@ typedef struct
     int32_t energies_every_step; /* 1: pair energies are booked on every step (0, default: only on the last step of an aztot_step call, the only one whose
                                     statistics the caller can see; forces and trajectories are bit-identical either way) */
     int32_t loopback_ranks;      /* measurement aid for aztot_init_device_slab without a transport: 1 = this rank exchanges its halo with itself
-                                    (one rank of N on one GPU; never a result) */
+                                    (one rank of N on one GPU; never a result): what it sends to one side comes back from the other, one slab width
+                                    along x away, so the physics is that of a system made of N copies of this slab.
+                                    2 = the same for a model that IS such a system - a box of N exact translates of one period along x, copy k of atom j
+                                    having id j * N + k; n_atoms and the cell layers along x must divide by N -: an atom or ghost that arrives from the
+                                    left is the left neighbour's copy (k - 1 modulo N), one from the right the right neighbour's (k + 1).
+                                    The rank then holds the atoms rank r of a real N-rank run of that box would hold, under their ids: bond and angle
+                                    partners across a seam are found, and aztot_md_to_host fills the atoms that moved in.  (With 1 an atom that leaves on
+                                    one side comes back as itself, and a bonded term across a seam finds no partner.)  This is what the tests hold a
+                                    device-side slab rank to: plain NVE with pair, Fennell / direct and bonded forces follows the one-GPU run of the box.
+                                    What does NOT follow any box, with 1 or 2: all-rank sums are rank-local under loopback (the statistics of aztot_get_stats
+                                    are this rank's share; the Ewald structure factor, the Nose-Hoover and equilibration kinetic energy are those of one
+                                    slab alone), and randomness keyed by atom id (the radiative thermostat's draws and photon index) differs between the
+                                    copies of a replicated box, which then stop being copies.  With the Ewald sum, Nose-Hoover, equilibration rescaling or
+                                    the radiative thermostat a loopback rank's timing is meaningful, its physics is not. */
     int32_t reserved[5];         /* must be zero */
 } aztot_options;
 
