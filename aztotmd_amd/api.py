@@ -135,6 +135,7 @@ class DebugBit(enum.IntFlag):
     DBG_FOLD_DRIFT = 8
     DBG_NO_FOLD_DRIFT = 16
     DBG_WIDE_ENTRIES = 32
+    DBG_HITS_BESIDE_TILE = 64
     DBG_KICK_EVERY_STEP = 128
     DBG_LARGE_KICK_PATH = 256
     DBG_GENERIC_PAIR = 512

@@ -104,6 +104,7 @@ enum DebugBit : unsigned
     DBG_FOLD_DRIFT = 8,                  // the next step's drift in the list kernel too (KICK_DRIFT, Engine::foldDriftOk_) whatever the system size: implies what DBG_FOLD_KICK implies ...
     DBG_NO_FOLD_DRIFT = 16,              // ... or off: a folded step is KICK_BOTH with k_drift_plain2 behind it
     DBG_WIDE_ENTRIES = 32,               // pair-list entries stay 16 bits wide where one byte would do (ListStore::narrow_fits)
+    DBG_HITS_BESIDE_TILE = 64,           // k_build_lists keeps its hit array beside the tile and pops a group's hits before the next group's filter (BuildLds: more LDS per wave)
     DBG_KICK_EVERY_STEP = 128,          // k_integrate2 launched every step
     DBG_LARGE_KICK_PATH = 256,           // the deferred half-kick of large systems whatever the size
     DBG_GENERIC_PAIR = 512,              // the generic (switch-based) pair body instead of a specialised mode

@@ -599,6 +599,7 @@ void ListStore::allocate(int candCapNew, int iterCapNew)
     iterCapNew = std::max(kListMinIter, std::min((iterCapNew + 7) & ~7, kListIterMax));
     PairLists probe;
     probe.candCap = probe.candLds = probe.stageLds = candCapNew; probe.iterCap = probe.iterLds = iterCapNew; probe.recBytes = pair_list_rec_bytes(P); probe.waves = waves;
+    probe.buildGroups = (P.debugMask & DBG_HITS_BESIDE_TILE) ? 0 : 1;      // (the capacities are clipped for the smallest mask buffer; the buffer then takes what is left: below)
     while (candCapNew > kListMinCand && (pair_list_lds_bytes(P, probe) > ldsMax_ || build_lists_lds_bytes(probe) > ldsMax_))
     {
         candCapNew -= 64;
@@ -612,6 +613,7 @@ void ListStore::allocate(int candCapNew, int iterCapNew)
     report = mem_.alloc<int32_t>(LR_COUNT, true, stream_); rel = mem_.alloc<float4>((size_t)capacity_ + kWave, true, stream_);
     candCap = candCapNew; iterCap = iterCapNew;
     candLds = stageLds = candCapNew; iterLds = iterCapNew;          // (tightened once the builder has reported what the cells really hold: tighten / adapt)
+    buildGroups = groups_that_fit(4 * waves, stageLds, iterLds);    // (the worst case - 64 atoms per wave - for the first recording only)
     entryBytes = entryNext = 2;                                     // (... and 16-bit entries until then: one-byte entries go with a tile of at most 256 records)
     {   // header: -1 = no list ; second word: the cell's coordinates in the local grid (the kernels decode them with shifts)
         std::vector<int32_t> mx(4 * nc, 0);
@@ -656,6 +658,7 @@ PairLists ListStore::pair_lists() const
     {
         pl.cand = cand; pl.meta = meta; pl.pairs = pairs; pl.noList = report;
         pl.candCap = candCap; pl.iterCap = iterCap; pl.candLds = candLds; pl.stageLds = stageLds; pl.iterLds = iterLds; pl.recBytes = pair_list_rec_bytes(*P_); pl.waves = waves;
+        pl.buildGroups = buildGroups;
         pl.entryBytes = entryBytes; pl.entryScale = entryBytes == 1 ? 1 : pair_list_entry_scale(*P_);      // (one-byte entries are record numbers in every mode)
         pl.rel = rel;
     }
@@ -699,9 +702,32 @@ int ListStore::stage_records_for(int maxStaged) const
     return std::max(4 * kWave, std::min(candCap, (maxStaged + maxStaged / 16 + 4 + 127) & ~127));
 }
 
+// Groups of 16 atoms the builder's mask buffer holds (PairLists::buildGroups) for cells of `want` groups: no more than a cell can have, 4 x waves, and no more
+// than the LDS a workgroup is granted leaves room for beside a staging area and a list buffer of these sizes - cells with more keep no list and are served by
+// the clean-up launch.  LDS per wave bounds the builder's occupancy too and comes in blocks of 1 280 B (tile_records_for): the buffer takes the groups that
+// cost no block more than `want` does, and no others - C4's cells of up to 32 atoms get two groups in seven blocks, 18 waves per CU, where a third would take
+// an eighth.  0 with DBG_HITS_BESIDE_TILE: the builder then runs one group at a time
+int ListStore::groups_that_fit(int want, int stageLdsNew, int iterLdsNew) const
+{
+    if (P_->debugMask & DBG_HITS_BESIDE_TILE) return 0;
+    constexpr size_t kLdsBlock = 1280;
+    PairLists L;
+    L.stageLds = stageLdsNew; L.iterLds = iterLdsNew; L.waves = waves;
+    L.buildGroups = std::max(1, std::min(want, 4 * waves));
+    while (L.buildGroups > 1 && build_lists_lds_bytes(L) > ldsMax_) L.buildGroups--;
+    const size_t blocks = (build_lists_lds_bytes(L) + kLdsBlock - 1) / kLdsBlock;
+    while (L.buildGroups < 4 * waves)
+    {
+        L.buildGroups++;
+        if ((build_lists_lds_bytes(L) + kLdsBlock - 1) / kLdsBlock > blocks || build_lists_lds_bytes(L) > ldsMax_) { L.buildGroups--; break; }
+    }
+    return L.buildGroups;
+}
+
 // LDS per wave is what bounds the occupancy of k_pair_list: its tile is sized from the largest KEPT candidate set ever recorded, not from the capacity of
-// the arrays; the builder's staging area from the largest STAGED set, its list buffer from the longest list (+ 1/8)
-void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& stageLdsNew, int& iterLdsNew) const
+// the arrays; the builder's staging area from the largest STAGED set, its list buffer from the longest list (+ 1/8), its mask buffer from the most atoms
+// a cell held, in whole groups of 16
+void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& stageLdsNew, int& iterLdsNew, int& groupsNew) const
 {
     candLdsNew = tile_records_for(rep[LR_MAX_TILE]);
     stageLdsNew = stage_records_for(rep[LR_MAX_STAGED]);
@@ -709,6 +735,7 @@ void ListStore::lds_for(const int32_t* rep, int& candLdsNew, int& stageLdsNew, i
     // (one-byte entries are read out sixteen iterations at a time: whole chunks where the capacity allows.  A cell's stride in `pairs`, iterCap x 128 B, holds
     //  2 iterCap one-byte iterations, so any iterCap >= 16 keeps whole chunks of them inside it)
     if (entryNext == 1 && ((iterLdsNew + 15) & ~15) <= iterCap) iterLdsNew = (iterLdsNew + 15) & ~15;
+    groupsNew = groups_that_fit((rep[LR_MAX_ATOMS] + 15) / 16, stageLdsNew, iterLdsNew);
 }
 
 bool ListStore::narrow_fits(int maxTile, int candLdsNew, int wavesNew) const
@@ -719,19 +746,22 @@ bool ListStore::narrow_fits(int maxTile, int candLdsNew, int wavesNew) const
 bool ListStore::tighten(const int32_t* rep, bool* formatChanged)
 {
     if (formatChanged) *formatChanged = false;
-    if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_KEPT_FULL] != 0 || rep[LR_MAX_STAGED] <= 0) return false;
-    int c, s, i;
-    lds_for(rep, c, s, i);
+    if (rep[LR_TILE_FULL] != 0 || rep[LR_LIST_FULL] != 0 || rep[LR_KEPT_FULL] != 0 || rep[LR_MASK_FULL] != 0 || rep[LR_MAX_STAGED] <= 0) return false;
+    int c, s, i, g;
+    lds_for(rep, c, s, i, g);
     bool changed = false;
     if (entryNext == 2 && narrow_fits(rep[LR_MAX_TILE], std::min(candLds, c), waves))
     {   // the lists just recorded hold 16-bit entries: the caller records them again
         entryNext = 1;
-        lds_for(rep, c, s, i);
+        lds_for(rep, c, s, i, g);
         changed = true;
         if (formatChanged) *formatChanged = true;
     }
-    if (c >= candLds && s >= stageLds && i >= iterLds) return changed;
-    candLds = std::min(candLds, c); stageLds = std::min(stageLds, s); iterLds = std::min(iterLds, i);
+    if (c >= candLds && s >= stageLds && i >= iterLds && g >= buildGroups) return changed;
+    candLds = std::min(candLds, c); stageLds = std::min(stageLds, s); iterLds = std::min(iterLds, i); buildGroups = std::min(buildGroups, g);
+    if (std::getenv("AZTOT_VERBOSE"))
+        std::fprintf(stderr, "aztot: list LDS sized from the first recording: tile %d, staging %d, %d iterations, %d mask groups: %zu B (list kernel) / %zu B (builder)\n", candLds, stageLds, iterLds,
+                     buildGroups, pair_list_lds_bytes(*P_, pair_lists()), build_lists_lds_bytes(pair_lists()));
     return true;
 }
 
@@ -752,18 +782,23 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
     // (LR_UNLISTED_NOW stays: it describes the lists in force; the maxima are all-time)
     HIP_CHECK(hipMemsetAsync(&report[LR_UNLISTED], 0, sizeof(int32_t) * 2, stream_));
     HIP_CHECK(hipMemsetAsync(&report[LR_TILE_FULL], 0, sizeof(int32_t) * 3, stream_));
-    // ("tile full": the staged candidates did not fit the builder's staging area; "kept full": the kept ones did not fit the tile of k_pair_list)
-    const int tileFull = rep[LR_TILE_FULL], keptFull = rep[LR_KEPT_FULL], listFull = rep[LR_LIST_FULL], recorded = rep[LR_RECORDED], unlisted = rep[LR_UNLISTED];
+    HIP_CHECK(hipMemsetAsync(&report[LR_MASK_FULL], 0, sizeof(int32_t), stream_));
+    // ("tile full": the staged candidates did not fit the builder's staging area; "kept full": the kept ones did not fit the tile of k_pair_list; "mask full":
+    //  more groups of 16 atoms than the builder's mask buffer holds)
+    const int tileFull = rep[LR_TILE_FULL], keptFull = rep[LR_KEPT_FULL], listFull = rep[LR_LIST_FULL], maskFull = rep[LR_MASK_FULL], recorded = rep[LR_RECORDED], unlisted = rep[LR_UNLISTED];
     if (std::getenv("AZTOT_VERBOSE"))
-        std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: staging full, %d: tile full, %d: list full); most staged %d of %d (LDS %d), largest tile %d (LDS %d), longest list %d of %d (LDS %d)\n",
-                     recorded, unlisted, tileFull, keptFull, listFull, rep[LR_MAX_STAGED], candCap, stageLds, rep[LR_MAX_TILE], candLds, rep[LR_MAX_ITERS], iterCap, iterLds);
+        std::fprintf(stderr, "aztot: lists recorded since the last look: %d cells, %d of them without a list (%d: staging full, %d: tile full, %d: list full, %d: mask buffer full); most staged %d of %d (LDS %d), largest tile %d (LDS %d), longest list %d of %d (LDS %d), most atoms %d (LDS %d groups, builder %zu B)\n",
+                     recorded, unlisted, tileFull, keptFull, listFull, maskFull, rep[LR_MAX_STAGED], candCap, stageLds, rep[LR_MAX_TILE], candLds, rep[LR_MAX_ITERS], iterCap, iterLds, rep[LR_MAX_ATOMS], buildGroups,
+                     build_lists_lds_bytes(pair_lists()));
     // A cell that does not fit next time keeps no list for one interval (exact: the clean-up launch serves it) and is counted; then the tiles grow again.
-    int candLdsNew, stageLdsNew, iterLdsNew;
-    lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew);
+    int candLdsNew, stageLdsNew, iterLdsNew, groupsNew;
+    lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew, groupsNew);
     if (tileFull > 0) stageLdsNew = std::min(candCap, std::max(stageLdsNew, stageLds + 128));
     if (keptFull > 0) candLdsNew = std::min(candCap, std::max(candLdsNew, candLds + 32));
     if (listFull > 0) iterLdsNew = std::min(iterCap, std::max(iterLdsNew, iterLds + 8));
-    if (frozen) { candLdsNew = candLds; stageLdsNew = stageLds; iterLdsNew = iterLds; }
+    // (the mask buffer follows the largest cell reported, which the cells that did not fit reported too; staging area and list buffer may have grown beside it)
+    groupsNew = groups_that_fit((rep[LR_MAX_ATOMS] + 15) / 16, stageLdsNew, iterLdsNew);
+    if (frozen) { candLdsNew = candLds; stageLdsNew = stageLds; iterLdsNew = iterLds; groupsNew = buildGroups; }
     // more waves per cell where the cells turn out denser than the mean density promised (a droplet in a large box - case study 2: tiles of 1 487
     // candidates, lists of 210 iterations where the homogeneous estimate said 1 wave would do): decided from what the builder recorded
     const int wWant = std::max(waves, waves_wanted((double)rep[LR_MAX_TILE], rep[LR_MAX_ITERS]));
@@ -777,11 +812,11 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
         entryNext = 2; wideForGood_ = true;
         v.rebuild = v.launchChanged = true;
     }
-    else if (entryNext == 2 && !frozen && tileFull + keptFull + listFull == 0 && narrow_fits(rep[LR_MAX_TILE], candLdsNew, wavesNew))
+    else if (entryNext == 2 && !frozen && tileFull + keptFull + listFull + maskFull == 0 && narrow_fits(rep[LR_MAX_TILE], candLdsNew, wavesNew))
     {
         entryNext = 1;
         v.launchChanged = true;
-        lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew);
+        lds_for(rep, candLdsNew, stageLdsNew, iterLdsNew, groupsNew);
     }
     if (wWant > waves && !forcedWaves_ && !frozen)
     {   // (what was recorded describes lists that no longer exist: nothing more to decide now)
@@ -803,12 +838,12 @@ ListStore::Verdict ListStore::adapt(const int32_t* rep, unsigned debug)
         v.launchChanged = true;
         if (growths < 3 && (candNew > candCap || itersNew > iterCap)) { growths++; regrow(candNew, itersNew); v.rebuild = true; }
     }
-    else if (candLdsNew != candLds || stageLdsNew != stageLds || iterLdsNew != iterLds)
+    else if (candLdsNew != candLds || stageLdsNew != stageLds || iterLdsNew != iterLds || groupsNew != buildGroups)
     {
-        candLds = candLdsNew; stageLds = stageLdsNew; iterLds = iterLdsNew;
+        candLds = candLdsNew; stageLds = stageLdsNew; iterLds = iterLdsNew; buildGroups = groupsNew;
         v.launchChanged = true;               // (launch parameters are baked into the graphs)
     }
-    if (on && (double)unlisted > 0.02 * (double)recorded && !frozen && tileFull + keptFull + listFull < unlisted / 2)
+    if (on && (double)unlisted > 0.02 * (double)recorded && !frozen && tileFull + keptFull + listFull + maskFull < unlisted / 2)
     {   // mostly cells of more than 64 atoms: no list will ever hold them
         on = false;
         v.launchChanged = true;

@@ -30,6 +30,8 @@ struct ListStore
     int candLds = 0, iterLds = 0;   // what the LDS tile of k_pair_list (the candidates a cell KEEPS) and the builder's list buffer are sized for (<= the capacities;
                                     // from the largest cell recorded)
     int stageLds = 0;               // what the builder's staging area is sized for: the candidates a cell STAGES before the unreachable ones are dropped (<= candCap)
+    int buildGroups = 0;            // groups of 16 atoms whose hit masks the builder parks in LDS (PairLists::buildGroups): the worst case, 4 x waves, until a report says how
+                                    // many atoms the largest cell holds; 0 with DBG_HITS_BESIDE_TILE
     int waves = 1;                  // waves per cell in k_pair_list (PairLists::waves)
     int growths = 0;
     // Bytes per pair-list entry (PairLists::entryBytes).  entryBytes: the format of the lists on the device, what k_pair_list is launched with; entryNext: the
@@ -46,7 +48,7 @@ struct ListStore
     void release() noexcept;        // behind a stream synchronisation
     PairLists pair_lists() const;   // what the kernels are launched with (all-null when off)
     // LDS sizes that hold the largest cell of a report
-    void lds_for(const int32_t* rep, int& candLds, int& stageLds, int& iterLds) const;
+    void lds_for(const int32_t* rep, int& candLds, int& stageLds, int& iterLds, int& buildGroups) const;
     // the first lists of an engine's life: tighter LDS sizes right away, if every cell fitted.  True when launch parameters changed; *formatChanged when
     // entryNext differs from the format those lists were recorded in (the caller records them again)
     bool tighten(const int32_t* rep, bool* formatChanged = nullptr);
@@ -62,6 +64,7 @@ private:
     void allocate(int candCap, int iterCap);
     int tile_records_for(int maxT) const;
     int stage_records_for(int maxStaged) const;
+    int groups_that_fit(int want, int stageLds, int iterLds) const;
     int waves_wanted(double tileRecords, int iters) const;
     DeviceArena mem_;
     const StepParams* P_ = nullptr; // the engine's (outlives the store)

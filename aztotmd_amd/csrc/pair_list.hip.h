@@ -518,42 +518,65 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
 // exceed iterCap or that holds more than 64 atoms per wave keeps no list (header -1): the clean-up launch of k_pair_tile stages it on every step, and
 // the engine grows the capacities when that happens.  A cell whose atoms reach nobody keeps a list with T = 0: k_pair_list writes its forces as zero.
 // ---------------------------------------------------------------------------------------------------------------------------------------------
-constexpr int kBuildEntRegs = 8;           // k_build_lists: list entries of up to 512 staged candidates wait in registers while the filter runs
+constexpr int kBuildEntRegsBeside = 8;     // ... 512 with DBG_HITS_BESIDE_TILE, as that layout always had
+constexpr int kBuildEntRegs = 12;          // k_build_lists: list entries of up to 768 staged candidates wait in registers while the filter runs
 struct BuildLds
 {
     int capS;            // floats per coordinate array: stageLds rounded up to whole mask words (the matrix filter reads 8 blocks of 16 candidates at a time)
     int nWords;          // 32-bit hit-mask words per lane and atom group: capS / 128
     int hitCap;          // entries of the compact hit array: iterLds x 64 x waves per cell
     int nTab;            // entries of each of the three small tables (staging table: <= 64 runs ; per atom of the cell: <= 64 x waves)
-    __host__ __device__ BuildLds(int stageLds, int iterLds, int waves)
-        : capS((stageLds + 127) & ~127), nWords((stageLds + 127) / 128), hitCap(iterLds * kWave * waves), nTab(kWave * waves) {}
-    // The staged candidates' list entries outlive the filter (only then is it known who is kept), which fills the hit array.  Up to kBuildEntRegs x 64 staged
-    // candidates they wait in registers meanwhile and the hit array takes their place in LDS (a liquid's cells: LDS per wave bounds the builder's occupancy
-    // too); larger staging areas keep both
-    __host__ __device__ bool ent_in_regs() const { return capS <= kBuildEntRegs * kWave; }
-    __host__ __device__ size_t ent_hit_bytes() const
+    int groups;          // groups of 16 atoms whose hit masks are parked (PairLists::buildGroups); 0: one in flight, and the hit array beside the tile
+    __host__ __device__ BuildLds(int stageLds, int iterLds, int waves, int buildGroups)
+        : capS((stageLds + 127) & ~127), nWords((stageLds + 127) / 128), hitCap(iterLds * kWave * waves), nTab(kWave * waves), groups(buildGroups) {}
+    // LDS per wave bounds the builder's occupancy (a chain of dependent LDS round trips: its time goes as 1 / waves per CU), so nothing lives longer than it
+    // must.  The TILE serves the matrix filter and nothing else: every group's filter runs before the first hit is popped, the groups' hit masks wait in the
+    // mask buffer, and the compact hit array then takes the tile's bytes - behind the first 2 capS of them, where the keep pass writes the renumbering while
+    // the hit array is live.  The staged candidates' list ENTRIES outlive the filter (only then is it known who is kept).  Up to kBuildEntRegs x 64 staged
+    // candidates they wait in registers meanwhile, and their place in LDS is the mask buffer's (a liquid's cells); larger staging areas keep both.
+    //   front:  tile 16 capS  |  renumbering 2 capS, hit array 2 hitCap        (whichever is larger)
+    //   middle: entries 4 capS  |  masks 256 nWords groups                      (entries in registers: whichever is larger ; else both)
+    //   tables: 3 x 4 nTab
+    // groups == 0 (DBG_HITS_BESIDE_TILE), the layout this one replaced: tile, entries | hit array (in registers: whichever is larger ; else both), the masks of
+    // the one group in flight, tables
+    __host__ __device__ bool ent_in_regs() const { return capS <= (beside() ? kBuildEntRegsBeside : kBuildEntRegs) * kWave; }
+    __host__ __device__ bool beside() const { return groups == 0; }
+    __host__ __device__ size_t tile_bytes() const { return sizeof(float) * 4 * (size_t)capS; }
+    __host__ __device__ size_t ent_bytes() const { return sizeof(uint32_t) * (size_t)capS; }
+    __host__ __device__ size_t hit_bytes() const { return (sizeof(uint16_t) * (size_t)hitCap + 15) & ~(size_t)15; }
+    __host__ __device__ size_t remap_bytes() const { return sizeof(uint16_t) * (size_t)capS; }                  // (capS is a multiple of 128: 16-byte aligned)
+    __host__ __device__ size_t mask_bytes() const { return sizeof(uint32_t) * (size_t)nWords * kWave * (size_t)(groups > 0 ? groups : 1); }
+    __host__ __device__ size_t ent_off() const { return beside() || tile_bytes() > remap_bytes() + hit_bytes() ? tile_bytes() : remap_bytes() + hit_bytes(); }
+    __host__ __device__ size_t hit_off() const { return !beside() ? remap_bytes() : ent_in_regs() ? ent_off() : ent_off() + ent_bytes(); }
+    __host__ __device__ size_t mask_off() const
     {
-        const size_t a = sizeof(uint32_t) * (size_t)capS, b = sizeof(uint16_t) * (size_t)hitCap;
-        return ((ent_in_regs() ? (a > b ? a : b) : a + b) + 15) & ~(size_t)15;
+        if (!beside()) return ent_in_regs() ? ent_off() : ent_off() + ent_bytes();
+        return ent_off() + (ent_in_regs() ? (ent_bytes() > hit_bytes() ? ent_bytes() : hit_bytes()) : ent_bytes() + hit_bytes());
     }
-    // tile, entries + hit array, hit masks of the group in flight, the three small tables
-    __host__ __device__ size_t bytes() const { return sizeof(float) * 4 * (size_t)capS + ent_hit_bytes() + sizeof(uint32_t) * (size_t)nWords * kWave + sizeof(int32_t) * 3 * (size_t)nTab; }
+    __host__ __device__ size_t tab_off() const
+    {
+        if (!beside() && ent_in_regs()) return ent_off() + (ent_bytes() > mask_bytes() ? ent_bytes() : mask_bytes());
+        return mask_off() + mask_bytes();
+    }
+    __host__ __device__ size_t bytes() const { return tab_off() + sizeof(int32_t) * 3 * (size_t)nTab; }
 };
 
 __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32_t* __restrict__ cellStart, int firstCell, int nCellsRun, PairLists L)
 {
     extern __shared__ float ldsBuild[];
     const int W = L.waves;
-    const BuildLds G(L.stageLds, L.iterLds, W);
+    const BuildLds G(L.stageLds, L.iterLds, W, L.buildGroups);
+    char* const lds = (char*)ldsBuild;
     float4* const tile = (float4*)ldsBuild;                         // {x, y, z, -(x^2 + y^2 + z^2)} of every staged candidate, relative to the cell centre: one 16-byte store each;
                                                                     // lane (row c, component k) of the matrix operand reads float 4 (16 b + perm(c)) + k: 64 different banks
     uint16_t* const remap = (uint16_t*)ldsBuild;                    // ... and, once the filter has run: staged candidate number -> list entry of its record in k_pair_list's tile
-    uint32_t* const tent = (uint32_t*)(tile + G.capS);              // list entries of the staged candidates (atom index | image code << 26), tile order ...
-    const bool entInRegs = G.ent_in_regs();                         // ... which wait in registers while the filter runs, if they are few enough (BuildLds) ...
-    uint16_t* const hits = (uint16_t*)(entInRegs ? tent : tent + G.capS);      // ... and leave their place to the compact hit array (staged candidate numbers, atom by atom)
-    uint32_t* const maskBuf = (uint32_t*)((char*)tent + G.ent_hit_bytes());    // [nWords][64] hit masks of the atom group in flight
-    int32_t* const entJ = (int32_t*)(maskBuf + (size_t)G.nWords * kWave);      // staging table: first atom, count (<= 64), codes ; later, per atom of the cell:
-    int32_t* const entN = entJ + G.nTab;                            //   tile slot / offset / hit count
+    uint32_t* const tent = (uint32_t*)(lds + G.ent_off());          // list entries of the staged candidates (atom index | image code << 26), tile order ...
+    const bool entInRegs = G.ent_in_regs();                         // ... which wait in registers while the filter runs, if they are few enough (BuildLds)
+    const bool beside = G.beside();                                 // (DBG_HITS_BESIDE_TILE)
+    uint16_t* const hits = (uint16_t*)(lds + G.hit_off());          // the compact hit array (staged candidate numbers, atom by atom): in the tile's bytes once every group's filter has run
+    uint32_t* const maskBuf = (uint32_t*)(lds + G.mask_off());      // [groups][nWords][64] hit masks of the cell's atom groups
+    int32_t* const entJ = (int32_t*)(lds + G.tab_off());            // staging table: first atom, count (<= 64), codes ; later, per atom of the cell:
+    int32_t* const entN = entJ + G.nTab;                            //   tile slot, then hit counts of its quarters / offset / hit count
     int32_t* const entC = entN + G.nTab;
 
     const int lane = threadIdx.x;
@@ -569,7 +592,11 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     const int nthis = ie - ib;
     if (nthis == 0) { if (lane == 0) L.meta[4 * cell] = 0; return; }            // an empty cell: a list with nothing in it
     auto no_list = [&](int why) { if (lane == 0) { L.meta[4 * cell] = -1; atomicAdd(&L.noList[LR_UNLISTED], 1); atomicAdd(&L.noList[LR_UNLISTED_NOW], 1); if (why != LR_NONE) atomicAdd(&L.noList[why], 1); } };
-    if (nthis > kWave * W) { no_list(LR_NONE); return; }                 // (W waves of k_pair_list share the cell: up to 64 atoms each)
+    auto report_atoms = [&]() { if (lane == 0 && nthis > L.noList[LR_MAX_ATOMS]) atomicMax(&L.noList[LR_MAX_ATOMS], nthis); };
+    if (nthis > kWave * W) { report_atoms(); no_list(LR_NONE); return; }      // (W waves of k_pair_list share the cell: up to 64 atoms each)
+    // (more groups of 16 atoms than the mask buffer holds: no list this time - the clean-up launch serves the cell -, and the engine sizes the buffer from the
+    //  largest cell reported at its next look)
+    if (!beside && nthis > 16 * G.groups) { report_atoms(); no_list(LR_MASK_FULL); return; }
     const int RECB = L.entryScale;                                  // record number -> list entry (k_pair_list's mode decides: byte offset or number)
     const int stageLds = L.stageLds;
     const float cs0 = (float)P.csz[0], cs1 = (float)P.csz[1], cs2 = (float)P.csz[2];
@@ -731,7 +758,8 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
     // the per-candidate term rides in the A operand, so a block costs ONE LDS read per lane and no operand selects
     const float* const pa = (const float*)tile + 4 * permc + kq;
     int nIter = 0, hitBase = 0, tooLong = 0;
-    for (int g0 = 0; g0 < nthis; g0 += 16)
+    // one group's matrix filter: its hit masks go to mb, its atoms' offsets and counts to the tables; returns where this lane's hits go in the hit array
+    auto filter_group = [&](int g0, uint32_t* mb) -> int
     {
         const int a = g0 + c16;
         const bool validA = a < nthis;
@@ -764,7 +792,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
             uint32_t m = ~miss;
             // the atom itself is a candidate of its own tile (always a hit): not a partner
             if (kSelf >= 0 && (kSelf & 3) == kq && (kSelf >> 7) == wd) m &= ~(0x80000000u >> ((kSelf & 127) >> 2));
-            maskBuf[wd * kWave + lane] = m;
+            mb[wd * kWave + lane] = m;
             h += __popc(m);
             // who is hit by anybody: OR over the 16 atoms of the group (the lanes of one kq are one DPP row: four rotations), then into the cell's keep word
             uint32_t any = m;
@@ -775,13 +803,14 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
             if (c16 == wd) keepAcc |= any;
         }
         // where this lane's hits go: behind those of the lower quarters of its atom, which come behind the atoms before it
-        int below = 0, total = 0;
+        int below = 0, total = 0, quarters = 0;
 #pragma unroll
         for (int q = 0; q < 4; q++)
         {
             const int hq = __shfl(h, c16 | (q << 4), kWave);
             below += (q < kq) ? hq : 0;
             total += hq;
+            if (q < 3) quarters |= hq << (10 * q);                   // (a quarter holds at most 32 candidates per mask word, 15 words: 480)
         }
         if (!validA) total = 0;
         int incl = total;                                            // inclusive scan over the 16 atoms of the group (every quarter computes the same)
@@ -789,21 +818,57 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         for (int o = 1; o < 16; o <<= 1) { const int up = __shfl_up(incl, o, 16); if (c16 >= o) incl += up; }
         const int myOff = hitBase + incl - total;
         hitBase += __shfl(incl, 15, 16);
-        if (validA && kq == 0) { entN[a] = myOff; entC[a] = total; }
+        // (the atom's tile slot has served - every quarter read it above -: its place keeps the quarters' hit counts for the pop that comes after every group's filter)
+        if (validA && kq == 0) { entJ[a] = quarters; entN[a] = myOff; entC[a] = total; }
         nIter = max(nIter, ((total + NS - 1) * rcpNS) >> 16);
-        if (hitBase > G.hitCap) { tooLong = 1; break; }              // (wave-uniform)
-        if ((P.debugMask & DBG_BUILD_PHASE_MASK) == 2) continue;                           // (phase timing: no compaction)
-        // bit 31 - p of word wd is the staged candidate 128 wd + kq + 4 p
-        uint16_t* dst = hits + myOff + below;
+        if (hitBase > G.hitCap) tooLong = 1;                         // (wave-uniform)
+        return myOff + below;
+    };
+    // ... and its compaction: every lane pops its hits, in the order quarter, word, bit.  Bit 31 - p of word wd is the staged candidate 128 wd + kq + 4 p
+    auto pop_group = [&](const uint32_t* mb, int at)
+    {
+        uint16_t* dst = hits + at;
         for (int wd = 0; wd < nW; wd++)
         {
-            uint32_t cur = maskBuf[wd * kWave + lane];
+            uint32_t cur = mb[wd * kWave + lane];
             const int base = 128 * wd + kq;
             while (cur != 0u)
             {
                 const int p = __clz(cur);
                 cur &= ~(0x80000000u >> p);
                 *dst++ = (uint16_t)(base + p * 4);
+            }
+        }
+    };
+    const bool compact = (P.debugMask & DBG_BUILD_PHASE_MASK) != 2;                        // (phase timing: no compaction)
+    if (beside)
+    {   // (DBG_HITS_BESIDE_TILE) group by group: the hit array lives beside the tile
+        for (int g0 = 0; g0 < nthis && !tooLong; g0 += 16)
+        {
+            const int at = filter_group(g0, maskBuf);
+            if (!tooLong && compact) pop_group(maskBuf, at);
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    else
+    {
+        const int groupWords = G.nWords * kWave;
+        uint32_t* mb = maskBuf;
+        for (int g0 = 0; g0 < nthis && !tooLong; g0 += 16, mb += groupWords) filter_group(g0, mb);
+        __builtin_amdgcn_wave_barrier();                            // (the tile has served: its place takes the hit array)
+        if (!tooLong && compact)
+        {
+            mb = maskBuf;
+            for (int g0 = 0; g0 < nthis; g0 += 16, mb += groupWords)
+            {
+                const int a = g0 + c16;
+                int at = 0;
+                if (a < nthis)
+                {   // (idle atom slots hit nobody)
+                    const int quarters = entJ[a];
+                    at = entN[a] + (kq > 0 ? quarters & 1023 : 0) + (kq > 1 ? (quarters >> 10) & 1023 : 0) + (kq > 2 ? quarters >> 20 : 0);
+                }
+                pop_group(mb, at);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -898,6 +963,7 @@ __global__ __launch_bounds__(kWave) void k_build_lists(StepParams P, const int32
         if (T > L.noList[LR_MAX_STAGED]) atomicMax(&L.noList[LR_MAX_STAGED], T);       // (a read first: after the first few cells nobody has a new record to report)
         if (kept > L.noList[LR_MAX_TILE]) atomicMax(&L.noList[LR_MAX_TILE], kept);
         if (usable && nIter > L.noList[LR_MAX_ITERS]) atomicMax(&L.noList[LR_MAX_ITERS], nIter);
+        if (nthis > L.noList[LR_MAX_ATOMS]) atomicMax(&L.noList[LR_MAX_ATOMS], nthis);
         if (P.debugMask & DBG_LIST_STATS)
         {   // measurement aid (slow)
             atomicAdd(&L.noList[LR_SUM_ITERS], nIter); atomicAdd(&L.noList[LR_SUM_CANDS], kept); atomicAdd(&L.noList[LR_SUM_ATOMS], nthis); atomicAdd(&L.noList[LR_SUM_STAGED], T);
@@ -912,10 +978,10 @@ inline void launch_build_lists(const PairLaunch& C, PairRange R, PairLists L)
 {
     pair_range_default(C.P, R);
     if (R.n == 0) return;
-    const BuildLds G(L.stageLds, L.iterLds, L.waves);
+    const BuildLds G(L.stageLds, L.iterLds, L.waves, L.buildGroups);
     hipLaunchKernelGGL(k_build_lists, dim3(pair_range_grid(R.n)), dim3(kWave), G.bytes(), C.stream, C.P, C.cellStart, R.first, R.n, L);
 }
-inline size_t build_lists_lds_bytes(const PairLists& L) { return BuildLds(L.stageLds, L.iterLds, L.waves).bytes(); }
+inline size_t build_lists_lds_bytes(const PairLists& L) { return BuildLds(L.stageLds, L.iterLds, L.waves, L.buildGroups).bytes(); }
 
 template <int MODE, int VDW>
 inline void launch_pair_list_as(const PairLaunch& C, PairRange R, PairLists L, NextStep N, bool energies)

@@ -432,6 +432,8 @@ enum ListReport : int
     LR_SUM_ITERS = 8, LR_SUM_CANDS = 9, LR_SUM_ATOMS = 10, LR_SUM_STAGED = 11,     // DBG_LIST_STATS: totals over the cells recorded (four in a row: cleared together)
     LR_MAX_STAGED = 12,     // largest number of candidates a cell staged (box-pruned, before the unreachable ones were dropped) ever recorded
     LR_OVER_16 = 13,        // DBG_LIST_STATS: cells recorded with more than 16 list iterations (a second chunk of one-byte entries); cleared with the totals
+    LR_MAX_ATOMS = 14,      // most atoms a cell held ever recorded (what the builder's mask buffer is sized from: PairLists::buildGroups)
+    LR_MASK_FULL = 15,      // cells with more groups of 16 atoms than the builder's mask buffer holds since the host last looked
     LR_COUNT = 16,
     LR_NONE = -1            // (k_build_lists: a cell without a list that no counter of its own explains - more than 64 atoms per wave)
 };
@@ -454,6 +456,8 @@ struct PairLists
                                    //      seen, because LDS per wave is what bounds the occupancy of k_pair_list (7.7 KiB: 95 us, 10.8 KiB: 106 us on the 1 M-atom box)
     int32_t stageLds = 0;          // candidates the builder's staging area holds (>= candLds, <= candCap): from the largest STAGED count seen
     int32_t iterLds = 0;           // iterations the builder's LDS list buffer holds (multiple of 8, <= iterCap)
+    int32_t buildGroups = 0;       // groups of 16 atoms whose hit masks the builder parks in LDS while the tile is live (<= 4 x waves: from the largest cell seen);
+                                   //      0: one group in flight and the hit array beside the tile (DBG_HITS_BESIDE_TILE)
     int32_t waves = 1;             // waves per cell in k_pair_list (1, 2 or 4): they share ONE tile and split the cell's atoms - where a cell's candidates are
                                    //      many and the cells few (dense systems, slab ranks), LDS per wave and wave lifetime are what bounds the kernel.
                                    //      `pairs` then holds `waves` lists per cell ([nCell][waves][iterCap * 64])
