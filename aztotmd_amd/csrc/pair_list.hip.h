@@ -190,9 +190,12 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     // (candidate groups are dealt to the waves round-robin: wave w gathers groups w, w + W, ...; candCap >= 64 * 5 * W keeps the preloads inside the array)
     const uint32_t* const myList = L.cand + (size_t)cell * L.candCap + lane;
     const uint4* const pl = (const uint4*)(L.pairs + ((size_t)cell * W + wave) * L.iterCap * kWave) + lane;
+    // one wave and four groups: the FOURTH group's entries are asked for below, once the header has said that the group holds a candidate (T > 192).  A
+    // liquid's cells keep ~160 candidates: in most of them the group is 256 B of padding that nobody needs to load (17.6 MB per launch on the 1 M-atom box)
+    constexpr bool kLazyLast = PRE == 4 && !MULTI;
     uint32_t ent[PRE];
 #pragma unroll
-    for (int u = 0; u < PRE; u++) ent[u] = myList[(wave + u * W) * kWave];
+    for (int u = 0; u < PRE; u++) ent[u] = (kLazyLast && u == PRE - 1) ? 0u : myList[(wave + u * W) * kWave];
     uint4 w = pl[0];
     uint4 w1 = make_uint4(0u, 0u, 0u, 0u);
     if (EB == 2) w1 = pl[kWave];                                    // (the second chunk too: 16 iterations cover a liquid's cells, and a chunk asked for only
@@ -212,6 +215,16 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
     if (meta > 0)
     {
         const int T = meta & 0xFFF, nIter = (meta >> 12) & 0xFF;
+        // the last group up front holds a candidate (wave-uniform).  A wave that skips it loads no entries, fetches no coordinates and leaves records
+        // 193 .. candLds of its tile unwritten.  No list entry of such a cell names them: k_build_lists writes whole chunks (every lane's 16 bytes of every
+        // chunk below nIter), each entry the record of a KEPT candidate - n + 1 <= T - or 0, the dummy; the walk reads no chunk at or above nIter, and the
+        // read ahead behind a list's last chunk is the dummy's (below) - stale entries of an older, larger list are never looked up
+        const bool lastGroup = !kLazyLast || T > (PRE - 1) * kWave;
+        if (kLazyLast)
+        {   // (in front of the gather and behind a barrier, like chunk 1 below)
+            if (lastGroup) ent[PRE - 1] = myList[(PRE - 1) * kWave];
+            if (EB != 1) asm volatile("" ::: "memory");
+        }
         if (EB == 1)
         {   // one-byte entries: the second chunk, for the cells that have one (wave-uniform).  Asked for here, in front of the gather, so that it travels with
             // the coordinates; the barrier keeps the compiler from sinking the load behind the LDS writes (as it once did with a conditional preload of
@@ -260,8 +273,9 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         int ti = 0;
         if (!kOneSpecies) ti = A.type[myl];
         if ((MODE == PM_GENERIC && P.use_radii) || MODE == PM_ONE_SURK) radi = A.rad[myl];
-        // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  PRE groups are gathered whatever T is (stale
-        // entries are atom indices too: the array starts out zeroed and only indices are ever written); all their loads travel together
+        // ---- gather the candidates (groups of 64; the builder padded the last group with a valid atom).  PRE groups are gathered whatever T is - but for the
+        // fourth of a one-wave, four-group kernel, lastGroup above - (stale entries are atom indices too: the array starts out zeroed and only indices are ever
+        // written); all their loads travel together
         const int gx0 = lx + P.cx0;
         // does any neighbour cell lie across a periodic boundary (or the seam of a slab ring)?  wave-uniform
         const bool images = gx0 - P.hw[0] < 0 || gx0 + P.hw[0] >= P.nc[0] || cy - P.hw[1] < 0 || cy + P.hw[1] >= ncy || cz - P.hw[2] < 0 || cz + P.hw[2] >= ncz;
@@ -293,23 +307,23 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
             };
             // this wave's groups are wave + q W, q = 0, 1, ...  PRE of them are gathered whatever T is - straight-line code, 3 PRE loads in flight together
             // (the builder fills all PRE groups of the array: behind the last candidate with the cell's first atom, one cache line for the whole wave.
-            //  Skipping the last group's fetch behind a wave-uniform test of T where it holds only padding - most cells of a liquid - was measured: ~1 us of
-            //  85 on the 1 M-atom box, inside the spread of the runs at 85 K: not kept, NOTES.md)
-            Cand cd[PRE];
+            //  Skipping only the last group's coordinate FETCH where it holds padding was measured earlier: ~1 us of 85, not kept; skipping its 256 B of
+            //  entries as well - kLazyLast, above - is worth 2 us of 91 on the 1 M-atom box, NOTES.md)
+            Cand cd[PRE] = {};
 #pragma unroll
-            for (int u = 0; u < PRE; u++) cd[u] = fetch(ent[u]);
+            for (int u = 0; u < PRE; u++) if (u < PRE - 1 || lastGroup) cd[u] = fetch(ent[u]);
             using ImgYes = std::integral_constant<bool, true>;
             using ImgNo = std::integral_constant<bool, false>;
             // (two copies of the straight-line code rather than a wave-uniform branch inside every put: interior cells - nearly all - shift nothing)
             if (images)
             {
 #pragma unroll
-                for (int u = 0; u < PRE; u++) put(ImgYes(), wave + u * W, ent[u], cd[u]);
+                for (int u = 0; u < PRE; u++) if (u < PRE - 1 || lastGroup) put(ImgYes(), wave + u * W, ent[u], cd[u]);
             }
             else
             {
 #pragma unroll
-                for (int u = 0; u < PRE; u++) put(ImgNo(), wave + u * W, ent[u], cd[u]);
+                for (int u = 0; u < PRE; u++) if (u < PRE - 1 || lastGroup) put(ImgNo(), wave + u * W, ent[u], cd[u]);
             }
             if (T > PRE * W * kWave)
             {   // dense systems: the rest of the tile, four groups per round trip
@@ -353,6 +367,8 @@ __global__ __launch_bounds__(MULTI ? kWave * kListMaxWaves : kWave) void k_pair_
         int tj = 0;
         auto fetch = [&](uint32_t en, double& x, double& y, double& z, int& ty, double& rd) {
             const uint32_t ko = en * ESCALE;                           // (table modes: one v_mad_u32_u24 with the records' base)
+            // (x and y leave as one ds_read2_b64, z as a ds_read_b64.  Three ds_read_b64 - the offset laundered through an empty asm between the uses, so that
+            //  the compiler cannot merge them - were measured on this layout: 98-102 us against 91-93 on the 1 M-atom box, NOTES.md)
             x = *(const double*)(tb + ko);
             y = *(const double*)(tb + ko + 8);
             z = *(const double*)(tb + ko + 16);
