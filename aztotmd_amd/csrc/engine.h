@@ -17,6 +17,7 @@
 #include "model.h"
 #include "msg_layout.h"
 #include "samplers.h"
+#include "step_plan.h"
 
 namespace aztot {
 
@@ -77,18 +78,14 @@ namespace aztot {
 //  snap_.valid       a verified snapshot of the dynamic state exists       take_snapshot (start of a settled call,     choose_optimism (not optimistic any more),  aztot_forces, aztot_set_state, aztot_set_clock,
 //                                                                          every clean look; kept when younger than    settle (no roll-back mode)                  mark_failed
 //                                                                          kSnapshotKeepSteps)
-// -- per-launch scratch ---
+// -- across a step boundary ---
 //  kickOwed_         the last step's second half-kick has not been         step_body (= lazyKick_ at the end of a      finish_steps (k_integrate2); start of the   -
 //                    applied and settle must apply it                      call), look at the end of a call (replay)   next step_body (the device flag
 //                                                                                                                      DevStats::pendingKick makes the next
 //                                                                                                                      integrate kernel pay it)
-//  preIntegrated_    the step being launched was opened by the previous    launch_pair (next-step fusion, KICK_DRIFT), sort_and_forces (consumes it), run_steps,   -
-//                    step's pair kernel / boundary kernel                  launch_step_kernels (k_boundary_radi)       graph capture, replay
-//  kickFolded_       the step being launched was kicked by the previous    launch_pair (the list launch that took up   sort_and_forces (consumes it: k_drift_plain2 -
-//                    step's k_pair_list (KICK_BOTH), which stored v and    foldKick_)                                  instead of k_integrate_plain2), graph        a folded step is always followed by a plain
-//                    no f: the state is NOT the canonical one                                                          capture, replay                             step of the same run_steps, so no entry point,
-//                                                                                                                                                                  look, snapshot or rebuild ever sees it set
-//  fuseNext_/fuseNow_/foldKick_/pairClosedStep_/overlapHalo_/candMode_/stepsLeftInRun_   set and consumed inside launch_step_kernels / launch_pair
+//  left_             how the previous step left the one being launched     launch_step_kernels (StepPlan::leaves: a    run_steps, graph capture, replay            - (a kicked step is always followed by a plain
+//                    (StepPlan::Left): untouched, opened, or kicked        pair launch that opened or kicked the       (-> untouched)                              step of the same run_steps: no entry point,
+//                    (v stored and no f: NOT the canonical state)          next step, k_boundary_radi)                                                             look, snapshot or rebuild ever sees it)
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 class Engine final : private Samplers::Host
 {
@@ -131,11 +128,14 @@ private:
     void upload_bonded();
     void upload_ewald();
     void launch_ewald();
-    void sort_and_forces(int stepMode, bool withBonded = true);   // StepMode (kernels.hip.h): bin + sort + forces (aztot_forces), a step that re-sorts, a plain step of the lazy re-sort
-    void launch_step_kernels();
+    StepPlan plan_step(int stepsLeft) const;        // stepsLeft: steps that follow the one being launched before the host looks / the cycle ends
+    StepPlan plan_forces(bool withBonded) const;    // aztot_forces: bin + sort + forces on the positions as they stand
+    void sort_and_forces(const StepPlan& plan);
+    void launch_step_kernels(int stepsLeft);
     void run_steps(int nsteps);
-    void launch_pair();
-    int pair_variant() const;
+    void launch_pair(const StepPlan& plan);
+    int pair_variant() const { return pairVariant_; }
+    bool walks_lists() const { return lists_.on && lazyOn_ && lazyK_ > 1 && pairVariant_ == 2; }      // plain steps of this engine walk pair lists
     void exchange_halo();
     void collect_and_finalize(unsigned slotMask);
     void finish_steps();
@@ -160,6 +160,7 @@ private:
     Model model_;
     aztot_options opt_;
     unsigned debug_ = 0;            // AZTOT_DEBUG (DebugBit)
+    int pairVariant_ = 1;           // which pair kernel runs (construct)
     StepParams P_{};
     SpecTable S_{};
     int rank_, nranks_;
@@ -287,29 +288,20 @@ private:
     bool can_graph() const;
     void set_buf_state(const BufState& b);
 
-    // -- per-launch scratch, and who applies the second half-kick (decided once, in the constructor) ---
+    // -- what crosses a step boundary, and who applies the second half-kick (decided once, in the constructor) ---
     bool lazyKick_ = false;         // large plain-NVE runs: integrate2 is folded into the next step's integrate1 (flushed by finish_steps)
     bool kickOwed_ = false;
     bool fuseEpilogue_ = false;     // small plain-NVE runs: the tile kernel's epilogue applies integrate2
-    bool fuseNow_ = false;          // the pair launch in flight also does integrate2's job (plain NVE steps, tile kernel)
     // large plain-NVE runs on one GPU that walk pair lists: on a step that books no energies and is followed by a plain step of the same run, k_pair_list
     // applies both half-kicks (this step's second, the next step's first) and stores the velocity instead of the force; the next step is a drift
     bool foldKickOk_ = false;       // this engine may fold (decided once)
-    bool foldKick_ = false;         // the list launch of the step being launched is asked to fold
-    bool kickFolded_ = false;       // ... and the previous step's did: the step being launched opens with k_drift_plain2
-    bool foldDriftOk_ = false;      // ... and a folding launch also drifts (KICK_DRIFT; decided once): the new positions go to altXyz_ and the next step is
-                                    // preIntegrated_, not kickFolded_
-    bool overlapHalo_ = false;      // the pair launch in flight is split: interior cells now, boundary cells once evHalo_ has fired
-    int candMode_ = 0;              // for the pair launch in flight: 0 none, 1 record, 2 plain step of the lazy re-sort
+    bool foldDriftOk_ = false;      // ... and a folding launch also drifts (KICK_DRIFT; decided once): the new positions go to altXyz_ and the next step is opened, not kicked
     // next-step fusion (pair_tile.hip.h NextStep): on plain NVE steps of a lazy run on one GPU the pair kernel's epilogue also does the next step's
     // k_integrate1_bin<2>; the new positions go to a second set of coordinate arrays, swapped in after the launch
     double* altXyz_[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     bool fuseNextOk_ = false;       // this engine may fuse (decided once)
-    bool fuseNext_ = false;         // the pair kernel of the step being launched fuses
     bool fuseNextTstat_ = false;    // ... in a run with the radiative thermostat: the fused epilogue also applies it (k_pair_list<..., TSTAT>; decided once)
-    bool pairClosedStep_ = false;   // the pair launch of the step in flight has closed the step (second half-kick + thermostat): no k_integrate2_post / k_boundary_radi
-    bool preIntegrated_ = false;    // the step being launched was opened by the previous step's pair kernel: no k_integrate1_bin
-    int stepsLeftInRun_ = 0;        // steps that follow the one being launched before the host looks / the cycle ends
+    StepPlan::Left left_ = StepPlan::LEFT_UNTOUCHED;    // how the previous step left the one being launched
 
     // -- snapshot: Slab ranks cannot repair a skin violation on the spot (they hold hw ghost layers: no wider stencil to fall back on), and the host learns
     // of one only at its next look.  So every look that finds none leaves a snapshot of the dynamic state (per-atom arrays, DevStats, Counts, partial sums -

@@ -277,6 +277,11 @@ void Engine::construct()
         S_.charged[i] = s.charged; S_.frozen[i] = s.frozen;
     }
     choose_cells();
+    // which pair kernel runs: 1 per-atom gather (any geometry), 2 one wave per cell with its own LDS tile (+ the pair lists of the lazy re-sort).
+    // 0 = the best one that supports the system.  (Round 2's variant 3 - four waves sharing a tile of 16-atom cell bins, measured 8 % slower than 2 - was
+    // retired in round 4: NOTES.md.)
+    pairVariant_ = opt_.pair_variant == 0 ? 2 : opt_.pair_variant;
+    if (pairVariant_ == 2 && !pair_tile_supported(P_)) pairVariant_ = 1;
     allocate();
     upload_bonded();
     upload_ewald();
@@ -292,7 +297,7 @@ void Engine::construct()
         // run, k_pair_list applies this step's second half-kick AND the next step's first and stores the velocity instead of the force (KICK_BOTH); the next
         // step is then a drift (k_drift_plain2: 76 B per atom instead of k_integrate_plain2's 124).  Above the sizes that fuse the next step (they keep what
         // they have); DBG_FOLD_KICK forces it on whatever the size - such an engine neither fuses the next step nor kicks in the tile kernel's epilogue -,
-        // DBG_NO_FOLD_KICK switches it off.  Which steps fold: launch_step_kernels.
+        // DBG_NO_FOLD_KICK switches it off.  Which steps fold: plan_step.
         foldKickOk_ = plainNve && nranks_ == 1 && lists_.on && variant == 2 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & (DBG_NO_FOLD_KICK | DBG_PLAIN_ONE_ATOM)) &&
                       (capacity_ > 2 * kFuseKickMaxAtoms || (debug_ & (DBG_FOLD_KICK | DBG_FOLD_DRIFT))) && !((debug_ & DBG_FUSE_NEXT) && !(debug_ & DBG_NO_FUSE_NEXT));
         // ... and the same lane drifts the atom too (KICK_DRIFT): the step behind a folded one then opens with no launch of its own.  Its positions go to the
@@ -1047,48 +1052,33 @@ void Engine::upload_initial()
 // ---------------------------------------------------------------------------------------------------
 // pair kernel dispatch
 // ---------------------------------------------------------------------------------------------------
-// which pair kernel runs: 1 per-atom gather (any geometry), 2 one wave per cell with its own LDS tile (+ the pair lists of the lazy re-sort).
-// 0 = the best one that supports the system.  (Round 2's variant 3 - four waves sharing a tile of 16-atom cell bins, measured 8 % slower than 2 - was
-// retired in round 4: NOTES.md.)
-int Engine::pair_variant() const
-{
-    int variant = opt_.pair_variant;
-    if (variant == 0) variant = pair_tile_supported(P_) ? 2 : 1;
-    if (variant == 2 && !pair_tile_supported(P_)) variant = 1;
-    return variant;
-}
-
 PairLaunch Engine::pair_launch(const StepParams& Q) { return PairLaunch{Q, S_, dPots_, cur(), dCounts_, dCellStart_, dPartials_, maxBlocks_, stream_}; }
 
-void Engine::launch_pair()
+void Engine::launch_pair(const StepPlan& plan)
 {
-    const int variant = pair_variant();
     int splitBlocks = 0;            // partial-sum slots a split or list launch has booked into (0: the plain tile grid)
-    if (variant == 2)
+    if (plan.pair != StepPlan::PAIR_ATOM)
     {
         StepParams Q = P_;
-        Q.fuseKick = fuseNow_ ? KICK_SECOND : KICK_NONE;
+        Q.fuseKick = plan.tileKick;
         const PairLaunch C = pair_launch(Q);
-        // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
-        // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
-        const bool wantEnergies = stepsLeftInRun_ == 0 || (debug_ & DBG_ENERGIES_EVERY_STEP);
         // (a step that records the lists records them in the entry format the store has decided on, and walks them in it)
-        if (candMode_ == 1 && lists_.on && !overlapHalo_) lists_.begin_recording();
+        if (plan.lists == StepPlan::LISTS_RECORD) lists_.begin_recording();
         const PairLists pl = lists_.pair_lists();
-        if (overlapHalo_)
+        if (plan.overlapHalo)
         {   // interior x-layers [2 hw, ncx - 2 hw) first; then, once the neighbours' coordinates have landed, the two runs of boundary layers
             const int plane = P_.nc[1] * P_.nc[2], hw = P_.hw[0];
             PairRange in, lo, hi;
             in.first = 2 * hw * plane; in.n = (P_.ncxLocal - 4 * hw) * plane;
             lo.first = hw * plane; lo.n = hw * plane;
             hi.first = (P_.ncxLocal - 2 * hw) * plane; hi.n = hw * plane;
-            const bool lists = candMode_ == 2 && pl.cand;
+            const bool lists = plan.pair == StepPlan::PAIR_LIST;
             int nb = 0;
             auto run = [&](PairRange& r) {
                 r.blockBase = nb;
                 if (lists)
                 {
-                    nb += launch_pair_list(C, r, pl, NextStep(), wantEnergies);
+                    nb += launch_pair_list(C, r, pl, NextStep(), plan.wantEnergies);
                     nb += launch_pair_cleanup(C, r, pl);
                 }
                 else
@@ -1104,14 +1094,13 @@ void Engine::launch_pair()
                 run(hi);
             });
             splitBlocks = nb;
-            overlapHalo_ = false;
         }
         else
         {
-            if (candMode_ != 0 && pl.cand)
+            if (plan.pair == StepPlan::PAIR_LIST)
             {   // lazy re-sort.  The step that rebuilds the cells first makes the lists (candidates of every tile, partners of every atom); then, like every
                 // plain step until the next rebuild, it walks them; the clean-up launch stages the cells that keep no list
-                if (candMode_ == 1)
+                if (plan.lists == StepPlan::LISTS_RECORD)
                 {   // (k_rank_gather has cleared the count of cells without a list)
                     timed("build_lists", [&] { launch_build_lists(C, PairRange(), pl); });
                     listsValid_ = true;
@@ -1122,22 +1111,17 @@ void Engine::launch_pair()
                         hUnlisted_.mark(stream_);
                     }
                 }
-                else if (nranks_ > 1 && unlistedState_ == 0 && !capturing_ && hUnlisted_.landed())
+                else if (plan.cleanup == StepPlan::CLEANUP_UNLESS_IDLE && unlistedState_ == 0 && hUnlisted_.landed())
                     unlistedState_ = (*hUnlisted_.as<int32_t>() == 0) ? 1 : 2;
-                const bool skipCleanup = (nranks_ > 1 && unlistedState_ == 1 && candMode_ == 2 && !capturing_) || optimistic_;
+                // (the one answer the plan leaves open: has this slab rank learnt by now that no cell is without a list?)
+                const bool skipCleanup = plan.cleanup == StepPlan::CLEANUP_NONE || (plan.cleanup == StepPlan::CLEANUP_UNLESS_IDLE && unlistedState_ == 1);
                 NextStep nx;
                 nx.st = dStats_; nx.cnt = dCounts_; nx.R0 = ref_;
-                if (fuseNext_) { nx.xn = altXyz_[cur_][0]; nx.yn = altXyz_[cur_][1]; nx.zn = altXyz_[cur_][2]; }
-                if (fuseNext_ && fuseNextTstat_) { nx.photons = dPhotons_; nx.uvx = dUvx_; nx.uvy = dUvy_; nx.uvz = dUvz_; pairClosedStep_ = true; }
-                else nx.pendingAfter = lazyKick_ ? 1 : -1;         // this step's second half-kick is owed to the next k_integrate1_bin (a call may open
-                                                                    // with a plain step, where no scan re-arms the flag)
-                // both half-kicks in this launch (launch_step_kernels decided; no clean-up launch follows, which has no such epilogue): neither kick is owed
-                const bool fold = foldKick_ && skipCleanup && !fuseNext_ && !wantEnergies;
-                foldKick_ = false;
-                StepParams QL = Q;
-                // ... and the next step's drift with them (KICK_DRIFT): that step is then opened like a fused one, not by k_drift_plain2
-                const bool foldDrift = fold && foldDriftOk_;
-                if (fold) { QL.fuseKick = foldDrift ? KICK_DRIFT : KICK_BOTH; nx.pendingAfter = 0; kickFolded_ = !foldDrift; }
+                nx.pendingAfter = plan.pendingAfter;
+                if (plan.fuseNext) { nx.xn = altXyz_[cur_][0]; nx.yn = altXyz_[cur_][1]; nx.zn = altXyz_[cur_][2]; }
+                if (plan.closesStep) { nx.photons = dPhotons_; nx.uvx = dUvx_; nx.uvy = dUvy_; nx.uvz = dUvz_; }
+                StepParams QL = Q; QL.fuseKick = plan.listKick;
+                const bool foldDrift = plan.listKick == KICK_DRIFT;
                 if (foldDrift)
                 {
                     nx.xd = altXyz_[cur_][0]; nx.yd = altXyz_[cur_][1]; nx.zd = altXyz_[cur_][2];
@@ -1146,14 +1130,13 @@ void Engine::launch_pair()
                 }
                 const PairLaunch CL = pair_launch(QL);
                 if (profile_ && !capturing_ && pl.entryBytes == 1) timers_.count("narrow_lists");      // (a count, no time of its own: the launch is timed as pair_list)
-                timed("pair_list", [&] { splitBlocks = launch_pair_list(CL, PairRange(), pl, nx, wantEnergies); });
+                timed("pair_list", [&] { splitBlocks = launch_pair_list(CL, PairRange(), pl, nx, plan.wantEnergies); });
                 if (!skipCleanup)
                     timed("pair_cleanup", [&] { splitBlocks += launch_pair_cleanup(C, PairRange(), pl, nx); });
-                if (fuseNext_ || foldDrift)
+                if (plan.fuseNext || foldDrift)
                 {   // the next step's positions are in the other set of coordinate arrays now
                     AtomArrays& A = cur();
                     std::swap(A.x, altXyz_[cur_][0]); std::swap(A.y, altXyz_[cur_][1]); std::swap(A.z, altXyz_[cur_][2]);
-                    preIntegrated_ = true;
                 }
             }
             else
@@ -1165,9 +1148,7 @@ void Engine::launch_pair()
             hipLaunchKernelGGL(k_pair_atom, dim3(div_up(capacity_, kBlock)), dim3(kBlock), 0, stream_, P_, S_, dPots_, cur(), dCounts_, dCellStart_,
                                dCellOfSorted_, dPartials_, maxBlocks_);
         });
-    if (variant < 2) fuseNow_ = false;           // only the tile kernels have the fused epilogue (cannot happen: see the constructor)
-    foldKick_ = false;                           // (a request no list launch took up is dropped)
-    notes_.pairBlocksUsed = (variant == 2) ? (splitBlocks ? splitBlocks : pair_tile_grid(P_) * split_.n) : div_up(capacity_, kBlock);
+    notes_.pairBlocksUsed = (plan.pair != StepPlan::PAIR_ATOM) ? (splitBlocks ? splitBlocks : pair_tile_grid(P_) * split_.n) : div_up(capacity_, kBlock);
     notes_.blocksEver = std::max(notes_.blocksEver, std::max(notes_.pairBlocksUsed, div_up(capacity_, kBlock)) + 1);
 }
 
@@ -1218,29 +1199,23 @@ void Engine::exchange_halo()
 // ---------------------------------------------------------------------------------------------------
 // iter_fastCellList (cuPairs.cu:2519-2567): histogram -> [halo] -> scan -> sort -> pair forces
 // ---------------------------------------------------------------------------------------------------
-void Engine::sort_and_forces(int stepMode, bool withBonded)
+void Engine::sort_and_forces(const StepPlan& plan)
 {
     const int gridAtoms = div_up(capacity_, kBlock);
-    const bool integrate_first = stepMode != STEP_BIN_ONLY;
-    P_.cycleStep = (stepMode == STEP_PLAIN) ? sinceSort_ + 1 : 0;           // which step since the last rebuild (the slack-violation flag is indexed by it)
-    if (stepMode == STEP_PLAIN)
+    P_.cycleStep = plan.cycleStep;          // (the slack-violation flag is indexed by it)
+    if (plan.stepMode == STEP_PLAIN)
     {   // plain step of the lazy re-sort: integrate only; slots, cells and buffers stay as they are
-        if (preIntegrated_) preIntegrated_ = false;                 // the previous step's pair kernel has opened this step already (NextStep)
-        else if (kickFolded_)
-        {   // the previous step's pair kernel applied both half-kicks and stored no force (KICK_BOTH): the drift alone
-            kickFolded_ = false;
+        if (plan.opener == StepPlan::OPEN_DRIFT)
             timed("drift", [&] {
                 hipLaunchKernelGGL(k_drift_plain2, dim3(div_up(div_up(capacity_, 2), kBlock)), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dPartials_,
                                    maxBlocks_, dStats_, ref_);
             });
-        }
-        else if (nranks_ == 1 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & DBG_PLAIN_ONE_ATOM))
-            // one GPU (the owned range starts at 0: 16-byte loads are aligned), nothing scales the velocities at the start of the step: two atoms per thread
+        else if (plan.opener == StepPlan::OPEN_PLAIN2)
             timed("integrate1", [&] {
                 hipLaunchKernelGGL(k_integrate_plain2, dim3(div_up(div_up(capacity_, 2), kBlock)), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dPartials_,
                                    maxBlocks_, dStats_, ref_);
             });
-        else
+        else if (plan.opener == StepPlan::OPEN_PLAIN)
         timed("integrate1", [&] {
             hipLaunchKernelGGL(k_integrate1_bin<STEP_PLAIN>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
@@ -1250,33 +1225,23 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
             take_halo_info();
             AtomArrays& A = cur();
             double* arr[4] = {A.x, A.y, A.z, A.rad};
-            // The exchange touches the ghost ranges only, and the cells two or more layers inside the slab never read them: it runs on its
-            // own stream next to the interior cells' pair forces; the boundary cells wait for it (launch_pair).  Not while kernels are being timed
-            // one by one, not with the per-atom kernel, and not when there is no interior to speak of.
-            const int interiorLayers = P_.ncxLocal - 4 * P_.hw[0];
-            // OPT-IN (DBG_OVERLAP_HALO): measured on one rank of 7 (loopback) the two cross-stream event waits and the two extra launches cost 30 us
-            // where the exchange they hide takes 7 (0.0685 -> 0.0981 ms/step), so the default is the serial order
-            overlapHalo_ = !profile_ && xch_->device_side() && pair_variant() == 2 && interiorLayers >= 1 && (debug_ & DBG_OVERLAP_HALO);
-            if (overlapHalo_)
+            if (plan.overlapHalo)
             {
                 HIP_CHECK(hipEventRecord(evIntegrated_, stream_));
                 HIP_CHECK(hipStreamWaitEvent(commStream_, evIntegrated_, 0));
             }
-            hipStream_t xs = overlapHalo_ ? commStream_ : stream_;
+            hipStream_t xs = plan.overlapHalo ? commStream_ : stream_;
             timed("exchange_coords", [&] {
                 xch_->exchange_ranges(left(), right(), arr, P_.use_radii ? 4 : 3, halo_[0], halo_[1] - halo_[0], halo_[2], halo_[3] - halo_[2], 0, halo_[0], halo_[3],
                                       halo_[4] - halo_[3], xs);
             });
-            if (overlapHalo_) HIP_CHECK(hipEventRecord(evHalo_, commStream_));
+            if (plan.overlapHalo) HIP_CHECK(hipEventRecord(evHalo_, commStream_));
         }
         sinceSort_++;
-        candMode_ = 2;
     }
     else
     {
-    if (kickFolded_) throw std::runtime_error("a step that needs the forces follows a pair kernel that stored none");      // (cannot happen: launch_step_kernels)
-    candMode_ = (stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? 1 : 0;       // a step that opens an interval of plain steps records the lists
-    if (integrate_first)
+    if (plan.opener == StepPlan::OPEN_RESORT)
         timed("integrate1_bin", [&] {
             hipLaunchKernelGGL(k_integrate1_bin<STEP_RESORT>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellOf_, dSlotOf_,
                                dCellCount_, dPartials_, maxBlocks_, lay_, dMsg_[0], dMsg_[1], dStats_, ref_);
@@ -1291,14 +1256,13 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     }
     if (nranks_ > 1) exchange_halo();
     const int nChunks = div_up(P_.nCellLocal, kScanChunk);
-    const int setPending = (integrate_first && lazyKick_) ? 1 : 0;
     timed("scan_cells", [&] {
         if (P_.nCellLocal <= kScanSingleMax)
-            hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, P_.nCellLocal, dCellCount_, dCellStart_, dCounts_, dStats_, setPending);
+            hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream_, P_.nCellLocal, dCellCount_, dCellStart_, dCounts_, dStats_, plan.setPending);
         else
         {
             hipLaunchKernelGGL(k_scan_totals, dim3(nChunks), dim3(kBlock), 0, stream_, P_.nCellLocal, dCellCount_, dChunkTot_);
-            hipLaunchKernelGGL(k_scan_apply, dim3(nChunks), dim3(kBlock), 0, stream_, P_.nCellLocal, dCellCount_, dChunkTot_, dCellStart_, dCounts_, dStats_, setPending);
+            hipLaunchKernelGGL(k_scan_apply, dim3(nChunks), dim3(kBlock), 0, stream_, P_.nCellLocal, dCellCount_, dChunkTot_, dCellStart_, dCounts_, dStats_, plan.setPending);
         }
     });
     timed("place", [&] {
@@ -1308,11 +1272,11 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
     timed("rank_gather", [&] {
         hipLaunchKernelGGL(k_rank_gather, dim3(gridAtoms), dim3(kBlock), 0, stream_, dCounts_, dCellStart_, dTmpId_, dTmpSrc_, dTmpCell_, cur(), oth(),
                            dCellOfSorted_, (P_.tstat == AZTOT_TSTAT_RADI || P_.use_radii || thermoTouched_) ? 2 : 0, P_, dCounts_, bonded_.idxOfId, ref_,
-                           dHaloInfo_, (lists_.on && stepMode == STEP_RESORT && lazyOn_ && lazyK_ > 1) ? &lists_.report[LR_UNLISTED_NOW] : nullptr, lists_.on ? lists_.rel : nullptr);
+                           dHaloInfo_, plan.lists == StepPlan::LISTS_RECORD ? &lists_.report[LR_UNLISTED_NOW] : nullptr, lists_.on ? lists_.rel : nullptr);
     });
     cur_ ^= 1;
     sinceSort_ = 0;
-    if (!capturing_ && stepMode == STEP_RESORT) rebuilds_++;
+    if (!capturing_ && plan.stepMode == STEP_RESORT) rebuilds_++;
     listsValid_ = false;            // (until this step's launch_pair records them)
     if (nranks_ > 1 && lazyOn_ && lazyK_ > 1)
     {   // where the boundary layers sit in the sorted arrays: [ownedBegin, end of layer 2hw-1) goes left, [start of layer ncx-2hw, ownedEnd) goes right;
@@ -1323,9 +1287,9 @@ void Engine::sort_and_forces(int stepMode, bool withBonded)
         haloInfoPending_ = true;      // (no stall here: take_halo_info waits when the numbers are needed)
     }
     }
-    launch_pair();
+    launch_pair(plan);
     if (hasEwald_) launch_ewald();
-    if (hasBonded_ && withBonded)      // exec_bondlist + exec_anglelist, main.cpp:101-104 (GPU path: main.cu:307-312,353-363)
+    if (hasBonded_ && plan.withBonded)      // exec_bondlist + exec_anglelist, main.cpp:101-104 (GPU path: main.cu:307-312,353-363)
         timed("bonded", [&] {
             if (nranks_ > 1)
                 hipLaunchKernelGGL(k_bonded<true>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, cur(), dCounts_, bonded_, dPartials_, maxBlocks_);
@@ -1350,7 +1314,7 @@ void Engine::forces(bool withBonded)
     settle();
     snap_.valid = false;
     sinceSort_ = kNoSort;           // a sort interval does not run on through a force call (it re-bins wrapped coordinates)
-    sort_and_forces(STEP_BIN_ONLY, withBonded);
+    sort_and_forces(plan_forces(withBonded));
     forget_interval();
     // energies of this configuration; kinetic energy and wall counters are left untouched
     unsigned mask = (1u << PS_EVDW) | (1u << PS_ECOUL) | (1u << PS_DROPPED);
@@ -1361,51 +1325,98 @@ void Engine::forces(bool withBonded)
     check_overflow();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// one iteration of the loop body of main.cu:281-410 (serial twin: main.cpp:89-142)
-// ---------------------------------------------------------------------------------------------------
-void Engine::launch_step_kernels()
+// what a step launches (step_plan.h): decided here, once, from host state alone; executed below
+StepPlan Engine::plan_forces(bool withBonded) const
 {
-    const int gridAtoms = div_up(capacity_, kBlock);
-    if (P_.tstat == AZTOT_TSTAT_NOSE) timed("nose_begin", [&] { hipLaunchKernelGGL(k_nose_begin, dim3(1), dim3(64), 0, stream_, P_, dStats_); });
+    StepPlan p;                     // STEP_BIN_ONLY: bin + sort, no lists, no kick, energies booked, nothing closes it
+    p.pair = (pair_variant() == 2) ? StepPlan::PAIR_TILE : StepPlan::PAIR_ATOM; p.withBonded = withBonded;
+    return p;
+}
+
+StepPlan Engine::plan_step(int stepsLeft) const
+{
+    StepPlan p;
     // does this step need the all-atom kinetic energy on the device?  Nose-Hoover: every step; equilibration rescaling: the steps it acts on
     // (integrators.cpp:511-522: step <= nequil and a multiple of eqfreq) - the host knows the number of the step it is launching.  (A captured cycle is
     // replayed at many step numbers: cycles are captured only once the equilibration period is over, can_graph.)
     const long long iStep = hostStep_ + 1;
-    const bool scalingDue = !capturing_ && P_.nEq > 0 && iStep <= P_.nEq && P_.freqEq > 0 && (iStep % P_.freqEq) == 0;
-    const bool equil = scalingDue || P_.tstat == AZTOT_TSTAT_NOSE;
-    // plain NVE steps leave integrate2 to somebody else (decided once, in the constructor): small systems / slabs -> the tile
-    // kernel's epilogue (fuseEpilogue_); large ones -> the next step's k_integrate1_bin (lazyKick_, see finish_steps)
-    fuseNow_ = fuseEpilogue_;
-    const int stepMode = (lazyOn_ && sinceSort_ < lazyK_ - 1) ? STEP_PLAIN : STEP_RESORT;
+    p.scalingDue = !capturing_ && P_.nEq > 0 && iStep <= P_.nEq && P_.freqEq > 0 && (iStep % P_.freqEq) == 0;
+    p.equil = p.scalingDue || P_.tstat == AZTOT_TSTAT_NOSE;
+    const bool plain = lazyOn_ && sinceSort_ < lazyK_ - 1;
+    p.stepMode = plain ? STEP_PLAIN : STEP_RESORT; p.cycleStep = plain ? sinceSort_ + 1 : 0;
     // is there a next step before the host looks or the cycle ends, and is it a plain one?
-    const int sinceAfter = (stepMode == STEP_PLAIN) ? sinceSort_ + 1 : 0;
-    const bool nextPlain = lazyOn_ && sinceAfter < lazyK_ - 1 && stepsLeftInRun_ > 0;
-    {   // does this step's pair kernel also open the next step?  Only if this step walks the lists (k_pair_list and its clean-up launch carry the epilogue)
-        const bool lists = lists_.on && lazyOn_ && lazyK_ > 1 && pair_variant() == 2;
-        fuseNext_ = fuseNextOk_ && lists && nextPlain;
-        // thermostat runs: only where no clean-up launch follows (it has no thermostat epilogue), on steps without equilibration scaling, never with energies on every step
-        // (and one wave per cell: in the multi-wave kernels of dense systems the thermostat's registers cost the loop more than the launch saves -
-        //  measured with a second radius array for case study 2's surk kernel: S40 0.076 -> 0.093 ms/step, case study 2 unchanged; not kept)
-        if (fuseNextTstat_) fuseNext_ = fuseNext_ && optimistic_ && !equil && lists_.waves == 1 && !(debug_ & DBG_ENERGIES_EVERY_STEP);
-        // ... or kick for it?  (foldKickOk_: plain NVE on one GPU, no next-step fusion.)  The same walk of the lists with no clean-up launch behind it, a step
-        // that books no energies, and a plain step of this run to follow: whoever else may come next - a rebuild (k_integrate1_bin and k_rank_gather need
-        // the force and the kick state they know), a look, the end of the call and everything that can read the state there - finds the canonical state,
-        // velocities half-kicked, forces valid, DevStats::pendingKick as ever.  (stepsLeftInRun_ > 0 inside nextPlain: this is not the step whose
-        // energies are wanted either, but for DBG_ENERGIES_EVERY_STEP.)
-        foldKick_ = foldKickOk_ && lists && nextPlain && optimistic_ && !(debug_ & DBG_ENERGIES_EVERY_STEP);
-    }
-    pairClosedStep_ = false;
-    sort_and_forces(stepMode);
-    const bool fused = fuseNow_;                 // launch_pair drops the request if the tile kernel is not the one running
-    fuseNow_ = false;
-    notes_.ekinFromPair = fused;
-    // radiative thermostat without equilibration scaling: nothing global happens between the second half-kick and the thermostat - one launch
-    // (DBG_KICK_POST_SPLIT: two, as everywhere else)
-    const bool closed = pairClosedStep_;           // (thermostat run, fused: the pair kernel has closed this step and opened the next)
-    const bool kickAndPost = !closed && !fused && !lazyKick_ && !equil && P_.tstat == AZTOT_TSTAT_RADI && !(debug_ & DBG_KICK_POST_SPLIT);
-    // ... and when a plain step follows, the same launch opens it (k_boundary_radi; DBG_NO_BOUNDARY_RADI: no)
-    if (kickAndPost && nextPlain && !(debug_ & DBG_NO_BOUNDARY_RADI))
+    const bool nextPlain = lazyOn_ && p.cycleStep < lazyK_ - 1 && stepsLeft > 0;
+    const bool everyStep = debug_ & DBG_ENERGIES_EVERY_STEP;
+    // -- opener.  A kicked step (KICK_BOTH: v stored, no f) takes the drift alone; one the previous pair / boundary kernel opened takes nothing
+    if (left_ == StepPlan::LEFT_KICKED) p.opener = StepPlan::OPEN_DRIFT;
+    else if (!plain) p.opener = StepPlan::OPEN_RESORT;
+    else if (left_ == StepPlan::LEFT_OPENED) p.opener = StepPlan::OPEN_NONE;
+    // one GPU (the owned range starts at 0: 16-byte loads are aligned), nothing scales the velocities at the start of the step: two atoms per thread
+    else p.opener = (nranks_ == 1 && P_.tstat != AZTOT_TSTAT_NOSE && !(debug_ & DBG_PLAIN_ONE_ATOM)) ? StepPlan::OPEN_PLAIN2 : StepPlan::OPEN_PLAIN;
+    p.setPending = lazyKick_ ? 1 : 0;
+    // -- exchange.  A plain slab step's coordinate exchange touches the ghost ranges only, and the cells two or more layers inside the slab never read them
+    // (SURVEY 8e): it may run on its own stream next to the interior cells' pair forces; the boundary cells wait for it (launch_pair).  Not while kernels
+    // are being timed one by one, not with the per-atom kernel, and not when there is no interior to speak of.
+    // OPT-IN (DBG_OVERLAP_HALO): measured on one rank of 7 (loopback) the two cross-stream event waits and the two extra launches cost 30 us
+    // where the exchange they hide takes 7 (0.0685 -> 0.0981 ms/step), so the default is the serial order
+    p.overlapHalo = plain && nranks_ > 1 && !profile_ && xch_->device_side() && pair_variant() == 2 && P_.ncxLocal - 4 * P_.hw[0] >= 1 && (debug_ & DBG_OVERLAP_HALO);
+    // -- lists and pair kernel.  A step that opens an interval of plain steps records the lists and walks them, like every plain step behind it.
+    // (walks_lists() holds lists_.on, and PairLists::cand is non-null exactly when the store is on - ListStore::allocate / release / pair_lists - and
+    // the tile variant: a step with lists is a k_pair_list step)
+    if (walks_lists()) p.lists = plain ? StepPlan::LISTS_WALK : StepPlan::LISTS_RECORD;
+    p.pair = pair_variant() != 2 ? StepPlan::PAIR_ATOM : (p.lists != StepPlan::LISTS_NONE ? StepPlan::PAIR_LIST : StepPlan::PAIR_TILE);
+    // pair energies are looked at through the statistics of a call's last step only (finish_steps): the list kernel of every other step books none
+    // (options.energies_every_step: every step does).  Inside a graph the last step of the cycle is the one that may be the call's last
+    p.wantEnergies = stepsLeft == 0 || everyStep;
+    // the clean-up launch stages the cells that keep no list: none on optimistic runs (one GPU only, choose_optimism); a slab rank drops it from the plain
+    // steps of an interval once it has learnt that the build left no such cell; the split launch of the overlapped exchange always carries it
+    if (optimistic_) p.cleanup = StepPlan::CLEANUP_NONE;
+    else if (nranks_ > 1 && plain && !capturing_ && !p.overlapHalo) p.cleanup = StepPlan::CLEANUP_UNLESS_IDLE;
+    // plain NVE steps leave integrate2 to somebody else (decided once, in the constructor): small systems / slabs -> the tile
+    // kernel's epilogue (fuseEpilogue_, which holds the tile variant); large ones -> the next step's k_integrate1_bin (lazyKick_, see finish_steps)
+    p.tileKick = p.listKick = fuseEpilogue_ ? KICK_SECOND : KICK_NONE; p.ekinFromPair = fuseEpilogue_;
+    // does this step's pair kernel also open the next step?  Only if it walks the lists (k_pair_list and its clean-up launch carry the epilogue; the split launch does not)
+    p.fuseNext = fuseNextOk_ && p.pair == StepPlan::PAIR_LIST && nextPlain && !p.overlapHalo;
+    // thermostat runs: only where no clean-up launch follows (it has no thermostat epilogue), on steps without equilibration scaling, never with energies on every step
+    // (and one wave per cell: in the multi-wave kernels of dense systems the thermostat's registers cost the loop more than the launch saves -
+    //  measured with a second radius array for case study 2's surk kernel: S40 0.076 -> 0.093 ms/step, case study 2 unchanged; not kept)
+    if (fuseNextTstat_) p.fuseNext = p.fuseNext && optimistic_ && !p.equil && lists_.waves == 1 && !everyStep;
+    p.closesStep = p.fuseNext && fuseNextTstat_;        // (second half-kick + thermostat in the fused epilogue: the pair launch has closed this step)
+    // this step's second half-kick is owed to the next k_integrate1_bin (a call may open with a plain step, where no scan re-arms the flag)
+    p.pendingAfter = (!p.closesStep && lazyKick_) ? 1 : -1;
+    // ... or kick for it?  (foldKickOk_: plain NVE on ONE GPU - so never a split launch - that walks lists and never fuses the next step.)  The same walk of
+    // the lists with no clean-up launch behind it (it has no such epilogue), a step that books no energies, and a plain step of this run to follow: whoever
+    // else may come next - a rebuild (k_integrate1_bin and k_rank_gather need the force and the kick state they know), a look, the end of the call and
+    // everything that can read the state there - finds the canonical state, velocities half-kicked, forces valid, DevStats::pendingKick as ever.
+    // Both half-kicks in this launch: neither is owed.  With foldDriftOk_ the next step's drift too (KICK_DRIFT): that step is opened like a fused one
+    const bool fold = foldKickOk_ && p.pair == StepPlan::PAIR_LIST && nextPlain && optimistic_ && !p.fuseNext && !p.wantEnergies;
+    if (fold) { p.listKick = foldDriftOk_ ? KICK_DRIFT : KICK_BOTH; p.pendingAfter = 0; }
+    // -- closer.  Radiative thermostat without equilibration scaling: nothing global happens between the second half-kick and the thermostat - one launch
+    // (DBG_KICK_POST_SPLIT: two, as everywhere else); when a plain step follows, the same launch opens it (k_boundary_radi; DBG_NO_BOUNDARY_RADI: no)
+    const bool kickHere = !p.closesStep && !fuseEpilogue_ && !lazyKick_;
+    const bool kickAndPost = kickHere && !p.equil && P_.tstat == AZTOT_TSTAT_RADI && !(debug_ & DBG_KICK_POST_SPLIT);
+    if (kickAndPost) p.closer = (nextPlain && !(debug_ & DBG_NO_BOUNDARY_RADI)) ? StepPlan::CLOSE_BOUNDARY_RADI : StepPlan::CLOSE_INTEGRATE2_POST;
+    else if (kickHere) p.closer = StepPlan::CLOSE_INTEGRATE2;
+    p.post = (p.equil || P_.tstat == AZTOT_TSTAT_RADI) && !kickAndPost && !p.closesStep;
+    if (p.fuseNext || p.listKick == KICK_DRIFT || p.closer == StepPlan::CLOSE_BOUNDARY_RADI) p.leaves = StepPlan::LEFT_OPENED;     // -- hand-over
+    else if (fold) p.leaves = StepPlan::LEFT_KICKED;
+    if (p.opener == StepPlan::OPEN_DRIFT && !plain) throw std::runtime_error("a step that needs the forces follows a pair kernel that stored none");     // -- what no plan may hold
+    if ((fold && (p.cleanup != StepPlan::CLEANUP_NONE || p.wantEnergies || !nextPlain)) || (p.closesStep && !p.fuseNext))
+        throw std::runtime_error("step plan: a fold with a clean-up launch, with energies or without a plain step behind it, or a thermostat close without next-step fusion");
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// one iteration of the loop body of main.cu:281-410 (serial twin: main.cpp:89-142)
+// ---------------------------------------------------------------------------------------------------
+void Engine::launch_step_kernels(int stepsLeft)
+{
+    const StepPlan plan = plan_step(stepsLeft);
+    const int gridAtoms = div_up(capacity_, kBlock);
+    if (P_.tstat == AZTOT_TSTAT_NOSE) timed("nose_begin", [&] { hipLaunchKernelGGL(k_nose_begin, dim3(1), dim3(64), 0, stream_, P_, dStats_); });
+    sort_and_forces(plan);
+    notes_.ekinFromPair = plan.ekinFromPair;
+    if (plan.closer == StepPlan::CLOSE_BOUNDARY_RADI)
     {
         StepParams Q = P_;
         Q.cycleStep = sinceSort_ + 1;              // of the step being opened
@@ -1413,19 +1424,18 @@ void Engine::launch_step_kernels()
             hipLaunchKernelGGL(k_boundary_radi, dim3(gridAtoms), dim3(kBlock), 0, stream_, Q, S_, cur(), dCounts_, dPartials_, maxBlocks_, dStats_, dPhotons_, dUvx_, dUvy_,
                                dUvz_, ref_);
         });
-        preIntegrated_ = true;
     }
-    else if (kickAndPost)
+    else if (plan.closer == StepPlan::CLOSE_INTEGRATE2_POST)
         timed("integrate2_post", [&] {
             hipLaunchKernelGGL(k_integrate2_post, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellCount_, P_.nCellLocal, dPartials_,
                                maxBlocks_, dStats_, dPhotons_, dUvx_, dUvy_, dUvz_);
         });
-    else if (!closed && !fused && !lazyKick_)
+    else if (plan.closer == StepPlan::CLOSE_INTEGRATE2)
         timed("integrate2", [&] {
             hipLaunchKernelGGL(k_integrate2, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dCellCount_, P_.nCellLocal, dPartials_,
                                maxBlocks_, dStats_);
         });
-    if (equil)
+    if (plan.equil)
     {
         timed("reduce_kin", [&] {
             hipLaunchKernelGGL(k_reduce_kin, dim3(1), dim3(1024), 0, stream_, P_, dPartials_, maxBlocks_, gridAtoms, dStats_, dEkGlobal_);
@@ -1440,17 +1450,18 @@ void Engine::launch_step_kernels()
         }
         timed("scale_decision", [&] { hipLaunchKernelGGL(k_scale_decision, dim3(1), dim3(64), 0, stream_, P_, dStats_, dEkGlobal_); });
     }
-    if ((equil || P_.tstat == AZTOT_TSTAT_RADI) && !kickAndPost && !closed)
+    if (plan.post)
         timed("post_tstat", [&] {
             hipLaunchKernelGGL(k_post, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, dStats_, dPhotons_, dUvx_, dUvy_, dUvz_,
                                dPartials_, maxBlocks_);
         });
-    if (scalingDue && P_.tstat != AZTOT_TSTAT_NOSE)
+    if (plan.scalingDue && P_.tstat != AZTOT_TSTAT_NOSE)
     {   // the factor has been applied: the steps that follow take the short path, which never decides one (DevStats::vscale is read by every thermostat kernel)
         static const double one = 1.0;
         HIP_CHECK(hipMemcpyAsync(&dStats_->vscale, &one, sizeof(double), hipMemcpyHostToDevice, stream_));
     }
-    notes_.lastStepEquil = equil;
+    notes_.lastStepEquil = plan.equil;
+    left_ = plan.leaves;
     if (!capturing_) hostStep_++;
 }
 
@@ -1479,7 +1490,7 @@ void Engine::choose_optimism()
 {
     // (any size since round 4: on 1 M atoms the launch cost 6.9 us of a 123 us step - the drain and refill of the chip around a kernel that finds nothing
     //  to do -, a snapshot is 100 MB = 33 us per look, and looks are up to 256 steps apart)
-    const bool want = nranks_ == 1 && lazyOn_ && lists_.on && lazyMeasured_ && lazyK_ > 1 && pair_variant() == 2 &&
+    const bool want = nranks_ == 1 && walks_lists() && lazyMeasured_ &&
                       safeLooks_ == 0 && !unlistedAtLook_ && unlistedState_ != 2 && !(debug_ & DBG_ALWAYS_CLEANUP);
     if (want != optimistic_)
     {
@@ -1526,7 +1537,7 @@ void Engine::replay_from_snapshot()
     drop_graphs();
     set_buf_state(snap_.buf);
     copy_state(snap_, live());
-    forget_interval(); preIntegrated_ = false; kickFolded_ = false; haloInfoPending_ = false; unlistedState_ = 0;
+    forget_interval(); left_ = StepPlan::LEFT_UNTOUCHED; haloInfoPending_ = false; unlistedState_ = 0;
     kickOwed_ = false;
     hostStep_ = snap_.hostStep;
     if (nranks_ > 1) lazyK_ = 1;
@@ -1711,9 +1722,8 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     try
     {
         sinceSort_ = kNoSort;
-        preIntegrated_ = false;
-        kickFolded_ = false;
-        for (int k = 0; k < cycle; k++) { stepsLeftInRun_ = cycle - 1 - k; launch_step_kernels(); }
+        left_ = StepPlan::LEFT_UNTOUCHED;
+        for (int k = 0; k < cycle; k++) launch_step_kernels(cycle - 1 - k);
     }
     catch (...)
     {   // leave neither the stream in capture mode nor the engine believing it is capturing
@@ -1721,8 +1731,7 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
         (void)hipStreamEndCapture(stream_, &broken);
         if (broken) (void)hipGraphDestroy(broken);
         capturing_ = false;
-        preIntegrated_ = false;
-        kickFolded_ = false;
+        left_ = StepPlan::LEFT_UNTOUCHED;
         sinceSort_ = sinceBefore;
         lists_.entryBytes = entryBytesBefore;
         set_buf_state(now);
@@ -1739,7 +1748,6 @@ Engine::GraphSlot* Engine::graph_for_state(int cycle)
     set_buf_state(now);               // the capture itself executed nothing
     adopt_launch_notes(notesBefore);
     sinceSort_ = sinceBefore;
-    stepsLeftInRun_ = 0;
     graphs_.push_back(g);
     return &graphs_.back();
 }
@@ -1756,10 +1764,10 @@ void Engine::run_steps(int nsteps)
     // With pair lists a sort interval runs on from the previous call when nothing has touched the state since (the lists are those of the arrays as they
     // stand; slab ranks: when all ranks agreed at the end of the previous call that they can - a rebuild step carries the full exchange, so they must
     // take it together); the plain steps that finish it are launched one by one, whole cycles are replayed as graphs after that.
-    const bool carryOn = lazyOn_ && (nranks_ == 1 || carryAgreed_) && lists_.on && listsValid_ && lazyK_ > 1 && sinceSort_ < kNoSort / 2 && pair_variant() == 2;
+    const bool carryOn = walks_lists() && (nranks_ == 1 || carryAgreed_) && listsValid_ && sinceSort_ < kNoSort / 2;
     if (!carryOn) sinceSort_ = kNoSort;
-    preIntegrated_ = false;
-    while (carryOn && done < nsteps && sinceSort_ < lazyK_ - 1) { stepsLeftInRun_ = nsteps - 1 - done; launch_step_kernels(); done++; }
+    left_ = StepPlan::LEFT_UNTOUCHED;
+    while (carryOn && done < nsteps && sinceSort_ < lazyK_ - 1) { launch_step_kernels(nsteps - 1 - done); done++; }
     const int cycle = graph_cycle();
     if (can_graph() && nsteps - done >= cycle)
     {
@@ -1777,9 +1785,8 @@ void Engine::run_steps(int nsteps)
             sinceSort_ = kNoSort;                 // the next cycle (or the eager remainder) starts with a sort
         }
     }
-    preIntegrated_ = false;
-    for (; done < nsteps; done++) { stepsLeftInRun_ = nsteps - 1 - done; launch_step_kernels(); }
-    stepsLeftInRun_ = 0;
+    left_ = StepPlan::LEFT_UNTOUCHED;
+    for (; done < nsteps; done++) launch_step_kernels(nsteps - 1 - done);
 }
 
 // At the end of a call: what the next call will need and this one can provide without executing a step.  (1) The graph of a whole cycle for the buffer
@@ -1789,7 +1796,7 @@ void Engine::run_steps(int nsteps)
 void Engine::prepare_next_call()
 {
     if (!lazyOn_ || !lazyMeasured_) return;
-    if (lists_.on && lazyK_ > 1 && !listsValid_ && sinceSort_ == 0 && pair_variant() == 2)
+    if (walks_lists() && !listsValid_ && sinceSort_ == 0)
     {
         P_.cycleStep = 0;
         int32_t rep[LR_COUNT];
@@ -1822,7 +1829,7 @@ void Engine::prepare_next_call()
     }
     if (nranks_ > 1)
     {   // can every rank open the next call with plain steps?
-        double cannot = (lists_.on && listsValid_ && lazyK_ > 1 && pair_variant() == 2) ? 0.0 : 1.0;
+        double cannot = (walks_lists() && listsValid_) ? 0.0 : 1.0;
         xch_->allreduce_sum(&cannot, 1, stream_);
         carryAgreed_ = cannot == 0.0;
     }
