@@ -35,7 +35,7 @@ class _Control(C.Structure):
                 ("temperature", C.c_double), ("tstat_type", C.c_int32), ("tstat_tau", C.c_double), ("elec_type", C.c_int32),
                 ("r_real", C.c_double), ("alpha", C.c_double), ("init_vel", C.c_int32), ("init_vel_par", C.c_double * 3),
                 ("elecfield", C.c_double * 3), ("use_cell_list", C.c_int32), ("cell_list", C.c_double), ("stat", C.c_int32),
-                ("ewald_k", C.c_int32 * 3)]
+                ("ewald_k", C.c_int32 * 3), ("spme_mesh", C.c_int32 * 3), ("spme_order", C.c_int32)]
 
 
 _dp = C.POINTER(C.c_double)
@@ -121,7 +121,10 @@ EXPORTS = ("aztot_device_count", "aztot_device_synchronize", "aztot_init_md", "a
            "aztot_adf_neighbours",
            "aztot_sk_setup", "aztot_sk_sample", "aztot_sk_reset", "aztot_sk_shape", "aztot_sk_vectors", "aztot_sk_amplitudes", "aztot_sk_sums", "aztot_sk_values",
            "aztot_boo_setup", "aztot_boo_sample", "aztot_boo_reset", "aztot_boo_shape", "aztot_boo_per_atom", "aztot_boo_qlm", "aztot_boo_counts", "aztot_boo_values",
+           "aztot_spme_mesh", "aztot_spme_influence",
            "aztot_last_error", "aztot_version")
+
+SPME_MESHES = {"charge": 0, "spectrum": 1, "potential": 2}      # AZTOT_SPME_CHARGE / _SPECTRUM / _POTENTIAL
 
 RDF_KINDS = {"species": 0, "nuclei": 1}       # AZTOT_RDF_SPECIES / AZTOT_RDF_NUCLEI
 CN_KINDS = {"species": 0, "nuclei": 1}        # AZTOT_CN_SPECIES (outCN rules) / AZTOT_CN_NUCLEI (ncn rules)
@@ -276,6 +279,10 @@ def lib():
         L.aztot_boo_qlm.argtypes = [C.c_void_p, _dp, C.c_int]
         L.aztot_boo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint64), C.c_int]
         L.aztot_boo_values.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
+        L.aztot_spme_mesh.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        L.aztot_spme_mesh.restype = C.c_int64
+        L.aztot_spme_influence.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.aztot_spme_influence.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -336,6 +343,8 @@ class Model:
         c.tstat_tau = float(case.get("tau", 0.0))
         c.elec_type, c.r_real, c.alpha = int(case.get("elec_type", 0)), float(case.get("rReal", 0.0)), float(case.get("alpha", 0.0))
         c.ewald_k = (C.c_int32 * 3)(*[int(v) for v in case.get("ewald_k", (0, 0, 0))])
+        c.spme_mesh = (C.c_int32 * 3)(*[int(v) for v in case.get("spme_mesh", (0, 0, 0))])
+        c.spme_order = int(case.get("spme_order", 0))
         c.init_vel = 0
         c.elecfield = (C.c_double * 3)(case.get("Ux", 0.0), case.get("Uy", 0.0), case.get("Uz", 0.0))
         c.use_cell_list = int(case.get("use_clist", 1))
@@ -561,6 +570,25 @@ class Engine:
         n = _check(lib().aztot_kernel_times(self.h, names, 4096, ms, calls, 64))
         parts = names.raw.split(b"\0")
         return {parts[i].decode(): {"ms": ms[i], "calls": calls[i]} for i in range(n)}
+
+    def spme_mesh(self, which="charge"):
+        """A mesh of the last force evaluation of an 'elec spme' model (aztot_spme_mesh), indexed [gx, gy, gz]: "charge" the integer charge
+        mesh (int64, units of 2^-40 e), "spectrum" its forward DFT, "potential" phi after the inverse transform (both complex128)."""
+        kx, ky, kz = (int(v) for v in self.model.query("spme")[:3])
+        n = _check(lib().aztot_spme_mesh(self.h, SPME_MESHES[which], None, 0))
+        out = np.zeros(n, dtype=np.int64 if which == "charge" else np.float64)
+        _check(lib().aztot_spme_mesh(self.h, SPME_MESHES[which], out.ctypes.data_as(C.c_void_p), n))
+        if which != "charge":
+            out = out.view(np.complex128)
+        return out.reshape(kz, ky, kx).transpose(2, 1, 0)
+
+    def spme_influence(self):
+        """The influence function G of an 'elec spme' model (aztot_spme_influence), indexed [mx, my, mz]."""
+        kx, ky, kz = (int(v) for v in self.model.query("spme")[:3])
+        n = _check(lib().aztot_spme_influence(self.h, None, 0))
+        out = np.zeros(n)
+        _check(lib().aztot_spme_influence(self.h, out.ctypes.data_as(_dp), n))
+        return out.reshape(kz, ky, kx).transpose(2, 1, 0)
 
     def reset_kernel_times(self):
         _check(lib().aztot_reset_kernel_times(self.h))

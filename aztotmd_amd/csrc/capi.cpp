@@ -115,6 +115,7 @@ int aztot_model_nucleus_name(const aztot_model* m, int i, char* buf, int cap)
 //  species (per species: mass_amu, mass, charge, charged, frozen, rMass_hdt, radA, radB, mxEng, number)
 //  vdw (per ordered species pair a*nSpec+b: type, r2cut, p0..p4, use_radii)
 //  ewald (kx, ky, kz, mr4a2, rkcut2, engElec1, number of k-vectors)  kvecs (l, m, n, rkx, rky, rkz, akk per k-vector)
+//  spme (Kx, Ky, Kz, order, scale: the 'elec spme' line of control.txt, our extension, and the el_scale its energy and potential carry; zeros without one)
 //  n_bonded (bond types, angle types, bonds, angles)  bond_types (type, spec1, spec2, p0..p4)  angle_types (type, central, k, cos0)
 //  bonds (at1, at2, type id per bond, after the turn of read_bondlist)  angles (central, lig1, lig2, type id)
 //  rdf (present, rmax, dr, every, out_every, nucl: the 'rdf' line of control.txt; present = 0 without one)
@@ -174,6 +175,7 @@ int aztot_model_query(const aztot_model* h, const char* key, double* out, int ca
             for (const auto& p : m.pairpots)
             { double r[] = {(double)p.type, p.r2cut, p.p0, p.p1, p.p2, p.p3, p.p4, (double)p.use_radii}; v.insert(v.end(), r, r + 8); }
         else if (k == "ewald") { v = {(double)m.ewald_k[0], (double)m.ewald_k[1], (double)m.ewald_k[2], m.mr4a2, m.rkcut2, m.engElec1, (double)m.kvecs.size()}; }
+        else if (k == "spme") v = {(double)m.spme_mesh[0], (double)m.spme_mesh[1], (double)m.spme_mesh[2], (double)m.spme_order, m.elec_type == AZTOT_ELEC_SPME ? m.el_scale : 0.0};
         else if (k == "kvecs")
             for (const auto& q : m.kvecs) { double r[] = {(double)q.l, (double)q.m, (double)q.n, q.rkx, q.rky, q.rkz, q.akk}; v.insert(v.end(), r, r + 7); }
         else if (k == "n_bonded") v = {(double)m.bondTypes.size(), (double)m.angleTypes.size(), (double)m.bondA.size(), (double)m.angC.size()};
@@ -392,6 +394,22 @@ int aztot_kernel_times(aztot_md* md, char* names, int cap, double* ms, int64_t* 
         if (names && pos < cap) names[pos] = 0;
     });
     return status == AZTOT_OK ? n : status;
+}
+
+int64_t aztot_spme_mesh(aztot_md* md, int which, void* out, int64_t cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    long long n = 0;
+    const int rc = guarded([&] { n = md->eng->spme_mesh(which, out, cap); });
+    return rc < 0 ? rc : n;
+}
+
+int64_t aztot_spme_influence(aztot_md* md, double* out, int64_t cap)
+{
+    if (!md || !md->eng) return fail(AZTOT_ERR_ARG, "null handle");
+    long long n = 0;
+    const int rc = guarded([&] { n = md->eng->spme_influence(out, cap); });
+    return rc < 0 ? rc : n;
 }
 
 int aztot_reset_kernel_times(aztot_md* md)

@@ -83,6 +83,27 @@ struct EwaldTables
     double scale, scale2;            // elec.cpp:380-381
 };
 
+// smooth particle-mesh Ewald ('elec spme', spme.hip.h).  Every mesh is stored x fastest: point (gx, gy, gz) at (gz * K[1] + gy) * K[0] + gx
+struct SpmeTables
+{
+    long long* Qi;                   // integer charge mesh: sum of llrint(q theta_x theta_y theta_z 2^40); zero between two force evaluations
+    double* W;                       // complex work mesh (re, im per point): Q, then its spectrum, then G FQ, then phi
+    const double* G;                 // influence function (host, long double -> double)
+    const double* tw[3];             // per axis: exp(-2 pi i k / K), k = 0 .. K - 1, as (cos, -sin)
+    double* partial;                 // [nPts / 256]: energy partials of k_spme_convolve, folded in place by k_spme_energy
+    int32_t K[3], order, nPts;
+    double scale;                    // el_scale of finish_model: 4 pi Fcoul_scale / (V eps)
+    double KoverL[3];
+};
+// one pass of the 3-D transform: batched 1-D transforms of length N along one axis, `LT` lines per workgroup.  The lines of a tile are LT consecutive
+// rows (x axis: contiguous) or the lines through LT adjacent x (y, z axes): element e of line l is at base + l * (contiguous ? N : 1) + e * elemStride,
+// base = (block / tilesPerRow) * outerStride + (block % tilesPerRow) * LT
+struct SpmeAxis
+{
+    int32_t N, logN, LT, contiguous, tilesPerRow, nTiles;
+    int64_t outerStride, elemStride;
+};
+
 // Few cells, wide stencils (case study 2: 4 000 atoms on 2.7 A cells, 7^3 = 343 stencil cells, five tiles' worth of candidates per cell): one wave per
 // cell leaves most of the chip idle and makes every wave long.  The stencil's (x, y) columns are then dealt to `n` waves per cell (a power of two); every
 // wave writes its partial forces to scratch, and the last one to arrive (one atomic per wave) adds them up IN FIXED ORDER and finishes the atoms - no

@@ -109,7 +109,9 @@ public:
     int n_atoms_global() const { return model_.nAt; }
     int comm_ranks() const { return xch_ ? xch_->comm_ranks() : 0; }
     void sync_all();                        // everything queued or deferred by earlier calls has happened when this returns (aztot_sync)
-    Samplers& samplers() { return *samplers_; }     // RDF, coordination numbers, time correlation functions: they see the engine as a Samplers::Host
+    // debug read-back of the SPME meshes of the last force evaluation (aztot_spme_mesh / aztot_spme_influence); cap and result count 8-byte words
+    long long spme_mesh(int which, void* out, long long cap);
+    long long spme_influence(double* out, long long cap);    Samplers& samplers() { return *samplers_; }     // RDF, coordination numbers, time correlation functions: they see the engine as a Samplers::Host
 
 private:
     void step_body(int nsteps);
@@ -128,6 +130,9 @@ private:
     void upload_bonded();
     void upload_ewald();
     void launch_ewald();
+    void upload_spme();
+    void launch_spme();
+    void spme_stage(int upTo);      // spread [+ to_complex + forward transform [+ convolution + inverse transform]] on the arrays as they stand
     StepPlan plan_step(int stepsLeft) const;        // stepsLeft: steps that follow the one being launched before the host looks / the cycle ends
     StepPlan plan_forces(bool withBonded) const;    // aztot_forces: bin + sort + forces on the positions as they stand
     void sort_and_forces(const StepPlan& plan);
@@ -194,6 +199,10 @@ private:
     bool hasBonded_ = false;
     EwaldTables ew_{};              // reciprocal-space Ewald sum ('elec pme')
     bool hasEwald_ = false;
+    SpmeTables spme_{};             // smooth particle-mesh Ewald ('elec spme'): meshes, influence function, twiddles
+    SpmeAxis spmeAxis_[3]{};
+    bool hasSpme_ = false;
+    bool has_recip() const { return hasEwald_ || hasSpme_; }    // a reciprocal-space sum adds forces behind the pair kernel
     bool thermoTouched_ = false;    // the caller set U / radius on a run whose model does not use them: keep them attached to their atoms
 
     // -- pair lists of the lazy re-sort ---

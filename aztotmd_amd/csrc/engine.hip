@@ -14,6 +14,7 @@
 #include "exchange.h"
 #include "bonded.hip.h"
 #include "ewald.hip.h"
+#include "spme.hip.h"
 #include "kernels.hip.h"
 #include "pair_tile.hip.h"
 #include "pair_list.hip.h"
@@ -189,12 +190,23 @@ void Engine::construct()
     if (nranks_ > 1 && !xch_ && !opt_.loopback_ranks) throw std::runtime_error("slab decomposition needs an exchanger");
 
     const Model& m = model_;
+    if (m.elec_type == AZTOT_ELEC_SPME)
+    {   // what the mesh sum cannot do is refused before anything is allocated ("out of scope" -> AZTOT_ERR_INPUT)
+        if (nranks_ > 1) throw std::runtime_error("out of scope: 'elec spme' runs on one GPU only: the mesh is not decomposed over slab ranks (use elec pme or elec fenn)");
+        double qmax = 0.0;
+        for (int i = 0; i < m.nAt; i++) qmax = std::max(qmax, std::fabs(m.species[m.types[i]].charge));
+        if (!((double)m.nAt * qmax < kSpmeChargeCap))
+            throw std::runtime_error("out of scope: 'elec spme': n_atoms * max|q| = " + std::to_string((double)m.nAt * qmax) +
+                                     " reaches 2^22 = 4194304: the mesh's 64-bit sums of 2^-40 e could overflow");
+    }
+    // (an SPME model shows the pair kernels the real-space term of the Ewald sum: no pair kernel knows of the mesh)
+    const int elecPair = m.elec_type == AZTOT_ELEC_SPME ? (int)AZTOT_ELEC_EWALD : m.elec_type;
     P_.nSpec = m.nSpec();
     P_.nAtGlobal = m.nAt;
     for (int k = 0; k < 3; k++) { P_.L[k] = m.L[k]; P_.invL[k] = 1.0 / m.L[k]; P_.half[k] = m.L[k] * 0.5; P_.E[k] = m.E[k]; }
     P_.dt = m.tSt;
     P_.r2Max = m.r2Max;
-    P_.elec_type = m.elec_type; P_.alpha = m.alpha; P_.el_scale = m.el_scale; P_.el_scale2 = m.el_scale2; P_.daipi2 = m.daipi2;
+    P_.elec_type = elecPair; P_.alpha = m.alpha; P_.el_scale = m.el_scale; P_.el_scale2 = m.el_scale2; P_.daipi2 = m.daipi2;
     P_.rReal = m.rReal; P_.fcoul = units::Fcoul_scale; P_.sqrtpi = std::sqrt(units::pi);
     P_.tstat = m.tstat_type; P_.nEq = m.nEq; P_.freqEq = m.freqEq; P_.tKin = m.tKin; P_.revDegFree = m.revDegFree; P_.rkB = 1.0 / units::kB;
     if (m.tstat_type == AZTOT_TSTAT_NOSE) { P_.rQmass = 0.5 / m.tKin / m.tau / m.tau; P_.qMassTau2 = 2 * m.tKin; }
@@ -228,7 +240,7 @@ void Engine::construct()
             if (family == 0) family = p.type; else if (family != p.type) family = VDW_MIXED;   // mixed families, type looked up per species pair
         }
         if (family == 0) family = AZTOT_VDW_LJ;          // charges only: any family does, nothing is inside a VdW cut-off
-        if ((m.elec_type == AZTOT_ELEC_FENNEL || m.elec_type == AZTOT_ELEC_EWALD) && m.alpha * m.rReal > 4.0) uniform = false;
+        if ((elecPair == AZTOT_ELEC_FENNEL || elecPair == AZTOT_ELEC_EWALD) && m.alpha * m.rReal > 4.0) uniform = false;
         if (debug_ & DBG_GENERIC_PAIR) uniform = false;
         P_.potSet = uniform ? POTSET_ONE_FAMILY : POTSET_GENERIC;
         P_.vdwFamily = uniform ? family : 0;
@@ -285,9 +297,10 @@ void Engine::construct()
     allocate();
     upload_bonded();
     upload_ewald();
+    upload_spme();
     {
         // who applies the second half-kick on plain NVE steps (nothing is added to the pair forces, nothing rescales velocities)
-        const bool plainNve = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP);
+        const bool plainNve = !(P_.nEq > 0) && P_.tstat == AZTOT_TSTAT_NONE && !hasBonded_ && !has_recip() && !(debug_ & DBG_KICK_EVERY_STEP);
         const int variant = pair_variant();
         // small systems / slabs are bound by launch latency: the tile kernel's epilogue does it (one kernel less: C2 0.083 -> 0.063 ms).
         // Large systems are not: they fold the kick into the next step's streaming k_integrate1_bin.  (Round 2 measured 221 MB per step for that
@@ -320,7 +333,7 @@ void Engine::construct()
         // the step with the thermostat and opens the next): the thermostat acts on one atom at a time, so the lane that closes the atom's step applies it too
         // (k_pair_list<..., TSTAT>) and a step is ONE launch.  Not where the pair kernel reads radii (the thermostat rewrites them while other waves still
         // gather: case study 2's surk potential), not with bonded terms or the Ewald sum (their forces arrive after the pair kernel).
-        const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !hasEwald_ && !(debug_ & DBG_KICK_EVERY_STEP) && !P_.use_radii && P_.potSet != POTSET_ONE_SURK && (P_.single_lj || P_.potSet == POTSET_ONE_FAMILY) &&
+        const bool radiFuse = P_.tstat == AZTOT_TSTAT_RADI && !hasBonded_ && !has_recip() && !(debug_ & DBG_KICK_EVERY_STEP) && !P_.use_radii && P_.potSet != POTSET_ONE_SURK && (P_.single_lj || P_.potSet == POTSET_ONE_FAMILY) &&
                               nranks_ == 1 && capacity_ <= 2 * kFuseKickMaxAtoms;
         fuseNextTstat_ = radiFuse && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT);
         if (((plainNve && !foldKickOk_ && (capacity_ <= 2 * kFuseKickMaxAtoms || (debug_ & DBG_FUSE_NEXT))) || radiFuse) && lists_.on && variant == 2 && !(debug_ & DBG_NO_FUSE_NEXT))
@@ -996,6 +1009,133 @@ void Engine::launch_ewald()
     check_launch("Ewald kernels");
 }
 
+// Meshes, influence function and twiddles of 'elec spme' (spme.hip.h): everything the per-step path touches is allocated here, once
+void Engine::upload_spme()
+{
+    const Model& m = model_;
+    hasSpme_ = m.elec_type == AZTOT_ELEC_SPME;
+    if (!hasSpme_) return;
+    SpmeTables& T = spme_;
+    for (int k = 0; k < 3; k++) { T.K[k] = m.spme_mesh[k]; T.KoverL[k] = (double)m.spme_mesh[k] / m.L[k]; }
+    T.order = m.spme_order;
+    T.nPts = T.K[0] * T.K[1] * T.K[2];
+    T.scale = m.el_scale;
+    const size_t nPts = (size_t)T.nPts;
+    T.Qi = dev_alloc<long long>(nPts, true);
+    T.W = dev_alloc<double>(2 * nPts, true);
+    T.partial = dev_alloc<double>(nPts / kBlock, true);
+    {
+        std::vector<double> G;
+        aztot::spme_influence(m, G);
+        double* dG = dev_alloc<double>(nPts);
+        HIP_CHECK(hipMemcpy(dG, G.data(), sizeof(double) * nPts, hipMemcpyHostToDevice));
+        T.G = dG;
+    }
+    for (int a = 0; a < 3; a++)
+    {
+        std::vector<double> tw;
+        spme_twiddles(T.K[a], tw);
+        double* d = dev_alloc<double>(tw.size());
+        HIP_CHECK(hipMemcpy(d, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice));
+        T.tw[a] = d;
+    }
+    // the three passes of the transform (SpmeAxis, device_md.h): tiles of kSpmeTilePts points at the most
+    const int Kx = T.K[0], Ky = T.K[1], Kz = T.K[2];
+    auto log2i = [](int v) { int l = 0; while ((1 << l) < v) l++; return l; };
+    {
+        SpmeAxis& A = spmeAxis_[0];
+        A.N = Kx; A.logN = log2i(Kx); A.LT = std::min(kSpmeTilePts / Kx, Ky * Kz); A.contiguous = 1; A.tilesPerRow = 1;
+        A.nTiles = Ky * Kz / A.LT; A.outerStride = (int64_t)A.LT * Kx; A.elemStride = 1;
+    }
+    {
+        SpmeAxis& A = spmeAxis_[1];
+        A.N = Ky; A.logN = log2i(Ky); A.LT = std::min(kSpmeTilePts / Ky, Kx); A.contiguous = 0; A.tilesPerRow = Kx / A.LT;
+        A.nTiles = Kz * A.tilesPerRow; A.outerStride = (int64_t)Kx * Ky; A.elemStride = Kx;
+    }
+    {
+        SpmeAxis& A = spmeAxis_[2];
+        A.N = Kz; A.logN = log2i(Kz); A.LT = std::min(kSpmeTilePts / Kz, Kx); A.contiguous = 0; A.tilesPerRow = Kx / A.LT;
+        A.nTiles = Ky * A.tilesPerRow; A.outerStride = Kx; A.elemStride = (int64_t)Kx * Ky;
+    }
+    DevStats s;
+    HIP_CHECK(hipMemcpy(&s, dStats_, sizeof(DevStats), hipMemcpyDeviceToHost));
+    s.engCoulConst = m.engElec1;
+    HIP_CHECK(hipMemcpy(dStats_, &s, sizeof(DevStats), hipMemcpyHostToDevice));
+}
+
+// The stages of the mesh sum on the arrays as they stand, up to and including: 0 the spread (the integer mesh is left filled), 1 the forward transform
+// (the work mesh holds the spectrum), 2 the convolution (books engCoulRec) and the inverse transform (the work mesh holds phi)
+void Engine::spme_stage(int upTo)
+{
+    const SpmeTables& T = spme_;
+    const int gridAtoms = div_up(capacity_, kSpmeAtomsPerBlock), gridPts = T.nPts / kBlock;
+    timed("spme_spread", [&] {
+        if (T.order == 4) hipLaunchKernelGGL(k_spme_spread<4>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+        else if (T.order == 6) hipLaunchKernelGGL(k_spme_spread<6>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+        else hipLaunchKernelGGL(k_spme_spread<8>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+    });
+    if (upTo < 1) return;
+    timed("spme_fft_fwd", [&] {
+        hipLaunchKernelGGL(k_spme_to_complex, dim3(gridPts), dim3(kBlock), 0, stream_, T);
+        for (int a = 0; a < 3; a++) hipLaunchKernelGGL(k_spme_fft<false>, dim3(spmeAxis_[a].nTiles), dim3(kBlock), 0, stream_, T.W, T.tw[a], spmeAxis_[a]);
+    });
+    if (upTo < 2) return;
+    timed("spme_convolve", [&] {
+        hipLaunchKernelGGL(k_spme_convolve, dim3(gridPts), dim3(kBlock), 0, stream_, T);
+        hipLaunchKernelGGL(k_spme_energy, dim3(1), dim3(kBlock), 0, stream_, T, dStats_);
+    });
+    timed("spme_fft_inv", [&] {
+        for (int a = 2; a >= 0; a--) hipLaunchKernelGGL(k_spme_fft<true>, dim3(spmeAxis_[a].nTiles), dim3(kBlock), 0, stream_, T.W, T.tw[a], spmeAxis_[a]);
+    });
+}
+
+// the reciprocal part of 'elec spme', at launch_ewald's place in the step: energy into DevStats::engCoulRec, forces added to what the pair kernel wrote
+void Engine::launch_spme()
+{
+    spme_stage(2);
+    const SpmeTables& T = spme_;
+    const int gridAtoms = div_up(capacity_, kSpmeAtomsPerBlock);
+    timed("spme_gather", [&] {
+        if (T.order == 4) hipLaunchKernelGGL(k_spme_gather<4>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+        else if (T.order == 6) hipLaunchKernelGGL(k_spme_gather<6>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+        else hipLaunchKernelGGL(k_spme_gather<8>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, S_, cur(), dCounts_, T);
+    });
+    check_launch("SPME kernels");
+}
+
+long long Engine::spme_mesh(int which, void* out, long long cap)
+{
+    if (!hasSpme_) throw ArgError("aztot_spme_mesh: the model of this handle has no 'elec spme'");
+    if (which < AZTOT_SPME_CHARGE || which > AZTOT_SPME_POTENTIAL) throw ArgError("aztot_spme_mesh: which is AZTOT_SPME_CHARGE, _SPECTRUM or _POTENTIAL");
+    const long long words = which == AZTOT_SPME_CHARGE ? (long long)spme_.nPts : 2LL * spme_.nPts;
+    if (!out && cap == 0) return words;
+    if (!out || cap < words) throw ArgError("aztot_spme_mesh: the buffer is too small");
+    if (!failed_.empty()) throw std::runtime_error("this handle failed in an earlier call: " + failed_);
+    // the positions the handle holds are those of the last force evaluation; the stages run again on them (the same kernels, the same bits) without
+    // touching the forces, and leave the integer mesh clear as a force evaluation does
+    sync_all();
+    spme_stage(which);
+    if (which == AZTOT_SPME_CHARGE)
+    {
+        HIP_CHECK(hipMemcpyAsync(out, spme_.Qi, sizeof(long long) * (size_t)words, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemsetAsync(spme_.Qi, 0, sizeof(long long) * (size_t)words, stream_));
+    }
+    else HIP_CHECK(hipMemcpyAsync(out, spme_.W, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, stream_));
+    check_launch("SPME read-back");
+    sync();
+    return words;
+}
+
+long long Engine::spme_influence(double* out, long long cap)
+{
+    if (!hasSpme_) throw ArgError("aztot_spme_influence: the model of this handle has no 'elec spme'");
+    const long long words = spme_.nPts;
+    if (!out && cap == 0) return words;
+    if (!out || cap < words) throw ArgError("aztot_spme_influence: the buffer is too small");
+    HIP_CHECK(hipMemcpy(out, spme_.G, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost));
+    return words;
+}
+
 void Engine::upload_initial()
 {
     const Model& m = model_;
@@ -1289,7 +1429,8 @@ void Engine::sort_and_forces(const StepPlan& plan)
     }
     launch_pair(plan);
     if (hasEwald_) launch_ewald();
-    if (hasBonded_ && plan.withBonded)      // exec_bondlist + exec_anglelist, main.cpp:101-104 (GPU path: main.cu:307-312,353-363)
+    if (hasSpme_) launch_spme();
+    if (hasBonded_ && plan.withBonded)     // exec_bondlist + exec_anglelist, main.cpp:101-104 (GPU path: main.cu:307-312,353-363)
         timed("bonded", [&] {
             if (nranks_ > 1)
                 hipLaunchKernelGGL(k_bonded<true>, dim3(gridAtoms), dim3(kBlock), 0, stream_, P_, cur(), dCounts_, bonded_, dPartials_, maxBlocks_);

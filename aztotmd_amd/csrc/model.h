@@ -28,7 +28,10 @@ constexpr int kMaxSpecies = 15;                            // defines.h:14 MX_SP
 constexpr int kNumUnitVectors = 3072;                      // cuTemp.h:4 nUvect
 constexpr int kEwaldKMax = 48;                             // k-vectors per axis: the Ewald kernels keep kx + ky + kz harmonics x 1 KiB in LDS (<= 160 KiB, checked in upload_ewald; reference: NKVEC_MX 100)
 
-struct Species                                             // Spec, dataStruct.h:244-291
+constexpr int kSpmeMeshMin = 8, kSpmeMeshMax = 256;        // 'elec spme': a mesh axis is a power of two in this range (a line of the transform fits 4 KiB of LDS)
+constexpr double kSpmeChargeCap = 4194304.0;               // 2^22: n_atoms * max|q| stays below it, so that the mesh's 64-bit sums of 2^-40 e cannot overflow
+
+struct Species                                          // Spec, dataStruct.h:244-291
 {
     std::string name, nucleus;
     double mass = 0;        // internal units (amu * m_scale)
@@ -138,6 +141,9 @@ struct Model
     double mr4a2 = 0, rkcut2 = 0;      // prepare_elec elec.cpp:382-394
     double engElec1 = 0;               // constant part of the Ewald sum (ewald_const elec.cpp:144-164)
     std::vector<KVec> kvecs;
+    // 'elec spme rReal alpha Kx Ky Kz order' (ours): smooth particle-mesh Ewald; real-space and constant parts are those of 'elec pme'
+    int spme_mesh[3] = {0, 0, 0};      // mesh points per axis: a power of two in kSpmeMeshMin .. kSpmeMeshMax
+    int spme_order = 0;                // B-spline order: 4, 6 or 8
     // TStat (temperature.h:15)
     int tstat_type = AZTOT_TSTAT_NONE;
     double Temp = 0, tau = 0, tKin = 0;
@@ -179,6 +185,10 @@ void add_angle_type(Model& m, int central, int type, double k, double cos0);
 // raw user vdw line -> prepared potential (read_vdw, vdw.cpp:261-299)
 PairPot prepare_vdw(int type, double rcut, const double p[5]);
 void center_box(Model& m);   // box.cpp:337-384
+// 'elec spme' (a finished model): the influence function G(m) = exp(-k^2 / 4 alpha^2) / k^2 * b_x b_y b_z over the whole mesh (x fastest, G(0) = 0), in long
+// double, rounded to double; and one axis' forward twiddles exp(-2 pi i k / K), k = 0 .. K - 1, as (cos, -sin) pairs
+void spme_influence(const Model& m, std::vector<double>& G);
+void spme_twiddles(int K, std::vector<double>& tw);
 
 // tables of the radiative thermostat (temperature.cpp:28-89, 165-223) with the counter-based RNG
 void photon_engs(int n, double* engs, double T, uint64_t seed);

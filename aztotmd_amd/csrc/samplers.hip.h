@@ -521,6 +521,7 @@ void Samplers::stress_setup()
     need_one_gpu("pressure tensors");
     if (!model_.bondA.empty() || !model_.angC.empty()) throw std::runtime_error("out of scope: stress: the virial of bonds and angles is not built (the model has bonded terms)");
     if (model_.elec_type == AZTOT_ELEC_EWALD) throw std::runtime_error("out of scope: stress: the reciprocal-space virial of 'elec pme' is not built");
+    if (model_.elec_type == AZTOT_ELEC_SPME) throw std::runtime_error("out of scope: stress: the reciprocal-space virial of 'elec spme' is not built");
     StressState T;
     const int N = model_.nAt;
     T.isSetUp = true;

@@ -15,6 +15,24 @@ namespace {
 
 [[noreturn]] void fail(const std::string& msg) { throw std::runtime_error(msg); }
 
+// 'elec spme': what the mesh kernels are built for (spme.hip.h); the message names the offending value
+void check_spme(const Model& m)
+{
+    for (int k = 0; k < 3; k++)
+    {
+        const int K = m.spme_mesh[k];
+        if (K < kSpmeMeshMin || K > kSpmeMeshMax || (K & (K - 1)) != 0)
+            fail("ERROR[404] 'elec spme': mesh axis " + std::to_string(k) + " = " + std::to_string(K) + " is not a power of two in " + std::to_string(kSpmeMeshMin) + ".." +
+                 std::to_string(kSpmeMeshMax));
+    }
+    if (m.spme_order != 4 && m.spme_order != 6 && m.spme_order != 8)
+        fail("ERROR[404] 'elec spme': order = " + std::to_string(m.spme_order) + " is not 4, 6 or 8");
+    for (int k = 0; k < 3; k++)
+        if (m.spme_order > m.spme_mesh[k])
+            fail("ERROR[404] 'elec spme': order = " + std::to_string(m.spme_order) + " exceeds mesh axis " + std::to_string(k) + " = " + std::to_string(m.spme_mesh[k]));
+    if (!(m.alpha > 0)) fail("ERROR[404] 'elec spme': alpha = " + std::to_string(m.alpha) + " is not positive");
+}
+
 struct File
 {
     FILE* f = nullptr;
@@ -325,6 +343,13 @@ void read_sim(const std::string& dir, Model& m)
         m.elec_type = AZTOT_ELEC_EWALD;
         if (std::fscanf(f, " %lf %lf %d %d %d", &m.rReal, &m.alpha, &m.ewald_k[0], &m.ewald_k[1], &m.ewald_k[2]) != 5)
             fail("ERROR[404] malformed 'elec pme'");
+    }
+    else if (std::strcmp(s, "spme") == 0)
+    {   // our directive: smooth particle-mesh Ewald, 'elec spme rReal alpha Kx Ky Kz order'
+        m.elec_type = AZTOT_ELEC_SPME;
+        if (std::fscanf(f, " %lf %lf %d %d %d %d", &m.rReal, &m.alpha, &m.spme_mesh[0], &m.spme_mesh[1], &m.spme_mesh[2], &m.spme_order) != 6)
+            fail("ERROR[404] malformed 'elec spme' (elec spme <rReal> <alpha> <Kx> <Ky> <Kz> <order>)");
+        check_spme(m);
     }
     else if (std::strcmp(s, "fenn") == 0)
     {
@@ -748,10 +773,13 @@ void finish_model(Model& m, uint64_t seed)
 {
     // prepare_elec: elec.cpp:371-406
     m.kvecs.clear(); m.engElec1 = 0.0;
-    if (m.elec_type == AZTOT_ELEC_EWALD)
-    {   // 'elec pme' is a plain Ewald sum in the reference (ewald_rec elec.cpp:167-335; GPU twin recip_ewald + ewald_force cuElec.cu:151-382)
+    if (m.elec_type == AZTOT_ELEC_EWALD || m.elec_type == AZTOT_ELEC_SPME)
+    {   // 'elec pme' is a plain Ewald sum in the reference (ewald_rec elec.cpp:167-335; GPU twin recip_ewald + ewald_force cuElec.cu:151-382);
+        // 'elec spme' (ours) shares its constants, its real-space term and its constant term, and replaces the k-vector list by a mesh
+        const bool spme = m.elec_type == AZTOT_ELEC_SPME;
         const int kx = m.ewald_k[0], ky = m.ewald_k[1], kz = m.ewald_k[2];
-        if (kx < 1 || ky < 1 || kz < 1 || kx > kEwaldKMax || ky > kEwaldKMax || kz > kEwaldKMax)
+        if (spme) check_spme(m);
+        else if (kx < 1 || ky < 1 || kz < 1 || kx > kEwaldKMax || ky > kEwaldKMax || kz > kEwaldKMax)
             fail("ERROR[404] 'elec pme' needs 1 <= kx, ky, kz <= " + std::to_string(kEwaldKMax) + " k-vectors per axis");
         for (int k = 0; k < 3; k++) if (!(m.L[k] > 0)) fail("ERROR[008] box lengths must be positive");
         if (!(m.alpha > 0)) fail("ERROR[404] 'elec pme' needs a positive alpha");
@@ -781,7 +809,7 @@ void finish_model(Model& m, uint64_t seed)
         // the k-vector list in the order ewald_rec visits it (half space: l >= 0; m >= 0 when l == 0; n >= 1 when l == m == 0);
         // same table the GPU reference builds on the host, cuInit.cu:1017-1046
         int mmin = 0, nmin = 1;
-        for (int l = 0; l < kx; l++)
+        for (int l = 0; l < (spme ? 0 : kx); l++)
         {
             const double rkx = l * twopi * ra;
             for (int mm = mmin; mm < ky; mm++)
@@ -878,6 +906,57 @@ void finish_model(Model& m, uint64_t seed)
     }
 }
 
+void spme_twiddles(int K, std::vector<double>& tw)
+{
+    const long double twopi = 2.0L * std::acos(-1.0L);
+    tw.resize(2 * (size_t)K);
+    for (int k = 0; k < K; k++)
+    {
+        const long double a = twopi * (long double)k / (long double)K;
+        tw[2 * k] = (double)std::cos(a); tw[2 * k + 1] = (double)(-std::sin(a));
+    }
+}
+
+void spme_influence(const Model& m, std::vector<double>& G)
+{
+    const int p = m.spme_order;
+    const int K[3] = {m.spme_mesh[0], m.spme_mesh[1], m.spme_mesh[2]};
+    // M_p at the integers 0 .. p - 1 by the recurrence M_n(u) = (u M_{n-1}(u) + (n - u) M_{n-1}(u - 1)) / (n - 1)
+    std::vector<long double> M(p, 0.0L);
+    M[1] = 1.0L;
+    for (int n = 3; n <= p; n++)
+        for (int j = n - 1; j >= 1; j--) M[j] = ((long double)j * M[j] + (long double)(n - j) * M[j - 1]) / (long double)(n - 1);
+    // the phases of the spline moduli are those of the discrete transform itself: the full pi, not the model's truncated one
+    const long double twopiExact = 2.0L * std::acos(-1.0L);
+    std::vector<long double> b[3], kk[3];
+    for (int a = 0; a < 3; a++)
+    {
+        b[a].resize(K[a]); kk[a].resize(K[a]);
+        for (int mi = 0; mi < K[a]; mi++)
+        {
+            long double re = 0.0L, im = 0.0L;
+            for (int k = 0; k <= p - 2; k++)
+            {
+                const long double arg = twopiExact * (long double)((long long)mi * k % K[a]) / (long double)K[a];
+                re += M[k + 1] * std::cos(arg); im += M[k + 1] * std::sin(arg);
+            }
+            b[a][mi] = 1.0L / (re * re + im * im);
+            const int ms = mi <= K[a] / 2 ? mi : mi - K[a];
+            kk[a][mi] = 2.0L * (long double)units::pi * (long double)ms / (long double)m.L[a];
+        }
+    }
+    const long double r4a2 = 1.0L / (4.0L * (long double)m.alpha * (long double)m.alpha);
+    G.resize((size_t)K[0] * K[1] * K[2]);
+    for (int z = 0; z < K[2]; z++)
+        for (int y = 0; y < K[1]; y++)
+            for (int x = 0; x < K[0]; x++)
+            {
+                const long double k2 = kk[0][x] * kk[0][x] + kk[1][y] * kk[1][y] + kk[2][z] * kk[2][z];
+                const size_t g = ((size_t)z * K[1] + y) * K[0] + x;
+                G[g] = (x | y | z) == 0 ? 0.0 : (double)(std::exp(-k2 * r4a2) / k2 * b[0][x] * b[1][y] * b[2][z]);
+            }
+}
+
 void init_md(const std::string& dir, Model& m)
 {
     read_field(dir, m);
@@ -936,7 +1015,8 @@ void model_from_system(const aztot_system& sys, Model& m)
     m.nEq = c.nequil; m.freqEq = c.nequil ? c.eqfreq : 0;
     m.Temp = c.temperature; m.tstat_type = c.tstat_type; m.tau = c.tstat_tau;
     m.elec_type = c.elec_type; m.rReal = c.r_real; m.alpha = c.alpha;
-    for (int k = 0; k < 3; k++) m.ewald_k[k] = c.ewald_k[k];
+    for (int k = 0; k < 3; k++) { m.ewald_k[k] = c.ewald_k[k]; m.spme_mesh[k] = c.spme_mesh[k]; }
+    m.spme_order = c.spme_order;
     if (m.elec_type == AZTOT_ELEC_NONE) m.rReal = 0.0;
     if (!m.charged_spec && m.elec_type) m.elec_type = AZTOT_ELEC_NONE;
     m.r2Real = m.rReal * m.rReal;

@@ -14,7 +14,7 @@ import numpy as np
 VDW_TYPES = {"lnjs": 1, "buck": 2, "p746": 3, "bmhs": 4, "elin": 5, "einv": 6, "surk": 7}
 VDW_NAMES = {v: k for k, v in VDW_TYPES.items()}
 VDW_NPARAM = {1: 2, 2: 3, 3: 3, 4: 5, 5: 3, 6: 3, 7: 4}          # vdw.cpp:195
-ELEC_TYPES = {"none": 0, "dir": 1, "pme": 2, "fenn": 3}
+ELEC_TYPES = {"none": 0, "dir": 1, "pme": 2, "fenn": 3, "spme": 4}
 ELEC_NAMES = {v: k for k, v in ELEC_TYPES.items()}
 TSTAT_NAMES = {0: "none", 1: "nose", 2: "radi"}
 
@@ -216,6 +216,8 @@ def write_input_files(case, directory, stat=200):
             f.write("elec\tdir\t%r\n" % case["rReal"])
         elif et == "pme":
             f.write("elec\tpme\t%r\t%r\t%d\t%d\t%d\n" % ((case["rReal"], case["alpha"]) + tuple(int(v) for v in case["ewald_k"])))
+        elif et == "spme":              # ours: elec spme <rReal> <alpha> <Kx> <Ky> <Kz> <order>
+            f.write("elec\tspme\t%r\t%r\t%d\t%d\t%d\t%d\n" % ((case["rReal"], case["alpha"]) + tuple(int(v) for v in case["spme_mesh"]) + (int(case["spme_order"]),)))
         else:
             f.write("elec\t%s\t%r\t%r\n" % (et, case["rReal"], case["alpha"]))
         f.write("rdf\t8.0\t0.02\t1000000\t1000000\tnucl\n")

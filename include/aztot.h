@@ -31,7 +31,8 @@ extern "C" {
 /* pair potential ids: vdw.h:15-21 */
 enum { AZTOT_VDW_LJ = 1, AZTOT_VDW_BUCK = 2, AZTOT_VDW_746 = 3, AZTOT_VDW_BHM = 4, AZTOT_VDW_ELIN = 5, AZTOT_VDW_EINV = 6, AZTOT_VDW_SURK = 7 };
 /* electrostatics: elec.h:8-12 */
-enum { AZTOT_ELEC_NONE = 0, AZTOT_ELEC_DIRECT = 1, AZTOT_ELEC_EWALD = 2, AZTOT_ELEC_FENNEL = 3 };
+enum { AZTOT_ELEC_NONE = 0, AZTOT_ELEC_DIRECT = 1, AZTOT_ELEC_EWALD = 2, AZTOT_ELEC_FENNEL = 3,
+       AZTOT_ELEC_SPME = 4 };   /* ours: smooth particle-mesh Ewald, 'elec spme rReal alpha Kx Ky Kz order' (see aztot_spme_mesh below) */
 /* thermostats: temperature.h:10-12 */
 enum { AZTOT_TSTAT_NONE = 0, AZTOT_TSTAT_NOSE = 1, AZTOT_TSTAT_RADI = 2 };
 /* init_vel: dataStruct.h:7-10 */
@@ -74,6 +75,8 @@ typedef struct
     double cell_list;            /* desired cell edge */
     int32_t stat;                /* statistics period */
     int32_t ewald_k[3];          /* 'elec pme rReal alpha kx ky kz' (read_elec elec.cpp:33-38): k-vectors per axis, 1..48 (kEwaldKMax, csrc/model.h) */
+    int32_t spme_mesh[3];        /* 'elec spme rReal alpha Kx Ky Kz order' (ours): mesh points per axis, each a power of two in 8..256 */
+    int32_t spme_order;          /* ... and the B-spline order: 4, 6 or 8 */
 } aztot_control;
 
 /* array form of atoms.xyz + field.txt + control.txt (used by tests / bench; same state as aztot_init_md) */
@@ -642,6 +645,27 @@ int aztot_boo_qlm(aztot_md *md, double *qlm, int cap);
 int aztot_boo_counts(aztot_md *md, int64_t *samples, uint64_t *hist, double *sums, uint64_t *entered, int cap);
 /* bin centres (n_bins), density in hist's layout, mean in sums' layout; returns the size of density (each optional; cap counts density's entries) */
 int aztot_boo_values(aztot_md *md, double *centre, double *density, double *mean, int cap);
+
+/* ---- smooth particle-mesh Ewald: debug read-back ------------------------------------------------------ */
+/* 'elec spme' (AZTOT_ELEC_SPME) replaces the k-vector loop of 'elec pme' by a mesh; real-space and constant parts, and the statistics they are booked in
+   (engCoul, engCoulConst; the mesh part in engCoulRec), are those of 'elec pme'.  Orthorhombic box, mesh K = (Kx, Ky, Kz), spline order p:
+     u = K x / L per axis, f = floor(u), w = u - f; theta(j) = M_p(w + j), j = 0 .. p - 1 (M_p: cardinal B-spline) lands on mesh index (f - j) mod K
+     Q(g) = 2^-40 * sum over atoms of llrint(((q theta_x) theta_y) theta_z * 2^40): 64-bit integer sums, independent of the order of the atoms
+     G(m) = exp(-k^2 / 4 alpha^2) / k^2 * b_x b_y b_z, k = 2 pi m' / L (m' the signed index, pi the model's), b(m) = 1 / |sum_{k=0}^{p-2} M_p(k + 1) e^{2 pi i m k / K}|^2, G(0) = 0
+     engCoulRec = 1/2 scale sum_m G |FQ|^2 (FQ the forward DFT of Q; scale: aztot_model_query "spme"), phi = scale * unnormalised inverse DFT of G FQ (real part)
+     F_i,a = -q_i (K_a / L_a) sum_g phi(g) theta'_a theta_b theta_c over the atom's p^3 points; the net force is NOT removed
+   One GPU only: a slab handle (nranks > 1, loopback included) with such a model is refused with AZTOT_ERR_INPUT, and so is a model with
+   n_atoms * max|q| >= 2^22 (the integer sums could overflow).  aztot_stress_setup refuses it as it refuses 'elec pme'.
+   aztot_spme_mesh: a mesh of the last force evaluation (aztot_forces, or the last step), re-evaluated stage by stage from the positions the handle holds:
+     which = AZTOT_SPME_CHARGE    the integer charge mesh, int64_t[Kx Ky Kz], in units of 2^-40 e
+     which = AZTOT_SPME_SPECTRUM  its forward DFT, (re, im) pairs of doubles
+     which = AZTOT_SPME_POTENTIAL phi, (re, im) pairs of doubles (the forces use the real part)
+   Point (gx, gy, gz) is entry (gz * Ky + gy) * Kx + gx.  `cap` and the result count 8-byte words; out null and cap 0: the size alone; a shorter
+   buffer, an unknown `which` or a handle without an SPME model -> AZTOT_ERR_ARG. */
+enum { AZTOT_SPME_CHARGE = 0, AZTOT_SPME_SPECTRUM = 1, AZTOT_SPME_POTENTIAL = 2 };
+int64_t aztot_spme_mesh(aztot_md *md, int which, void *out, int64_t cap);
+/* the influence function G in the same layout, Kx Ky Kz doubles (built once on the host in long double, rounded to double); returns their number */
+int64_t aztot_spme_influence(aztot_md *md, double *out, int64_t cap);
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* per-kernel HIP-event times accumulated since the last reset (options.profile = 1).
